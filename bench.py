@@ -1,7 +1,18 @@
 """Benchmark: CDS bases extracted (+ translated) per second on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...        (one rank per GPU)
+
+A plain run does what the headline figure needs: it sets the job up, settles
+and warms up, times the K steps, writes the outputs of the last timed step
+when ``--dump-outputs DIR`` is given, and prints the JSON line.  Everything
+else the line can carry is measured or checked only with ``--full``: the
+oracle byte check (``parity``), the CPU baselines, the amd-smi snapshots and
+memory probes (``box_state``), the back-to-back / isolated / record-layout
+kernel timings, the quoted rocprofv3 and PMC figures, and the timed return
+of the outputs (pinned D2H, and the gather to rank 0 of a shared job).
+Without ``--full`` those fields of the line are null.
 
 ``python bench.py --gpus N`` with N > 1 and no WORLD_SIZE in the environment
 starts the N ranks itself (one child process per GPU, RANK / LOCAL_RANK /
@@ -22,7 +33,7 @@ configs[4] C5's six-frame job at any N).
     orf6_kernel, gather fused with the six-frame translation); all ranks
     launch concurrently, and the K steps are timed between a barrier +
     device synchronisation on both sides, max over ranks;
-  * returning the outputs is its own phase, timed once after the steps:
+  * returning the outputs is its own phase (``--full``), timed once after the steps:
     per-rank D2H into pinned host memory (the host is the consumer), and for
     N > 1 a gather of every rank's outputs to rank 0 over the collective
     backend, put back into global record order and checked.
@@ -566,10 +577,88 @@ def _rocprof_quote(config, kernel):
     return d
 
 
+DUMP_SAMPLE = 4 << 20    # elements of a byte output kept by --dump-outputs (float32: 16 MB)
+DUMP_BLOCKS = 1 << 16    # block sums over a whole byte output (float64: 0.5 MB)
+DUMP_TABLE = 1 << 20     # entries of an offset / length table kept (float64: 8 MB)
+DUMP_SEED = 20240607
+
+
+def _dump_table(t):
+    """An offset / length table as float64 (exact below 2^53): whole up to
+    DUMP_TABLE entries, else a fixed seeded sample of them in table order."""
+    t = np.asarray(t)
+    if len(t) > DUMP_TABLE:
+        rng = np.random.default_rng(DUMP_SEED)
+        t = t[np.sort(rng.integers(0, len(t), size=DUMP_TABLE))]
+    return t.astype(np.float64)
+
+
+def _dump_bytes(out, name, a):
+    """A uint8 output as float32: whole up to DUMP_SAMPLE elements, else a
+    fixed seeded sample of its positions, in position order, and beside it
+    ``<name>_blocksum``: float64 sums of DUMP_BLOCKS equal blocks that cover
+    every byte of the output."""
+    idx = None
+    if len(a) > DUMP_SAMPLE:
+        rng = np.random.default_rng(DUMP_SEED)
+        idx = np.sort(rng.integers(0, len(a), size=DUMP_SAMPLE))
+    out[name] = (a if idx is None else a[idx]).astype(np.float32)
+    if idx is not None:
+        edges = np.linspace(0, len(a), DUMP_BLOCKS + 1).astype(np.int64)[:-1]
+        out[name + '_blocksum'] = np.add.reduceat(a, edges, dtype=np.uint64).astype(np.float64)
+
+
+def dump_outputs(path, rank, world, plan, o6):
+    """``--dump-outputs``: what a caller of the timed path receives after its
+    last step, as float arrays in ``path/<name>.npy`` (``<name>_rank<r>`` for
+    the ranks of a multi-rank job, each its own shard).  The extraction job:
+    ``plan.fetch()``, the nucleotide and peptide bytes with their offset
+    tables, in record order.  The six-frame job: ``o6.fetch()``, the residue
+    bytes with the stream offsets and lengths; only the residues inside the
+    streams are kept (the padding between the 16-aligned streams is no
+    output: zeroed in a whole dump, never sampled).  The workload is seeded
+    and the samples are fixed, so two builds given the same arguments write
+    files that compare element for element."""
+    out = {}
+    if o6 is not None:
+        res, soff, slen = o6.fetch()
+        idx = None
+        if len(res) > DUMP_SAMPLE:
+            rng = np.random.default_rng(DUMP_SEED)
+            s = np.sort(rng.integers(0, len(slen), size=DUMP_SAMPLE))
+            s = s[slen[s] > 0]
+            pos = (rng.random(len(s)) * slen[s]).astype(np.uint64)
+            idx = (soff[s] + pos).astype(np.int64)
+        if idx is None:
+            # whole: padding bytes zeroed
+            keep = np.zeros(len(res) + 1, dtype=np.int32)
+            np.add.at(keep, soff[:-1].astype(np.int64), 1)
+            np.add.at(keep, (soff[:-1] + slen).astype(np.int64), -1)
+            out['residues'] = np.where(np.cumsum(keep[:-1]) > 0, res, 0).astype(np.float32)
+        else:
+            out['residues'] = res[idx].astype(np.float32)
+        out['stream_offsets'] = _dump_table(soff)
+        out['stream_lengths'] = _dump_table(slen)
+    else:
+        nuc, noff, pep, poff = plan.fetch()
+        if nuc is not None:
+            _dump_bytes(out, 'nucleotides', nuc)
+            out['nucleotide_offsets'] = _dump_table(noff)
+        if pep is not None:
+            _dump_bytes(out, 'peptides', pep)
+            out['peptide_offsets'] = _dump_table(poff)
+    os.makedirs(path, exist_ok=True)
+    suffix = '' if world == 1 else '_rank%d' % rank
+    for name, a in out.items():
+        np.save(os.path.join(path, name + suffix + '.npy'), a)
+    return {name + suffix: [str(a.dtype), int(a.size)] for name, a in out.items()}
+
+
 def run_job(args, dist, rank, local, world):
     import torch
 
     from magot_amd import _lib, engine, shard, synth
+    full = args.full
     strong = args.mode == 'strong'
     # one job over the process group (any world size, --dist at N=1): the
     # genome is broadcast from rank 0 and the outputs gathered back to it
@@ -668,11 +757,12 @@ def run_job(args, dist, rank, local, world):
 
     t_setup = time.perf_counter() - t_start
     # -- correctness of the measured configuration (each rank, its own shard) -----
-    parity = 'not checked'
+    verify = full and not args.no_verify
+    parity = 'not checked' if full else None
     launches_before = 0  # launches of the measured kernel before the timed steps
-    if multi and not args.no_verify:
+    if multi and verify:
         parity = 'checked on the gathered job (outputs_gather.parity)'
-    elif not args.no_verify:
+    elif verify:
         launches_before += 1
         t0 = time.perf_counter()
         ok = verify_orf6(w, plan, o6, mine) if c5 else verify_extract(w, plan, mine)
@@ -684,7 +774,7 @@ def run_job(args, dist, rank, local, world):
             else 'MISMATCH on %d rank(s)' % int(n_bad)
 
     # -- timed region ---------------------------------------------------------
-    record_box = rank == 0 and not args.no_box_state
+    record_box = full and rank == 0 and not args.no_box_state
     if record_box:
         smi0 = smi_snapshot(local)
         probe0 = memory_probe()
@@ -706,16 +796,22 @@ def run_job(args, dist, rank, local, world):
     elapsed_max = allreduce_max(dist, elapsed)
 
     # per-launch kernel duration from HIP events on the context stream (the
-    # kernel's own stream) around exactly the K timed launches; back-to-back
-    # and isolated launches after the timed region are reported beside it
+    # kernel's own stream) around exactly the K timed launches; with --full,
+    # back-to-back and isolated launches after the timed region are reported
+    # beside it
     timer = o6 if c5 else plan
     kernel_ms = ctx.elapsed_ms() / args.steps
+    dumped = None
+    if args.dump_outputs:
+        # the device buffers still hold what the last timed step wrote
+        dumped = dump_outputs(args.dump_outputs, rank, world, plan, o6)
+        barrier(dist)
     n_b2b = max(20, min(args.steps, 100))
-    kernel_b2b = timer.time_b2b(n_b2b)
-    kernel_iso = timer.time(10)
+    kernel_b2b = timer.time_b2b(n_b2b) if full else None
+    kernel_iso = timer.time(10) if full else None
     kernel_rec = None
     delivery = None
-    if outputs & engine.OUT_GENOME_ORDER and not args.no_layout_compare:
+    if full and outputs & engine.OUT_GENOME_ORDER and not args.no_layout_compare:
         # beside it, for transparency: the same job in record order (the
         # layout the reference's output has), given the same settle and
         # warm-up as the line's own plan, then timed back to back
@@ -743,24 +839,26 @@ def run_job(args, dist, rank, local, world):
     # -- returning the outputs (its own phase, once) -----------------------------
     phases = {'generate': t_gen, 'pack_h2d': t_pack, 'plan_h2d': t_plan}
     out_bytes = R if c5 else B + P
-    pin = torch.empty(max(int(o6.total if c5 else B + P), 1), dtype=torch.uint8,
-                      pin_memory=True)
-    ctx.sync()
-    barrier(dist)
-    t0 = time.perf_counter()
-    if c5:
-        o6.fetch_to(pin.data_ptr())
-    else:
-        plan.fetch_to(pin.data_ptr() if B else None,
-                      pin.data_ptr() + B if P else None)
-    t_d2h = allreduce_max(dist, time.perf_counter() - t0)
-    barrier(dist)
-    phases['outputs_d2h_pinned'] = t_d2h
-    del pin
+    t_d2h = None
+    if full:
+        pin = torch.empty(max(int(o6.total if c5 else B + P), 1), dtype=torch.uint8,
+                          pin_memory=True)
+        ctx.sync()
+        barrier(dist)
+        t0 = time.perf_counter()
+        if c5:
+            o6.fetch_to(pin.data_ptr())
+        else:
+            plan.fetch_to(pin.data_ptr() if B else None,
+                          pin.data_ptr() + B if P else None)
+        t_d2h = allreduce_max(dist, time.perf_counter() - t0)
+        barrier(dist)
+        phases['outputs_d2h_pinned'] = t_d2h
+        del pin
     gather = None
-    if multi:
+    if multi and full:
         gather = gather_outputs(args, dist, rank, world, w, plan, o6, shards, ctx)
-        if rank == 0 and not args.no_verify:
+        if rank == 0 and verify:
             parity = gather['parity']
     import resource
     rss_gb = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2.0 ** 20  # KiB -> GiB
@@ -785,15 +883,15 @@ def run_job(args, dist, rank, local, world):
 
     # -- roofline / traffic / baselines --------------------------------------------
     traffic = None
-    if world == 1 and os.path.exists(args.pmc_json):
+    if full and world == 1 and os.path.exists(args.pmc_json):
         with open(args.pmc_json) as fh:
             pmc = json.load(fh)
         if pmc.get('config') == args.config and pmc.get('kernel') == kernel_name:
             traffic = pmc.get('hbm_bytes_per_launch')
-    rp = _rocprof_quote(args.config, kernel_name) if world == 1 else None
+    rp = _rocprof_quote(args.config, kernel_name) if full and world == 1 else None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log('timing the CPU baseline on a bounded sample ...')
         if c5:
             cpu = cpu_baseline(w, args.cpu_sample_bases / 10, orfs=True)
@@ -849,7 +947,7 @@ def run_job(args, dist, rank, local, world):
                                              'timed launches, / K (max over ranks)',
                          'kernel_ms_b2b': kernel_b2b,
                          'kernel_ms_b2b_source': 'HIP events around %d back-to-back launches '
-                                                 'after the timed region' % n_b2b,
+                                                 'after the timed region' % n_b2b if full else None,
                          'kernel_ms_isolated': kernel_iso,
                          'kernel_ms_b2b_record_layout': kernel_rec,
                          'record_order_delivery': delivery,
@@ -872,6 +970,8 @@ def run_job(args, dist, rank, local, world):
             'box_state': boxrec,
             'outputs_d2h_bases_per_s': total_bases / t_d2h if t_d2h else None,
             'output_bytes_rank0': out_bytes,
+            'full': full,
+            'outputs_dumped': dumped,
         }
         if rehearse:
             rec['rehearsal'] = rehearse
@@ -1017,6 +1117,13 @@ def main(argv=None):
     # the steady state.
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--full', action='store_true',
+                    help='also check the outputs against the CPU oracle and measure everything '
+                         'beside the headline figure (CPU baselines, box state, further kernel '
+                         'timings, the return of the outputs); the --no-* options narrow it')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / '
+                         'float64; large outputs as a fixed seeded sample plus block sums)')
     ap.add_argument('--settle-ms', type=float, default=100.0,
                     help='back-to-back launches before the warm-up steps (power-state settle)')
     ap.add_argument('--config', default='C3', choices=CONFIGS)

@@ -13,7 +13,7 @@ for i in 1 2 3; do
   k=0
   for e in "${ENVS[@]}"; do
     k=$((k+1))
-    env $e timeout -k 10 300 python bench.py --no-verify --no-cpu-baseline "$@" > $OUT/v$k.$i.json 2> $OUT/v$k.$i.err || { tail -20 $OUT/v$k.$i.err; exit 1; }
+    env $e timeout -k 10 300 python bench.py --full --no-verify --no-cpu-baseline "$@" > $OUT/v$k.$i.json 2> $OUT/v$k.$i.err || { tail -20 $OUT/v$k.$i.err; exit 1; }
     python3 -c "import json;d=json.load(open('$OUT/v$k.$i.json'));print('[$e]', '%.4f'%d['roofline']['kernel_ms'], '%.4f'%d['ms_per_step'])"
   done
 done

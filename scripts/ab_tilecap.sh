@@ -17,7 +17,7 @@ for rep in 1 2; do
       [ $what != full ] && args="$args --rehearse-shard $what"
       envs=""; [ $cap != 0 ] && envs="MAGOT_EXTRACT_TILE_BYTES=$cap"
       f=$OUT/${what/:/_}.$cap.$rep.json
-      env $envs timeout -k 10 300 python bench.py $args > $f 2> $OUT/err || { tail -20 $OUT/err; exit 1; }
+      env $envs timeout -k 10 300 python bench.py --full $args > $f 2> $OUT/err || { tail -20 $OUT/err; exit 1; }
       python3 -c "import json;d=json.load(open('$f'));r=d['roofline'];print('$what cap=$cap', round(d['ms_per_step'],5), round(r['kernel_ms'],5))"
     done
   done

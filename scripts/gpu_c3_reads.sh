@@ -10,7 +10,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 TAG=$1; VAR=$2
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-B="python bench.py --no-verify --no-cpu-baseline --no-box-state"
+B="python bench.py --full --no-verify --no-cpu-baseline --no-box-state"
 for i in 1 2 3; do
   for v in base var; do
     lib=magot_amd/libmagot.so; [ $v = var ] && lib=$VAR
@@ -25,7 +25,7 @@ for v in base var sorted; do
   extra=""; [ $v = sorted ] && extra="--order sorted"
   for grp in FETCH_SIZE WRITE_SIZE; do
     rm -rf $OUT/pmc_$v/$grp
-    MAGOT_LIB=$lib timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc_$v/$grp -o pmc -- python bench.py --steps 5 --warmup 1 --settle-ms 0 --no-verify --no-cpu-baseline --no-box-state $extra > $OUT/pmc_$v.$grp.log 2>&1 || { echo "pmc $v $grp failed"; tail -3 $OUT/pmc_$v.$grp.log; exit 1; }
+    MAGOT_LIB=$lib timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc_$v/$grp -o pmc -- python bench.py --full --steps 5 --warmup 1 --settle-ms 0 --no-verify --no-cpu-baseline --no-box-state $extra > $OUT/pmc_$v.$grp.log 2>&1 || { echo "pmc $v $grp failed"; tail -3 $OUT/pmc_$v.$grp.log; exit 1; }
   done
 done
 echo done

@@ -10,7 +10,7 @@ for e in "$1" "$2"; do
   i=$((i+1)); j=0
   for grp in "FETCH_SIZE" "SQ_INSTS_VALU SQ_WAVES SQ_INSTS_VMEM" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
     j=$((j+1)); rm -rf $OUT/v${i}_$j
-    env $e timeout -k 10 120 rocprofv3 --pmc $grp --output-format csv -d $OUT/v${i}_$j -o pmc -- python bench.py --steps 5 --warmup 1 --settle-ms 0 --no-verify --no-cpu-baseline > $OUT/v${i}_$j.log 2>&1 || { tail -5 $OUT/v${i}_$j.log; exit 1; }
+    env $e timeout -k 10 120 rocprofv3 --pmc $grp --output-format csv -d $OUT/v${i}_$j -o pmc -- python bench.py --full --steps 5 --warmup 1 --settle-ms 0 --no-verify --no-cpu-baseline > $OUT/v${i}_$j.log 2>&1 || { tail -5 $OUT/v${i}_$j.log; exit 1; }
   done
   echo "[$e]"; python scripts/pmc_summary.py $OUT | python3 -c "
 import json,sys; d=json.load(sys.stdin)

@@ -29,11 +29,11 @@ for st in $STAGES; do
 done
 if has dist; then
   # the C3 job through the multi-GPU path at N=1: RCCL process group of one rank
-  NCCL_DEBUG=INFO timeout -k 10 600 python $BENCH --dist --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_dist_c3.json 2> $OUT/dist_c3.err || { tail -30 $OUT/dist_c3.err; exit 1; }
+  NCCL_DEBUG=INFO timeout -k 10 600 python $BENCH --full --dist --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_dist_c3.json 2> $OUT/dist_c3.err || { tail -30 $OUT/dist_c3.err; exit 1; }
   cut -c1-600 $OUT/bench_dist_c3.json
 fi
 if has dist5; then
-  NCCL_DEBUG=INFO timeout -k 10 900 python $BENCH --dist --config C5 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_dist_c5.json 2> $OUT/dist_c5.err || { tail -30 $OUT/dist_c5.err; exit 1; }
+  NCCL_DEBUG=INFO timeout -k 10 900 python $BENCH --full --dist --config C5 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_dist_c5.json 2> $OUT/dist_c5.err || { tail -30 $OUT/dist_c5.err; exit 1; }
   cut -c1-600 $OUT/bench_dist_c5.json
 fi
 if has fetchcal; then
@@ -49,7 +49,7 @@ fi
 for cfg in C3 C5; do
   if has gloo8${cfg,,}; then
     # the strong job over 8 ranks sharing this card (gloo, device tensors as under nccl)
-    MAGOT_DIST_BACKEND=gloo MAGOT_COLLECTIVE_TENSORS=cuda timeout -k 10 900 python $BENCH --gpus 8 --config $cfg --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_gloo8_$cfg.json 2> $OUT/gloo8_$cfg.err || { tail -30 $OUT/gloo8_$cfg.err; exit 1; }
+    MAGOT_DIST_BACKEND=gloo MAGOT_COLLECTIVE_TENSORS=cuda timeout -k 10 900 python $BENCH --full --gpus 8 --config $cfg --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_gloo8_$cfg.json 2> $OUT/gloo8_$cfg.err || { tail -30 $OUT/gloo8_$cfg.err; exit 1; }
     grep '^{' $OUT/bench_gloo8_$cfg.json | cut -c1-300
   fi
 done
@@ -85,24 +85,24 @@ if has slow; then
   tail -1 $OUT/pytest_gpu_slow.log
 fi
 if has bench; then
-  timeout -k 10 900 python $BENCH > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+  timeout -k 10 900 python $BENCH --full > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
   cat $OUT/bench.json
 fi
 if has driver; then
-  timeout -k 10 300 python $BENCH --steps 20 --warmup 5 > $OUT/bench_driver_cfg_20_5.json 2> $OUT/driver.err || { tail -30 $OUT/driver.err; exit 1; }
+  timeout -k 10 300 python $BENCH --full --steps 20 --warmup 5 > $OUT/bench_driver_cfg_20_5.json 2> $OUT/driver.err || { tail -30 $OUT/driver.err; exit 1; }
   cat $OUT/bench_driver_cfg_20_5.json
 fi
 if has c2; then
-  timeout -k 10 300 python $BENCH --config C2 > $OUT/bench_c2.json 2> $OUT/c2.err || { tail -30 $OUT/c2.err; exit 1; }
+  timeout -k 10 300 python $BENCH --full --config C2 > $OUT/bench_c2.json 2> $OUT/c2.err || { tail -30 $OUT/c2.err; exit 1; }
   cat $OUT/bench_c2.json
 fi
 if has c5; then
-  timeout -k 10 600 python $BENCH --config C5 > $OUT/bench_c5.json 2> $OUT/c5.err || { tail -30 $OUT/c5.err; exit 1; }
+  timeout -k 10 600 python $BENCH --full --config C5 > $OUT/bench_c5.json 2> $OUT/c5.err || { tail -30 $OUT/c5.err; exit 1; }
   cat $OUT/bench_c5.json
 fi
 if has multi5; then
   # the C5 job over two ranks sharing the card (gloo): six-frame outputs gathered back
-  MAGOT_DIST_BACKEND=gloo MAGOT_COLLECTIVE_TENSORS=cuda timeout -k 10 900 python $BENCH --gpus 2 --config C5 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_gloo2_c5.json 2> $OUT/gloo2_c5.err || { tail -30 $OUT/gloo2_c5.err; exit 1; }
+  MAGOT_DIST_BACKEND=gloo MAGOT_COLLECTIVE_TENSORS=cuda timeout -k 10 900 python $BENCH --full --gpus 2 --config C5 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_gloo2_c5.json 2> $OUT/gloo2_c5.err || { tail -30 $OUT/gloo2_c5.err; exit 1; }
   grep '^{' $OUT/bench_gloo2_c5.json | cut -c1-400
 fi
 if has e2e; then
@@ -142,28 +142,28 @@ fi
 if has multi; then
   # two ranks launched by bench itself, sharing the one card over gloo (the
   # C4 orchestration; the driver's 8-GPU node runs it over RCCL)
-  MAGOT_DIST_BACKEND=gloo MAGOT_COLLECTIVE_TENSORS=cuda timeout -k 10 600 python $BENCH --gpus 2 --steps 50 --warmup 5 --no-cpu-baseline > $OUT/bench_gloo2.json 2> $OUT/gloo2.err || { tail -30 $OUT/gloo2.err; exit 1; }
+  MAGOT_DIST_BACKEND=gloo MAGOT_COLLECTIVE_TENSORS=cuda timeout -k 10 600 python $BENCH --full --gpus 2 --steps 50 --warmup 5 --no-cpu-baseline > $OUT/bench_gloo2.json 2> $OUT/gloo2.err || { tail -30 $OUT/gloo2.err; exit 1; }
   grep '^{' $OUT/bench_gloo2.json
 fi
 if has kt; then
   # the bench line under the kernel trace; rocprof_summary.py --timed averages
   # exactly the line's K timed dispatches (roofline.timed_launches)
   rm -rf $OUT/kt
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $BENCH --no-box-state > $OUT/kt.json 2> $OUT/kt.err || { tail -30 $OUT/kt.err; exit 1; }
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $BENCH --full --no-box-state > $OUT/kt.json 2> $OUT/kt.err || { tail -30 $OUT/kt.err; exit 1; }
   grep -h extract_kernel $OUT/kt/kt_kernel_stats.csv
   cat $OUT/kt.json
 fi
 if has rehearse; then
   # one GPU's share of the K-GPU C4 job (bench.py --rehearse-shard K:r)
   for kr in 2:0 4:0 8:0 8:7; do
-    timeout -k 10 300 python $BENCH --rehearse-shard $kr --steps 300 --no-cpu-baseline > $OUT/rehearse_${kr/:/_}.json 2> $OUT/rehearse.err || { tail -20 $OUT/rehearse.err; exit 1; }
+    timeout -k 10 300 python $BENCH --full --rehearse-shard $kr --steps 300 --no-cpu-baseline > $OUT/rehearse_${kr/:/_}.json 2> $OUT/rehearse.err || { tail -20 $OUT/rehearse.err; exit 1; }
     python3 -c "import json;d=json.load(open('$OUT/rehearse_${kr/:/_}.json'));r=d['roofline'];print('$kr', round(d['ms_per_step'],5), round(r['kernel_ms'],5), round(r['frac'],4), d['parity'][:20])"
   done
 fi
 for cfg in C5 C2; do
   if has kt${cfg:1}; then
     rm -rf $OUT/kt_$cfg
-    timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$cfg -o kt -- python $BENCH --config $cfg --no-cpu-baseline --no-box-state > $OUT/kt_$cfg.json 2> $OUT/kt_$cfg.err || { tail -30 $OUT/kt_$cfg.err; exit 1; }
+    timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$cfg -o kt -- python $BENCH --full --config $cfg --no-cpu-baseline --no-box-state > $OUT/kt_$cfg.json 2> $OUT/kt_$cfg.err || { tail -30 $OUT/kt_$cfg.err; exit 1; }
     grep -h "orf6_kernel\|extract_kernel" $OUT/kt_$cfg/kt_kernel_stats.csv
   fi
 done
@@ -175,7 +175,7 @@ if has pmc; then
              "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
     i=$((i+1))
     rm -rf $OUT/pmc$i
-    timeout -k 10 600 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc$i -o pmc -- python bench.py --steps 5 --warmup 1 --no-verify --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/pmc$i.log 2>&1
+    timeout -k 10 600 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc$i -o pmc -- python bench.py --full --steps 5 --warmup 1 --no-verify --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/pmc$i.log 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "pmc group $i failed rc=$rc"; tail -3 $OUT/pmc$i.log; [ $rc -ge 124 ] && exit 1; fi
   done
@@ -188,7 +188,7 @@ if has traffic; then
     c=${cfg%%:*}
     for grp in FETCH_SIZE WRITE_SIZE; do
       rm -rf $OUT/traffic_$c/$grp
-      timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/traffic_$c/$grp -o pmc -- python bench.py --config $c --steps 5 --warmup 1 --settle-ms 0 --no-verify --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/traffic_$c.$grp.log 2>&1 || { echo "traffic $c $grp failed"; tail -3 $OUT/traffic_$c.$grp.log; exit 1; }
+      timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/traffic_$c/$grp -o pmc -- python bench.py --full --config $c --steps 5 --warmup 1 --settle-ms 0 --no-verify --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/traffic_$c.$grp.log 2>&1 || { echo "traffic $c $grp failed"; tail -3 $OUT/traffic_$c.$grp.log; exit 1; }
     done
   done
   echo traffic ok

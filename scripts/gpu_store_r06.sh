@@ -14,7 +14,7 @@ for v in SC1 NT_SC1 SC0_SC1; do
 done
 # one verified line per variant first (same bytes, different cache policy)
 for n in sc1 nt_sc1 sc0_sc1; do
-  MAGOT_LIB=scripts/lib_$n.so timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/verify_$n.json 2> $OUT/verify_$n.err || { tail -20 $OUT/verify_$n.err; exit 1; }
+  MAGOT_LIB=scripts/lib_$n.so timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/verify_$n.json 2> $OUT/verify_$n.err || { tail -20 $OUT/verify_$n.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/verify_$n.json'));print('$n', d['parity'])"
 done
 bash scripts/ab_pmc_libs.sh $OUT extract_kernel "scripts/lib_base.so scripts/lib_sc1.so scripts/lib_nt_sc1.so scripts/lib_sc0_sc1.so" --no-layout-compare

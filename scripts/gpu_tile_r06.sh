@@ -20,7 +20,7 @@ bash scripts/build_patch_variant.sh lc6a1k $P -- -DMAGOT_EXP_LC=6 -DMAGOT_EXP_PP
 LIBS="scripts/lib_base.so scripts/lib_lc7a128.so scripts/lib_lc7a1k.so scripts/lib_lc8a1k.so scripts/lib_lc9a4k.so scripts/lib_lc6a1k.so"
 for lib in $LIBS; do
   n=$(basename $lib .so)
-  MAGOT_LIB=$lib timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/verify_$n.json 2> $OUT/verify_$n.err || { tail -20 $OUT/verify_$n.err; exit 1; }
+  MAGOT_LIB=$lib timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-box-state --no-layout-compare > $OUT/verify_$n.json 2> $OUT/verify_$n.err || { tail -20 $OUT/verify_$n.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/verify_$n.json'));print('$n', d['parity'], d['roofline']['kernel_ms'])"
 done
 bash scripts/ab_pmc_libs.sh $OUT extract_kernel "$LIBS" --no-layout-compare

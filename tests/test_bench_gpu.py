@@ -44,7 +44,82 @@ def _bench(args, env_extra=None):
     return json.loads(lines[0])
 
 
-COMMON = ['--steps', '5', '--warmup', '1', '--settle-ms', '5', '--no-cpu-baseline']
+PLAIN = ['--steps', '5', '--warmup', '1', '--settle-ms', '5']
+# the checks and the figures beside the headline one are behind --full
+COMMON = PLAIN + ['--full', '--no-cpu-baseline']
+
+# fields of the line that only a --full run fills
+FULL_ONLY = ('parity', 'cpu_baseline', 'box_state', 'outputs_d2h_bases_per_s')
+FULL_ONLY_ROOFLINE = ('traffic', 'kernel_ms_b2b', 'kernel_ms_isolated',
+                      'kernel_ms_b2b_record_layout', 'record_order_delivery',
+                      'rocprof_kernel_ms')
+
+
+def _small_workload():
+    sys.path.insert(0, ROOT)
+    import bench
+    from magot_amd import synth
+    return synth.make('small', seed=bench.shard_seed('small', 0), order='random')
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run: the headline figure over exactly --steps launches, nothing
+    measured or checked beside it, and --dump-outputs writes the record-order
+    outputs of the last timed step as float arrays, here equal to the oracle's."""
+    import numpy as np
+
+    import bench
+    from oracle import cds_oracle
+    d = _bench(['--gpus', '1', '--config', 'small', '--dump-outputs', str(tmp_path)] + PLAIN)
+    assert d['full'] is False and d['steps'] == 5 and d['warmup'] == 1
+    assert d['metric'] == 'CDS bases extracted+translated/sec' and d['unit'] == 'bases/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'u8'
+    assert d['ms_per_step'] > 0
+    assert d['value'] == pytest.approx(d['config']['cds_bases'] / (d['ms_per_step'] * 1e-3))
+    tl = d['roofline']['timed_launches']
+    assert tl['count'] == 5 and tl['first'] == d['settle']['launches'] + 1
+    assert 0 < d['roofline']['kernel_ms'] <= d['ms_per_step'] * 1.05
+    for k in FULL_ONLY:
+        assert d[k] is None, k
+    for k in FULL_ONLY_ROOFLINE:
+        assert d['roofline'][k] is None, k
+    assert 'outputs_d2h_pinned' not in d['phases_s']
+
+    got = {p.name[:-4]: np.load(str(p)) for p in tmp_path.iterdir()}
+    assert sorted(got) == ['nucleotide_offsets', 'nucleotides', 'peptide_offsets', 'peptides']
+    assert sorted(d['outputs_dumped']) == sorted(got)
+    assert got['nucleotides'].dtype == np.float32 and got['nucleotide_offsets'].dtype == np.float64
+    w = _small_workload()
+    ref, roff, st = cds_oracle.extract_workload(w, False)
+    assert not st.any()
+    assert np.array_equal(got['nucleotide_offsets'], roff.astype(np.float64))
+    assert np.array_equal(got['nucleotides'], ref.astype(np.float32))
+    pref, _, _ = cds_oracle.extract_workload(w, True)
+    assert bench._pep_matches(got['peptides'].astype(np.uint8),
+                              got['peptide_offsets'].astype(np.uint64), pref)
+
+
+def test_bench_plain_run_dumps_six_frame_outputs(tmp_path):
+    """--dump-outputs of the six-frame job: the streams of every record, all
+    six frames, equal to the oracle's translations; padding dumped as zero."""
+    import numpy as np
+
+    from oracle import cds_oracle
+    d = _bench(['--config', 'small5', '--dump-outputs', str(tmp_path)] + PLAIN)
+    assert d['full'] is False and d['parity'] is None
+    assert d['roofline']['kernel'] == 'orf6_kernel'
+    got = {p.name[:-4]: np.load(str(p)) for p in tmp_path.iterdir()}
+    assert sorted(got) == ['residues', 'stream_lengths', 'stream_offsets']
+    w = _small_workload()
+    ref, roff, st = cds_oracle.extract_workload(w, False)
+    assert not st.any()
+    out = got['residues'].astype(np.uint8)
+    soff = got['stream_offsets'].astype(np.uint64)
+    slen = got['stream_lengths'].astype(np.uint64)
+    assert len(slen) == 6 * w.n_tx and len(soff) == 6 * w.n_tx + 1
+    assert int(np.count_nonzero(out)) <= int(slen.sum()) == d['config']['residues_rank0']
+    bad, first = cds_oracle.orf6_compare(ref, roff, out, soff, slen, threads=2)
+    assert bad == 0, first
 
 
 def test_bench_one_rank():
