@@ -317,6 +317,22 @@ int magot_plan_layout(const magot_plan* p, uint64_t* nuc_start, uint64_t* pep_st
  * ceil(B/4) + B*[nuc] + P*[pep] + 16*E + 32*T. */
 uint64_t magot_plan_algorithmic_bytes(const magot_plan* p);
 
+/* Debug (no device): the packed per-tile descriptor blocks magot_plan_create
+ * uploads, from the planner's u64 tables.  ex_g / ex_out / tx_nuc / tx_pep as
+ * the planner builds them (interval start | flag bits 63..61, n+1 output
+ * offsets, record output / residue starts with their sentinel); tiles =
+ * n_tiles rows {u64 T0, T1, Q0, Q1; u32 e1, e2, j1, j2}; lane_chunks 3 or 6.
+ * geometry[3]: in, the inline interval / record rows of a block to force (0:
+ * the planner's choice for these tiles); out, the rows used and the block
+ * stride in bytes.  blocks receives stride bytes per tile, ovf_ex / ovf_tx
+ * the overflow rows (8 / 16 bytes each); n_ovf[0..1] their counts.
+ * blocks == NULL: geometry and counts only. */
+int magot_debug_tile_blocks(const uint64_t* ex_g, const uint64_t* ex_out, const uint64_t* tx_nuc,
+                            const uint64_t* tx_pep, uint64_t span, uint32_t lane_chunks,
+                            const void* tiles, uint64_t n_tiles, uint32_t* geometry, void* blocks,
+                            uint64_t* ovf_ex, uint64_t ovf_ex_cap, int64_t* ovf_tx,
+                            uint64_t ovf_tx_cap, uint64_t* n_ovf);
+
 /*
  * Raw-sequence batch ops over n byte strings (seq_off has n+1 entries).
  * Replaces: Sequence.reverse_compliment (genome.py:784-793).

@@ -48,6 +48,7 @@ EXPORTS = (
     'magot_genome_load_ex', 'magot_genome_wire_ranges', 'magot_genome_attach_wire',
     'magot_copy_segments', 'magot_ctx_mark', 'magot_ctx_elapsed', 'magot_orf6_copy_outputs',
     'magot_genome_wire_export', 'magot_genome_wire_import',
+    'magot_debug_tile_blocks',
 )
 
 ERR_ARG = -1
@@ -105,6 +106,10 @@ def _declare(lib):
         'magot_plan_device_outputs': (ctypes.c_int, [_vp, ctypes.POINTER(_vp),
                                                      ctypes.POINTER(_vp)]),
         'magot_plan_algorithmic_bytes': (ctypes.c_uint64, [_vp]),
+        'magot_debug_tile_blocks': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64,
+                                                   ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp,
+                                                   _vp, ctypes.c_uint64, _vp, ctypes.c_uint64,
+                                                   _vp]),
         'magot_revcomp_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp]),
         'magot_translate_sizes': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp]),
         'magot_translate_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,

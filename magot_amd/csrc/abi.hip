@@ -84,7 +84,11 @@ struct magot_plan {
   const uint64_t* d_nuc_off = nullptr;  // T+1
   const uint64_t* d_pep_off = nullptr;  // T+1
   uint64_t n_exons = 0, n_tx = 0;
-  uint64_t n_ex_c = 0;  // compacted (non-empty) intervals in args.ex_g / ex_out
+  uint64_t n_ex_c = 0;  // compacted (non-empty) intervals
+  // the interval table of a record-order plan (n_ex_c starts with flag bits,
+  // n_ex_c + 1 output offsets), for magot_plan_orf6: the device holds only
+  // the packed tile blocks
+  std::unique_ptr<uint64_t[]> host_ex_g, host_ex_out;
   bool executed = false;
 };
 
@@ -415,6 +419,29 @@ int upload_pieces(magot_ctx* ctx, char* dev, const std::vector<HostPiece>& piece
     }
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   return MAGOT_OK;
+}
+
+// As upload_pieces for rows that are generated, not copied: fill(lo, hi, dst)
+// writes items [lo, hi) of `item` bytes each to dst, from several host threads
+// straight into the pinned buffer that is uploaded next (no pageable copy of
+// the table and no second pass over it).
+template <class F>
+int upload_generated(magot_ctx* ctx, char* dev, uint64_t n, uint64_t item, unsigned threads, F fill) {
+  std::lock_guard<std::mutex> lock(ctx->pin_mu);
+  if (int rc = ensure_pin_ring(ctx)) return rc;
+  const uint64_t per = kPinRing / item;
+  for (uint64_t i0 = 0, k = 0; i0 < n; i0 += per, ++k) {
+    const int b = (int)(k & 1);
+    const uint64_t i1 = std::min(n, i0 + per);
+    MAGOT_HIP_TRY(hipEventSynchronize(ctx->pin_ev[b]));
+    uint8_t* ring = ctx->pin[b];
+    parallel_ranges(i1 - i0, (i1 - i0) * item >= (1ull << 20) ? threads : 1u,
+                    [&](uint64_t lo, uint64_t hi, unsigned) { fill(i0 + lo, i0 + hi, ring + lo * item); });
+    MAGOT_HIP_TRY(hipMemcpyAsync(dev + i0 * item, ring, (i1 - i0) * item, hipMemcpyHostToDevice,
+                                 ctx->stream));
+    MAGOT_HIP_TRY(hipEventRecord(ctx->pin_ev[b], ctx->stream));
+  }
+  return MAGOT_OK;  // in flight: the caller's next upload_pieces (or a stream sync) completes it
 }
 
 // Stream the contigs' bytes (FASTA line layout removed) into dev[0, total),
@@ -1222,8 +1249,7 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
     }
   }
   // interval rows in layout order (the record-order rows themselves when the
-  // layout is record order), one padding row past each table (the kernel
-  // prefetches clamped rows j <= n)
+  // layout is record order)
   HostBuf<uint64_t> ex_perm(by_genome ? Ec + 1 : 0), ex_out(Ec + 2);
   uint64_t* const ex_g = by_genome ? ex_perm.data() : w_g.data();
   parallel_ranges(T, nth, [&](uint64_t t0, uint64_t t1, unsigned) {
@@ -1395,6 +1421,34 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
     else tail.push_back(r);
   }
   std::copy(tail.begin(), tail.end(), tiles.begin() + n_first);
+  // the blocks' inline capacities, from what this plan's tiles stage
+  // (MAGOT_TILE_BLOCK_ROWS=ex,tx forces them: tests and A/Bs), and each tile's
+  // place in the overflow arrays (rows past a block's inline part)
+  uint32_t force_ex = 0, force_tx = 0;
+  if (const char* e = std::getenv("MAGOT_TILE_BLOCK_ROWS")) {
+    unsigned fe = 0, fx = 0;
+    if (sscanf(e, "%u,%u", &fe, &fx) == 2) {
+      force_ex = std::min(fe, kBlkExMax);
+      force_tx = std::min(fx, kBlkTxMax);
+    }
+  }
+  const TileGeometry geo = tile_geometry(tiles.data(), n_tiles, force_ex, force_tx);
+  std::vector<uint32_t> ovf_at(2 * (size_t)n_tiles);
+  uint64_t n_ovf_ex = 0, n_ovf_tx = 0;
+  for (uint32_t t = 0; t < n_tiles; ++t) {
+    if (tiles[t].T1 - tiles[t].T0 > 0xFFFFull || tiles[t].Q1 - tiles[t].Q0 > 0xFFFFull) {
+      set_error("magot_plan_create: internal tiling error (tile block fields)");
+      return MAGOT_ERR_STATE;
+    }
+    ovf_at[2 * (size_t)t] = (uint32_t)n_ovf_ex;
+    ovf_at[2 * (size_t)t + 1] = (uint32_t)n_ovf_tx;
+    n_ovf_ex += tile_ovf_ex(geo, tiles[t]);
+    n_ovf_tx += tile_ovf_tx(geo, tiles[t]);
+  }
+  if (n_ovf_ex >= 0xFFFFFFFFull || n_ovf_tx >= 0xFFFFFFFFull) {
+    set_error("magot_plan_create: table too large for one plan (split it)");
+    return MAGOT_ERR_ARG;
+  }
   lap("launch_ord");
 
   // --- device arena -----------------------------------------------------------
@@ -1402,14 +1456,11 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   p->ctx = ctx;
   p->g = g;
   Carve cv;
-  // one padding row past each table: the kernel prefetches clamped rows j <= n
-  tn.push_back(B);
-  tp.push_back(P);
-  const uint64_t o_exg = cv.take<uint64_t>(Ec + 1);
-  const uint64_t o_exo = cv.take<uint64_t>(Ec + 2);
-  const uint64_t o_txn = cv.take<uint64_t>(Tc + 2);
-  const uint64_t o_txp = cv.take<uint64_t>(Tc + 2);
-  const uint64_t o_tiles = cv.take<TileRec>(n_tiles + 1);
+  // The device holds the tiles' packed blocks and their overflow rows, not
+  // the u64 tables they are packed from.
+  const uint64_t o_blocks = cv.take<uint8_t>((uint64_t)n_tiles * geo.stride);
+  const uint64_t o_ovf_ex = cv.take<uint64_t>(n_ovf_ex + 1);
+  const uint64_t o_ovf_tx = cv.take<TxRow>(n_ovf_tx + 1);
   // genome order: {layout place, record-order offsets} per output, for the
   // reassembly copies (magot_plan_fetch / copy_outputs)
   const uint64_t lay_rows = by_genome ? T : 0;
@@ -1426,11 +1477,27 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   out_arena = nullptr;  // the plan owns it now
   lap("malloc");
   char* base = static_cast<char*>(p->arena);
-  std::vector<HostPiece> pieces = {{o_exg, ex_g, (Ec + 1) * 8},
-                                   {o_exo, ex_out.data(), (Ec + 2) * 8},
-                                   {o_txn, tn.data(), (Tc + 2) * 8},
-                                   {o_txp, tp.data(), (Tc + 2) * 8},
-                                   {o_tiles, tiles.data(), tiles.size() * sizeof(TileRec)}};
+  // Blocks are packed by the host threads straight into the upload's pinned
+  // buffers, tile ranges in parallel; a tile's overflow rows go to its place
+  // in the (small) overflow arrays, uploaded after.
+  HostBuf<uint64_t> ovf_ex(n_ovf_ex + 1);
+  HostBuf<TxRow> ovf_tx(n_ovf_tx + 1);
+  ovf_ex[n_ovf_ex] = 0;
+  ovf_tx[n_ovf_tx] = TxRow{0, 0};
+  {
+    const TileTables tb{ex_g, ex_out.data(), tn.data(), tp.data(), g->span, lane_chunks};
+    if (int rc = upload_generated(
+            ctx, base + o_blocks, n_tiles, geo.stride, n_tiles >= (1u << 12) ? nth : 1u,
+            [&](uint64_t t0, uint64_t t1, uint8_t* dst) {
+              for (uint64_t t = t0; t < t1; ++t)
+                pack_tile_block(tb, geo, tiles[t], ovf_at[2 * t], ovf_at[2 * t + 1],
+                                dst + (t - t0) * geo.stride, ovf_ex.data(), ovf_tx.data());
+            }))
+      return rc;
+  }
+  lap("blocks");
+  std::vector<HostPiece> pieces = {{o_ovf_ex, ovf_ex.data(), (n_ovf_ex + 1) * 8},
+                                   {o_ovf_tx, ovf_tx.data(), (n_ovf_tx + 1) * sizeof(TxRow)}};
   if (by_genome) {
     pieces.push_back({o_lay_nuc, lay_nuc.data(), T * 8});
     pieces.push_back({o_rec_nuc, nuc_off.data(), (T + 1) * 8});
@@ -1446,17 +1513,25 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
     p->d_pep_off = reinterpret_cast<const uint64_t*>(base + o_rec_pep);
   }
   lap("upload");
+  if (lap.on) {  // everything in the arena is uploaded once, here
+    uint64_t up = (uint64_t)n_tiles * geo.stride;
+    for (const HostPiece& pc : pieces) up += pc.bytes;
+    fprintf(stderr,
+            "[plan] tiles %u, block rows %u + %u (%u bytes), overflow rows %llu + %llu, arena %llu "
+            "bytes, uploaded %llu\n",
+            n_tiles, geo.ex_rows, geo.tx_rows, geo.stride, (unsigned long long)n_ovf_ex,
+            (unsigned long long)n_ovf_tx, (unsigned long long)cv.used, (unsigned long long)up);
+  }
 
   ExtractArgs& a = p->args;
   a.nib = g->nib;
   a.span = g->span;
   a.runs = g->runs;
   a.dir = g->dir;
-  a.ex_g = reinterpret_cast<const uint64_t*>(base + o_exg);
-  a.ex_out = reinterpret_cast<const uint64_t*>(base + o_exo);
-  a.tx_nuc = reinterpret_cast<const uint64_t*>(base + o_txn);
-  a.tx_pep = reinterpret_cast<const uint64_t*>(base + o_txp);
-  a.tiles = reinterpret_cast<const TileRec*>(base + o_tiles);
+  a.blocks = reinterpret_cast<const uint8_t*>(base + o_blocks);
+  a.blk = geo;
+  a.ovf_ex = reinterpret_cast<const uint64_t*>(base + o_ovf_ex);
+  a.ovf_tx = reinterpret_cast<const TxRow*>(base + o_ovf_tx);
   a.nuc = static_cast<uint8_t*>(p->out_arena);
   a.pep = static_cast<uint8_t*>(p->out_arena) + ((out_nuc + 255) & ~255ull);
   a.total_nuc = B;
@@ -1480,6 +1555,10 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   p->n_exons = E;
   p->n_ex_c = Ec;
   p->n_tx = T;
+  if (!by_genome) {  // magot_plan_orf6's rows (it refuses a genome-order plan)
+    p->host_ex_g = std::move(w_g.p);
+    p->host_ex_out = std::move(ex_out.p);
+  }
   if (nuc_bytes) *nuc_bytes = B;
   if (pep_bytes) *pep_bytes = P;
   *out = p.release();
@@ -2042,11 +2121,9 @@ int magot_plan_orf6(magot_ctx* ctx, magot_plan* p, const uint8_t* lut64, magot_o
   // from the forward planes instead, '-' read backwards and reverse-
   // complemented in registers, measured 5 % slower: DESIGN.md 4, round 4)
   const uint64_t ne = p->n_ex_c;
-  std::vector<uint64_t> ex_g(ne), ex_out(ne + 1), rows(2 * (ne + 1));
-  if (ne) {
-    MAGOT_HIP_TRY(hipMemcpy(ex_g.data(), p->args.ex_g, ne * 8, hipMemcpyDeviceToHost));
-    MAGOT_HIP_TRY(hipMemcpy(ex_out.data(), p->args.ex_out, (ne + 1) * 8, hipMemcpyDeviceToHost));
-  }
+  const uint64_t* const ex_g = p->host_ex_g.get();
+  const uint64_t* const ex_out = p->host_ex_out.get();
+  std::vector<uint64_t> rows(2 * (ne + 1));
   const uint64_t span = p->args.span;
   std::vector<uint64_t> starts(ne + 1);
   for (uint64_t i = 0; i < ne; ++i) {

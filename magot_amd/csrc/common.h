@@ -197,11 +197,96 @@ constexpr uint32_t kDebugSlowPep = 1u << 9;
 // are stored in launch order, which is not output order: tiles that may take
 // the run-list path go first (magot_plan_create), so their extra dependent
 // loads overlap the rest of the launch instead of extending its tail.
+// Host only: the device reads a tile from its TileBlock.
 struct TileRec {
   uint64_t T0, T1, Q0, Q1;
   uint32_t e1, e2, j1, j2;
 };
 static_assert(sizeof(TileRec) == 48, "TileRec is 48 bytes");
+
+// ---------------------------------------------------------------------------
+// Packed tile descriptor blocks (tileblocks.cpp)
+// ---------------------------------------------------------------------------
+// Everything a wave stages for tile t, packed once per plan into block t of a
+// fixed-stride table (launch order), so every load of the tile's descriptor
+// has an address that follows from t alone: the header (scalar) and each
+// lane's rows are one round of loads.  An interval or record staged by two
+// tiles is in both blocks.  A block is
+//   TileHead   T0, Q0, span | residues << 16, m | nt << 8, overflow offsets
+//   ex[j]      interval e1 + j, j < min(m, ex_rows), 8 bytes (below)
+//   tx[r]      record j1 + r, r <= nt, r < tx_rows: {tn - T0, tp - Q0}; row nt
+//              is the sentinel (the record after the last), whose tp the
+//              kernel reads.  64-bit: a record can be longer than 2^31 bases.
+// The inline capacities ex_rows / tx_rows are the plan's (TileGeometry,
+// tile_geometry): what nearly all of its tiles stage, so a plan of short
+// tiles does not fetch blocks sized for the largest.  Rows past them (a tile
+// stages up to kExonCap intervals and kTxCap + 1 record rows) are in the
+// plan's overflow arrays at ovf_ex / ovf_tx: one more wave-uniform round, for
+// those tiles only, one overflow row of each kind per lane (ex_rows + 64 >=
+// the plan's largest m).  Rows the tile does not use are zero.
+// Interval row (tile-relative, 32-bit): lo = U mod 2^32 (tile byte p reads
+// unified base U + p); hi = bit 0: U bit 32, bits 1..13: end of the interval
+// relative to T0, clamped to tile_bytes + 4 * kHalo, bits 14..16: reverse
+// strand / exception / slow literal (kFlagRc, kFlagExc, kFlagSlowLit), bits
+// 17..25: first chunk starting in the interval, ceil((o0 - T0) / 16)
+// (kBlkNoChunk for row 0, which starts no chunk run).
+constexpr uint32_t kFlagRc = 1u;
+constexpr uint32_t kFlagExc = 2u;      // touches an exception run
+constexpr uint32_t kFlagSlowLit = 4u;  // ... one without a literal class (run-list path)
+constexpr uint32_t kBlkExMax = 64;  // most inline interval rows (one per lane)
+constexpr uint32_t kBlkTxMax = 14;  // most inline record rows (the sentinel row included)
+constexpr uint32_t kBlkNoChunk = 511;
+struct TxRow {
+  int64_t tn, tp;
+};
+struct TileHead {
+  uint64_t T0, Q0;
+  uint32_t span_res;  // T1 - T0 | (Q1 - Q0) << 16
+  uint32_t counts;    // m | nt << 8
+  uint32_t ovf_ex;    // first overflow interval row (m > ex_rows)
+  uint32_t ovf_tx;    // first overflow record row (nt + 1 > tx_rows)
+};
+static_assert(sizeof(TileHead) == 32, "TileHead is 32 bytes");
+struct TileGeometry {
+  uint32_t ex_rows, tx_rows;  // inline rows: 1..kBlkExMax, 1..kBlkTxMax
+  uint32_t stride;            // block bytes: header + rows, a multiple of 16
+};
+constexpr uint32_t tile_block_stride(uint32_t ex_rows, uint32_t tx_rows) {
+  return ((uint32_t)sizeof(TileHead) + 8u * ex_rows + 16u * tx_rows + 15u) & ~15u;
+}
+static_assert(tile_block_stride(kBlkExMax, kBlkTxMax) == 768, "the largest block is six lines");
+static_assert(kExonCap <= (int)kBlkExMax + 64 && kTxCap + 1 <= 1 + 64,
+              "one inline and one overflow row per lane");
+static_assert(tile_bytes(kLaneChunksLarge) + 4 * kHalo < (1 << 13) &&
+              (tile_bytes(kLaneChunksLarge) + kHalo + kChunk - 1) / kChunk < (int)kBlkNoChunk,
+              "interval row fields");
+// The u64 tables a plan is packed from (magot_plan_create): interval starts
+// with flag bits, n+1 output offsets, record output / residue starts (n+1).
+struct TileTables {
+  const uint64_t* ex_g;
+  const uint64_t* ex_out;
+  const uint64_t* tx_nuc;
+  const uint64_t* tx_pep;
+  uint64_t span;
+  uint32_t lane_chunks;
+};
+inline uint32_t tile_ovf_ex(const TileGeometry& g, const TileRec& r) {
+  return r.e2 - r.e1 > g.ex_rows ? r.e2 - r.e1 - g.ex_rows : 0u;
+}
+inline uint32_t tile_ovf_tx(const TileGeometry& g, const TileRec& r) {
+  const uint32_t rows = r.j2 > r.j1 ? r.j2 - r.j1 + 1 : 0u;
+  return rows > g.tx_rows ? rows - g.tx_rows : 0u;
+}
+// The plan's block geometry: inline capacities that hold every row of all but
+// about 2 % of the tiles (and leave at most 64 rows of either kind to the
+// overflow).  force_ex / force_tx > 0 (MAGOT_TILE_BLOCK_ROWS=ex,tx: tests,
+// A/Bs) replace the percentile, within the same limits.
+TileGeometry tile_geometry(const TileRec* tiles, uint64_t n_tiles, uint32_t force_ex,
+                           uint32_t force_tx);
+// Block of tile r at b (g.stride bytes, every one written), its overflow rows
+// to ovf_ex[oe ..) / ovf_tx[ot ..).
+void pack_tile_block(const TileTables& tb, const TileGeometry& g, const TileRec& r, uint32_t oe,
+                     uint32_t ot, uint8_t* b, uint64_t* ovf_ex, TxRow* ovf_tx);
 
 // Device plan.  Zero-length intervals and records without a codon are
 // compacted away on the host (they add no output); tiles are 16-byte aligned
@@ -214,11 +299,10 @@ struct ExtractArgs {
   uint64_t span;
   const ExcRun* runs;
   const uint32_t* dir;
-  const uint64_t* ex_g;       // per interval: global genome start | kRcBit
-  const uint64_t* ex_out;     // n+1 output prefix offsets
-  const uint64_t* tx_nuc;     // per codon-bearing record: output start (n+1, sentinel B)
-  const uint64_t* tx_pep;     // per codon-bearing record: residue start (n+1, sentinel P)
-  const TileRec* tiles;       // n_tiles, in launch order
+  const uint8_t* blocks;      // n_tiles blocks of blk.stride bytes, in launch order
+  const uint64_t* ovf_ex;     // interval rows past a block's blk.ex_rows
+  const TxRow* ovf_tx;        // record rows past a block's blk.tx_rows
+  TileGeometry blk;
   uint8_t* nuc;
   uint8_t* pep;
   uint64_t total_nuc;

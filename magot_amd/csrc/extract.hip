@@ -20,9 +20,16 @@
 //     chunks + a 3-chunk halo for codons that run past the tile end) and 1-2
 //     residue chunks per lane, so there is no workgroup barrier (every wave
 //     writes its own copy of the codon table).
-//   * Staging: the tile's intervals go to wave-private LDS as {64-bit unified
-//     anchor, tile-relative end, flags}; chunk -> interval and residue chunk
-//     -> record maps come from an LDS histogram + one packed DPP wave scan.
+//   * Staging: the host packs, once per plan, one descriptor block per tile
+//     at a fixed stride (common.h, tileblocks.cpp): a header, the tile's
+//     interval rows already tile-relative in 8 bytes each and its record
+//     rows.  The header's scalar loads and every lane's row loads have
+//     addresses that follow from the tile index alone, so they are one memory
+//     round (load_tile); only the few tiles with more rows than the plan's
+//     inline capacity read the rest through the header.  The rows go to
+//     wave-private LDS as {plane offset, anchor lo, tile-relative end, flags}
+//     with 32-bit arithmetic; chunk -> interval and residue chunk -> record
+//     maps come from an LDS histogram + one packed DPP wave scan.
 //   * The genome is a nibble plane (code | soft-mask << 2, or 8 | literal
 //     class for an exception byte) followed by its reverse-complement mirror,
 //     so a '-' interval reads its strand forward exactly like a '+' interval.
@@ -58,9 +65,7 @@ struct WaveLds {
   uint8_t pmap[kPepSlots];                // residue chunk -> record
 };
 
-constexpr uint32_t kFlagRc = 1u;
-constexpr uint32_t kFlagExc = 2u;      // touches an exception run
-constexpr uint32_t kFlagSlowLit = 4u;  // ... one without a literal class (run-list path)
+// kFlagRc / kFlagExc / kFlagSlowLit (bits 0..2): common.h, packed by the host.
 // '-' interval without exceptions: the fast path reads it from the forward
 // plane, descending (vb, shift in bits 13..15), and reverse-complements the
 // chunk in registers; its mirror anchor stays for the slow path and for
@@ -231,17 +236,11 @@ __device__ __forceinline__ void patch_runs(const Planes& a, uint64_t glo, uint64
   }
 }
 
-// Unified coordinate U of tile byte 0 for interval row {gw, o0, o1}: chunk
-// byte p of the tile reads unified base U + p (forward strand g = gs + (p -
-// s), reverse strand 2*span-1 - (gs + len-1 - (p - s)), s = o0 - T0).  U may
-// wrap below 0 for an interval that starts far into the tile; U + p does not,
-// and it is below 2^33 (genome < 4 Gbases), so 33 bits of U are enough.
-__device__ __forceinline__ uint64_t row_anchor(uint64_t gw, uint64_t o0, uint64_t o1, uint64_t T0,
-                                               uint64_t span) {
-  const uint64_t gs = gw & ~kExFlagBits;
-  const uint64_t s = o0 - T0;
-  return (gw & kRcBit) ? 2 * span - gs - (o1 - o0) - s : gs - s;
-}
+// The unified coordinate U of tile byte 0 of an interval row comes packed
+// from the host (pack_tile_block): chunk byte p of the tile reads unified base
+// U + p.  U may wrap below 0 for an interval that starts far into the tile;
+// U + p does not, and it is below 2^33 (genome < 4 Gbases), so 33 bits of U
+// are enough.
 constexpr uint64_t kUMask = (1ull << 33) - 1;
 
 // General chunk assembly: any number of interval segments, exception runs.
@@ -279,52 +278,51 @@ __device__ __noinline__ Chunk build_chunk_slow(Planes a, int p, int lim, int i,
 
 struct TileDesc {
   uint64_t T0, T1, Q0, Q1;
-  uint32_t eb, m, tb, nt;
+  uint32_t m, nt, ovf_ex, ovf_tx;
 };
 
-// Uniform loads through the constant address space: scalar (s_load) even in
-// the persistent loop after vector stores.
-template <class T>
-__device__ __forceinline__ T sload(const T* p, uint32_t i) {
-  typedef const __attribute__((address_space(4))) T CT;
-  return ((CT*)p)[i];
-}
-
-__device__ __forceinline__ TileDesc load_desc(const ExtractArgs& a, uint32_t t) {
-  typedef const __attribute__((address_space(4))) TileRec CT;
-  CT* r = (CT*)a.tiles + t;  // one round of scalar loads (48 bytes)
-  TileDesc d;
-  d.T0 = r->T0;
-  d.T1 = r->T1;
-  d.Q0 = r->Q0;
-  d.Q1 = r->Q1;
-  d.eb = r->e1;
-  d.m = r->e2 - r->e1;
-  d.tb = r->j1;
-  d.nt = r->j2 - r->j1;
-  return d;
-}
-
-// Per-lane rows of one tile: intervals lane and lane+64, record lane.
+// Per-lane rows of one tile: intervals lane (inline) and ex_rows + lane
+// (overflow), record rows lane (inline) and tx_rows + lane (overflow).
 struct TileRows {
-  uint64_t o0[2], o1[2], g[2];
-  uint64_t tn, tp, tq;
+  uint2 ex[2];
+  TxRow tx[2];
 };
 
-__device__ __forceinline__ TileRows load_rows(const ExtractArgs& a, const TileDesc& d, int lane) {
-  TileRows r;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const uint32_t j = min((uint32_t)(lane + 64 * h), d.m);  // clamped: rows stay in bounds
-    r.o0[h] = a.ex_out[d.eb + j];
-    r.o1[h] = a.ex_out[d.eb + j + 1];
-    r.g[h] = a.ex_g[d.eb + j];
-  }
-  const uint32_t j = min((uint32_t)lane, d.nt);
-  r.tn = a.tx_nuc[d.tb + j];
-  r.tp = a.tx_pep[d.tb + j];
-  r.tq = a.tx_pep[d.tb + j + 1];
-  return r;
+// One tile's descriptor.  Every address of the first round follows from t
+// and the kernel arguments: the header's scalar loads (32 bytes, through the
+// constant address space) and each lane's inline rows are issued together.
+// Lanes past the tile's rows read their own block's zero rows.  Only a tile
+// with more than blk.ex_rows intervals or blk.tx_rows record rows waits for a
+// second, wave-uniform round through the header's overflow offsets.
+__device__ __forceinline__ TileDesc load_tile(const ExtractArgs& a, uint32_t t, int lane,
+                                              TileRows& r) {
+  const uint32_t E = a.blk.ex_rows, X = a.blk.tx_rows;
+  const uint8_t* blk = a.blocks + (uint64_t)t * a.blk.stride;
+  const uint2* exr = reinterpret_cast<const uint2*>(blk + sizeof(TileHead));
+  const TxRow* txr = reinterpret_cast<const TxRow*>(blk + sizeof(TileHead) + 8 * (size_t)E);
+  r.ex[0] = make_uint2(0u, 0u);
+  r.tx[0] = TxRow{0, 0};
+  if ((uint32_t)lane < E) r.ex[0] = exr[lane];
+  if ((uint32_t)lane < X) r.tx[0] = txr[lane];
+  typedef const __attribute__((address_space(4))) TileHead CT;
+  CT* h = (CT*)blk;
+  TileDesc d;
+  d.T0 = h->T0;
+  d.Q0 = h->Q0;
+  const uint32_t sr = h->span_res, cn = h->counts;
+  d.ovf_ex = h->ovf_ex;
+  d.ovf_tx = h->ovf_tx;
+  d.T1 = d.T0 + (sr & 0xFFFFu);
+  d.Q1 = d.Q0 + (sr >> 16);
+  d.m = cn & 0xFFu;
+  d.nt = cn >> 8;
+  r.ex[1] = make_uint2(0u, 0u);
+  r.tx[1] = TxRow{0, 0};
+  if (d.m > E && E + (uint32_t)lane < d.m)
+    r.ex[1] = reinterpret_cast<const uint2*>(a.ovf_ex)[d.ovf_ex + (uint32_t)lane];
+  if (d.nt >= X && X + (uint32_t)lane <= d.nt)
+    r.tx[1] = a.ovf_tx[d.ovf_tx + (uint32_t)lane];
+  return d;
 }
 
 // Derived per-tile quantities (all wave-uniform).
@@ -352,51 +350,53 @@ __device__ __forceinline__ TileGeom geom(const ExtractArgs& a, const TileDesc& d
 template <int LC>
 __device__ __forceinline__ void stage(WaveLds<LC>& L, uint32_t* codes, uint32_t* valid32,
                                       const TileDesc& d, const TileGeom& g, const TileRows& rows,
-                                      uint64_t span, int lane) {
+                                      uint64_t span, const TileGeometry& blk, int lane) {
   const int m = (int)d.m, nt = (int)d.nt;
 #pragma unroll
   for (int h = 0; h < LC; ++h) codes[lane + 64 * h] = 0;
 #pragma unroll
   for (int h = 0; h < kPepPerLane; ++h) valid32[lane + 64 * h] = 0;
   __builtin_amdgcn_wave_barrier();
+  // 2 * span - 16: V of a reverse-strand row is this minus U (below)
+  const uint64_t vbase = 2 * span - 16;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int j = lane + 64 * h;
-    if (j < m) {
-      const uint64_t o0 = rows.o0[h], o1 = rows.o1[h], gw = rows.g[h];
-      const int64_t s = (int64_t)(o0 - d.T0);
-      const int64_t e = (int64_t)(o1 - d.T0);
-      const uint64_t U = row_anchor(gw, o0, o1, d.T0, span);
-      const uint32_t end32 = (uint32_t)min(e, (int64_t)(tile_bytes(LC) + 4 * kHalo));
+    const int j = h ? (int)blk.ex_rows + lane : lane;  // inline, overflow
+    if ((h || lane < (int)blk.ex_rows) && j < m) {
+      // packed row (common.h): all 32-bit from here
+      const uint32_t lo = rows.ex[h].x, hi = rows.ex[h].y;
+      const uint32_t u32 = hi & 1u, end32 = (hi >> 1) & 0x1FFFu, f3 = (hi >> 14) & 7u;
+      const uint32_t cj = (hi >> 17) & 0x1FFu;
       // reverse-forward: chunk c's 16 bytes are the forward bases V - 16c ..
-      // V - 16c + 15, reversed and complemented (V = gs + len - 16 + s)
-      const bool revfwd = (gw & kRcBit) && !(gw & kExcBit);
-      const int64_t V = (int64_t)(gw & ~kExFlagBits) + (int64_t)(o1 - d.T0) - 16;
-      const uint32_t fl = ((gw & kRcBit) ? kFlagRc : 0u) | ((gw & kExcBit) ? kFlagExc : 0u) |
-                          ((gw & kSlowLitBit) ? kFlagSlowLit : 0u) | ((uint32_t)(U & 7) << 8) |
-                          ((uint32_t)(U >> 32) & 1u) << 12 |
-                          (revfwd ? kFlagRevFwd | ((uint32_t)(V & 7) << 13) : 0u);
-      L.vb[j] = (uint32_t)(V >> 3) << 2;
+      // V - 16c + 15, reversed and complemented (V = gs + len - 16 + s, which
+      // for a reverse-strand row is 2 * span - 16 - U; 33 bits like U)
+      const bool revfwd = (f3 & (kFlagRc | kFlagExc)) == kFlagRc;
+      const uint64_t V = vbase - ((uint64_t)lo | (uint64_t)u32 << 32);
+      const uint32_t vlo = (uint32_t)V, v32 = (uint32_t)(V >> 32) & 1u;
+      const uint32_t fl = f3 | (lo & 7u) << 8 | u32 << 12 |
+                          (revfwd ? kFlagRevFwd | (vlo & 7u) << 13 : 0u);
+      L.vb[j] = (vlo >> 3 | v32 << 29) << 2;
       // byte offset of the plane word holding tile byte 0's base (mod 2^32:
       // U may wrap below 0, the chunks the row serves do not); chunk c reads
       // its window at bN + 8c, funnel shift 4 * (U & 7).  The slow path takes
       // U mod 2^33 from {y, flag bit 12}.
-      const uint32_t bN = (uint32_t)((int64_t)U >> 3) << 2;
-      L.ex[j] = make_uint4(bN, (uint32_t)U, end32, fl);
-      if (j >= 1) {
-        const int cj = ((int)s + kChunk - 1) / kChunk;
-        if (cj < g.n_all) atomicAdd(&codes[cj], 1u);
-      }
+      const uint32_t bN = (lo >> 3 | u32 << 29) << 2;
+      L.ex[j] = make_uint4(bN, lo, end32, fl);
+      // row 0 starts no chunk run (kBlkNoChunk >= n_all)
+      if ((int)cj < g.n_all) atomicAdd(&codes[cj], 1u);
     }
   }
-  if (lane < nt) {
-    const int64_t tp = (int64_t)(rows.tp - d.Q0);
-    L.tn[lane] = (int64_t)(rows.tn - d.T0);
-    L.tp[lane] = tp;
-    if (lane == nt - 1) L.tp[nt] = (int64_t)(rows.tq - d.Q0);
-    if (lane >= 1) {
-      const int pj = ((int)tp + g.qshift + 15) >> 4;
-      if (pj < g.n_pc) atomicAdd(&valid32[pj], 1u);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int r = h ? (int)blk.tx_rows + lane : lane;  // row nt: the sentinel (tp only)
+    if ((h || lane < (int)blk.tx_rows) && r <= nt && nt > 0) {
+      const int64_t tp = rows.tx[h].tp;
+      L.tn[r] = rows.tx[h].tn;
+      L.tp[r] = tp;
+      if (r >= 1 && r < nt) {
+        const int pj = ((int)tp + g.qshift + 15) >> 4;
+        if (pj < g.n_pc) atomicAdd(&valid32[pj], 1u);
+      }
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -509,9 +509,10 @@ __global__ __launch_bounds__(kThreads) void extract_kernel(ExtractArgs a) {
     L.codes_g[lane] = 0;
     L.valid_g[lane] = 0;
   }
-  const TileDesc d = load_desc(a, t);
+  TileRows rows;
+  const TileDesc d = load_tile(a, t, lane, rows);
   const TileGeom g = geom(a, d);
-  stage(L, codes, valid32, d, g, load_rows(a, d, lane), a.span, lane);
+  stage(L, codes, valid32, d, g, rows, a.span, a.blk, lane);
   const uint64_t T0 = d.T0;
 
   // Chunks at tile bytes p < edge_lo or p >= edge_hi lie in the 128-byte lines
