@@ -333,6 +333,34 @@ int magot_debug_tile_blocks(const uint64_t* ex_g, const uint64_t* ex_out, const 
                             uint64_t* ovf_ex, uint64_t ovf_ex_cap, int64_t* ovf_tx,
                             uint64_t ovf_tx_cap, uint64_t* n_ovf);
 
+/* Debug (no device): magot_plan_create's tile cut over the planner's tables,
+ * in output order.  ex_out = n_ex + 1 output offsets of the non-empty
+ * intervals; tx_nuc / tx_pep = output / residue starts of the n_rec records
+ * with a codon, then their sentinel (output bytes, residues); lane_chunks 3
+ * or 6.  tiles receives *n_tiles rows as in magot_debug_tile_blocks (at most
+ * tiles_cap).  tiles == NULL: the count only. */
+int magot_debug_tile_cut(const uint64_t* ex_out, uint64_t n_ex, const uint64_t* tx_nuc,
+                         const uint64_t* tx_pep, uint64_t n_rec, uint32_t lane_chunks, void* tiles,
+                         uint64_t tiles_cap, uint64_t* n_tiles);
+
+/* Debug (no device): everything magot_plan_create plans before it touches
+ * the device, for contigs given as to magot_genome_load (packed on the host)
+ * and tables and output flags given as to magot_plan_create; the same status
+ * and magot_last_error text on a bad table.  The MAGOT_EXTRACT_LANE_CHUNKS
+ * and MAGOT_TILE_BLOCK_ROWS overrides apply as they do there.
+ * info[9] = output bytes, residues, non-empty intervals Ec, records with a
+ * codon Tc, tiles, lane chunks, inline interval rows, inline record rows,
+ * block stride.  tiles == NULL: info only.  Otherwise info must hold what
+ * that first call gave, and ex_g / ex_out receive Ec + 1 rows (interval start
+ * | flag bits 63..61, output offset; layout order), tx_nuc / tx_pep Tc + 1,
+ * lay_nuc / lay_pep each record's place in the layout (n_tx), tiles the tiles
+ * in launch order. */
+int magot_debug_plan(const uint8_t* const* seqs, const uint64_t* lens, uint32_t n_contigs,
+                     const magot_exon* exons, uint64_t n_exons, const magot_tx* txs, uint64_t n_tx,
+                     uint32_t outputs, uint64_t* info, uint64_t* ex_g, uint64_t* ex_out,
+                     uint64_t* tx_nuc, uint64_t* tx_pep, uint64_t* lay_nuc, uint64_t* lay_pep,
+                     void* tiles);
+
 /*
  * Raw-sequence batch ops over n byte strings (seq_off has n+1 entries).
  * Replaces: Sequence.reverse_compliment (genome.py:784-793).

@@ -48,7 +48,7 @@ EXPORTS = (
     'magot_genome_load_ex', 'magot_genome_wire_ranges', 'magot_genome_attach_wire',
     'magot_copy_segments', 'magot_ctx_mark', 'magot_ctx_elapsed', 'magot_orf6_copy_outputs',
     'magot_genome_wire_export', 'magot_genome_wire_import',
-    'magot_debug_tile_blocks',
+    'magot_debug_tile_blocks', 'magot_debug_tile_cut', 'magot_debug_plan',
 )
 
 ERR_ARG = -1
@@ -110,6 +110,11 @@ def _declare(lib):
                                                    ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp,
                                                    _vp, ctypes.c_uint64, _vp, ctypes.c_uint64,
                                                    _vp]),
+        'magot_debug_tile_cut': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64,
+                                                ctypes.c_uint32, _vp, ctypes.c_uint64, _vp]),
+        'magot_debug_plan': (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp,
+                                            ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp]),
         'magot_revcomp_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp]),
         'magot_translate_sizes': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp]),
         'magot_translate_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,

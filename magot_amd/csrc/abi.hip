@@ -320,61 +320,6 @@ int magot_genome_load(magot_ctx* ctx, const uint8_t* const* seqs, const uint64_t
 
 namespace {
 
-struct Lap {
-  const char* tag;
-  const bool on;
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  explicit Lap(const char* env = "MAGOT_GENOME_TIMING", const char* tag_ = "genome")
-      : tag(tag_), on(std::getenv(env) != nullptr) {}
-  void operator()(const char* what) {
-    if (!on) return;
-    const auto t1 = std::chrono::steady_clock::now();
-    fprintf(stderr, "[%s] %-10s %.4f s\n", tag, what,
-            std::chrono::duration<double>(t1 - t0).count());
-    t0 = t1;
-  }
-};
-
-// Host threads for staging copies: the GPU's share of the host (OMP_NUM_THREADS
-// on the pool's boxes), at most 16.
-unsigned host_threads() {
-  unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  if (const char* e = std::getenv("OMP_NUM_THREADS")) {
-    const int v = atoi(e);
-    if (v > 0) hw = (unsigned)v;
-  }
-  return std::min(hw, 16u);
-}
-
-// fn(lo, hi, part) over `parts` contiguous ranges of [0, n), part 0 on the
-// calling thread; fn must not throw.
-template <class F>
-void parallel_ranges(uint64_t n, unsigned parts, F fn) {
-  if (parts <= 1 || n < 2) {
-    fn(0, n, 0u);
-    return;
-  }
-  std::vector<std::thread> pool;
-  pool.reserve(parts - 1);
-  for (unsigned k = 1; k < parts; ++k)
-    pool.emplace_back([&fn, n, parts, k]() { fn(n * k / parts, n * (k + 1) / parts, k); });
-  fn(0, n / parts, 0u);
-  for (std::thread& th : pool) th.join();
-}
-
-// A host array left uninitialised (POD rows the planner writes itself, in
-// parallel: no sequential zero fill, and its pages fault in on the writing threads).
-template <class T>
-struct HostBuf {
-  std::unique_ptr<T[]> p;
-  uint64_t n = 0;
-  explicit HostBuf(uint64_t count = 0) : p(count ? new T[count] : nullptr), n(count) {}
-  T& operator[](uint64_t i) { return p[i]; }
-  const T& operator[](uint64_t i) const { return p[i]; }
-  T* data() { return p.get(); }
-  const T* data() const { return p.get(); }
-};
-
 // Host rows bound for one device allocation (dev_off into it).
 struct HostPiece {
   uint64_t dev_off;
@@ -493,6 +438,30 @@ struct DevBuf {
   void* p = nullptr;
   ~DevBuf() {
     if (p) (void)hipFree(p);
+  }
+};
+
+// A device allocation made on another thread while the caller goes on
+// (hipMalloc of C3's 0.8 GB of outputs takes ~10 ms).  It is joined, and
+// freed unless taken, when it goes out of scope.
+struct AsyncAlloc {
+  void* mem = nullptr;
+  hipError_t err = hipSuccess;
+  std::thread th;
+  AsyncAlloc(int device, uint64_t bytes)
+      : th([this, device, bytes]() {
+          err = hipSetDevice(device);
+          if (err == hipSuccess) err = hipMalloc(&mem, bytes);
+        }) {}
+  hipError_t take(void** out) {  // the caller owns *out now
+    th.join();
+    *out = mem;
+    mem = nullptr;
+    return err;
+  }
+  ~AsyncAlloc() {
+    if (th.joinable()) th.join();
+    if (mem) (void)hipFree(mem);
   }
 };
 
@@ -1087,369 +1056,35 @@ int magot_copy_segments(magot_ctx* ctx, const void* src_dev, uint64_t src_bytes,
   return MAGOT_OK;
 }
 
+// The planning is tileplan.cpp's (host only); here: the device side of a plan.
 int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* exons,
                       uint64_t n_exons, const magot_tx* txs, uint64_t n_tx, uint32_t outputs,
                       magot_plan** out, uint64_t* nuc_bytes, uint64_t* pep_bytes) {
   if (int rc = bind(ctx)) return rc;
-  if (!g || !out || (n_exons && !exons) || (n_tx && !txs)) {
+  if (!g || !out) {
     set_error("magot_plan_create: null argument");
     return MAGOT_ERR_ARG;
   }
-  if (outputs & ~(MAGOT_OUT_NUC | MAGOT_OUT_PEP | MAGOT_OUT_GENOME_ORDER)) {
-    set_error("magot_plan_create: unknown output flags");
-    return MAGOT_ERR_ARG;
-  }
-  const bool by_genome = (outputs & MAGOT_OUT_GENOME_ORDER) != 0;
-  outputs &= ~MAGOT_OUT_GENOME_ORDER;
-  if (n_tx >= 0xFFFFFFFFull || n_exons >= 0xFFFFFFFFull) {
-    set_error("magot_plan_create: table too large for one plan (split it)");
-    return MAGOT_ERR_ARG;
-  }
+  if (int rc = plan_check_tables(exons, n_exons, txs, n_tx, outputs)) return rc;
   *out = nullptr;
   Lap lap("MAGOT_PLAN_TIMING", "plan");
-  const uint64_t E = n_exons, T = n_tx;
-  // --- validate and build per-record offsets --------------------------------
-  uint64_t expect = 0;
-  for (uint64_t t = 0; t < T; ++t) {
-    if (txs[t].exon_begin != expect) {
-      set_error("magot_plan_create: record " + std::to_string(t) +
-                " does not start where the previous one ended");
-      return MAGOT_ERR_ARG;
-    }
-    expect += txs[t].n_exons;
-    if (expect > E) {
-      set_error("magot_plan_create: records reference more exons than given");
-      return MAGOT_ERR_ARG;
-    }
-  }
-  if (expect != E) {
-    set_error("magot_plan_create: exons not covered by records");
-    return MAGOT_ERR_ARG;
-  }
-  const uint64_t n_contigs = g->contig_base.size();
-  // Host threads over record ranges for the per-interval passes (a large
-  // plan: C3's 4M intervals); small plans stay on the calling thread.
-  const unsigned nth = T >= (1u << 15) ? host_threads() : 1u;
-  // Pass 1, record order: every interval validated, flagged and compacted
-  // (zero-length intervals add no output) into words w_g / lengths w_len;
-  // record t's compacted intervals are [rec_ex[t], rec_ex[t+1]).  Two
-  // parallel sweeps: counts (and the first bad interval of each range), then,
-  // after a prefix over the counts, the words.
-  std::vector<uint64_t> rec_ex(T + 1), rec_len(T);
-  std::vector<uint64_t> first_bad(nth, ~0ull);
-  parallel_ranges(T, nth, [&](uint64_t t0, uint64_t t1, unsigned part) {
-    for (uint64_t t = t0; t < t1; ++t) {
-      uint64_t len = 0, nz = 0;
-      const uint64_t e0 = txs[t].exon_begin, e1 = e0 + txs[t].n_exons;
-      for (uint64_t e = e0; e < e1; ++e) {
-        const magot_exon& x = exons[e];
-        const uint64_t st = x.start_rc & ~kRcBit;
-        if (x.contig >= n_contigs || st > g->contig_len[x.contig] ||
-            st + x.len > g->contig_len[x.contig]) {
-          first_bad[part] = e;
-          return;
-        }
-        len += x.len;
-        nz += x.len != 0;
-      }
-      rec_len[t] = len;
-      rec_ex[t] = nz;
-    }
-  });
-  for (uint64_t e : first_bad)  // ranges ascend: the first bad range holds the first bad interval
-    if (e != ~0ull) {
-      set_error("magot_plan_create: exon " + std::to_string(e) + " outside its contig");
-      return MAGOT_ERR_RANGE;
-    }
-  uint64_t Ec = 0, B = 0, P = 0;
-  for (uint64_t t = 0; t < T; ++t) {
-    const uint64_t c = rec_ex[t];
-    rec_ex[t] = Ec;
-    Ec += c;
-    B += rec_len[t];
-    P += rec_len[t] / 3;
-  }
-  rec_ex[T] = Ec;
+  const PlanInput in{GenomeView{g->contig_base.data(), g->contig_len.data(), g->contig_base.size(),
+                                g->span, g->host_runs.data(), g->host_dir.data()},
+                     exons, n_exons, txs, n_tx, plan_options(outputs)};
+  const bool by_genome = in.opt.by_genome;
+  PlanCount cnt;
+  if (int rc = plan_count(in, &cnt)) return rc;
+  const uint64_t T = n_tx, B = cnt.B, P = cnt.P;
   // The output buffers' size is known now: allocate them on another thread
-  // while this one plans (hipMalloc of C3's 0.8 GB takes ~10 ms).
-  const uint64_t out_nuc = (outputs & MAGOT_OUT_NUC) ? B + 64 : 64;
-  const uint64_t out_pep = (outputs & MAGOT_OUT_PEP) ? P + 64 : 64;
+  // while this one plans.
+  const uint64_t out_nuc = (in.opt.outputs & MAGOT_OUT_NUC) ? B + 64 : 64;
+  const uint64_t out_pep = (in.opt.outputs & MAGOT_OUT_PEP) ? P + 64 : 64;
   const uint64_t out_bytes = ((out_nuc + 255) & ~255ull) + out_pep;
-  void* out_arena = nullptr;
-  hipError_t out_err = hipSuccess;
-  std::thread out_alloc([&]() {
-    out_err = hipSetDevice(ctx->device);
-    if (out_err == hipSuccess) out_err = hipMalloc(&out_arena, out_bytes);
-  });
-  struct JoinFree {  // the allocation is joined, and freed unless the plan took it
-    std::thread& th;
-    void*& mem;
-    ~JoinFree() {
-      if (th.joinable()) th.join();
-      if (mem) (void)hipFree(mem);
-    }
-  } out_guard{out_alloc, out_arena};
-  HostBuf<uint64_t> w_g(Ec + 1);
-  HostBuf<uint32_t> w_len(Ec);
-  parallel_ranges(T, nth, [&](uint64_t t0, uint64_t t1, unsigned) {
-    for (uint64_t t = t0; t < t1; ++t) {
-      uint64_t k = rec_ex[t];
-      const uint64_t e0 = txs[t].exon_begin, e1 = e0 + txs[t].n_exons;
-      for (uint64_t e = e0; e < e1; ++e) {
-        const magot_exon& x = exons[e];
-        if (x.len == 0) continue;
-        const uint64_t gs = g->contig_base[x.contig] + (x.start_rc & ~kRcBit);
-        // does [gs, gs+len) touch an exception run?  (dir: first run ending past the block)
-        uint64_t d = g->host_dir[gs >> kDirShift] & ~kDirClean;
-        while (g->host_runs[d].start + g->host_runs[d].len <= gs) ++d;
-        uint64_t exc = g->host_runs[d].start < gs + x.len ? kExcBit : 0;
-        if (exc && !(x.start_rc & kRcBit)) {
-          // forward strand: a byte without a literal class needs the run list
-          for (uint64_t r = d; g->host_runs[r].start < gs + x.len; ++r)
-            if (lit_class(g->host_runs[r].byte) == 7u) {
-              exc |= kSlowLitBit;
-              break;
-            }
-        }
-        w_g[k] = gs | (x.start_rc & kRcBit) | exc;
-        w_len[k] = x.len;
-        ++k;
-      }
-    }
-  });
-  lap("pass1");
-  // Layout order of the records: record order, or (MAGOT_OUT_GENOME_ORDER) by
-  // the genome position of each record's first non-empty interval (records
-  // without output last), so that records sharing genome lines run in
-  // neighbouring tiles (C3: fills 0.89 -> 0.54 GB per launch); the places come
-  // back through magot_plan_layout, and fetch / copy_outputs restore record order.
-  std::vector<uint32_t> order;
-  if (by_genome) {
-    std::vector<uint64_t> key(T);
-    for (uint64_t t = 0; t < T; ++t)
-      key[t] = rec_ex[t] < rec_ex[t + 1] ? w_g[rec_ex[t]] & ~kExFlagBits : g->span;
-    radix_order(key, &order);
-  }
-  lap("order");
-  // Pass 2, layout order: each record's place (lay_*, indexed by record) from
-  // one sweep in layout order, then the interval table with its output
-  // offsets, record ranges in parallel (each record's rows are one block)
-  std::vector<uint64_t> lay_nuc(T), lay_pep(T);
-  HostBuf<uint64_t> lay_ex(T);
-  {
-    uint64_t acc = 0, q = 0, ek = 0;
-    for (uint64_t k = 0; k < T; ++k) {
-      const uint64_t t = by_genome ? order[k] : k;
-      lay_nuc[t] = acc;
-      lay_pep[t] = q;
-      lay_ex[t] = ek;
-      acc += rec_len[t];
-      q += rec_len[t] / 3;
-      ek += rec_ex[t + 1] - rec_ex[t];
-    }
-  }
-  // interval rows in layout order (the record-order rows themselves when the
-  // layout is record order)
-  HostBuf<uint64_t> ex_perm(by_genome ? Ec + 1 : 0), ex_out(Ec + 2);
-  uint64_t* const ex_g = by_genome ? ex_perm.data() : w_g.data();
-  parallel_ranges(T, nth, [&](uint64_t t0, uint64_t t1, unsigned) {
-    for (uint64_t t = t0; t < t1; ++t) {
-      uint64_t k = lay_ex[t], o = lay_nuc[t];
-      for (uint64_t i = rec_ex[t]; i < rec_ex[t + 1]; ++i, ++k) {
-        if (by_genome) ex_g[k] = w_g[i];
-        ex_out[k] = o;
-        o += w_len[i];
-      }
-    }
-  });
-  ex_g[Ec] = 0;
-  ex_out[Ec] = B;
-  ex_out[Ec + 1] = B;
-  // Compacted record table in layout order: records with at least one codon.
-  std::vector<uint64_t> tn, tp;
-  tn.reserve(T + 3);
-  tp.reserve(T + 3);
-  for (uint64_t k = 0; k < T; ++k) {
-    const uint64_t t = by_genome ? order[k] : k;
-    if (rec_len[t] >= 3) {
-      tn.push_back(lay_nuc[t]);
-      tp.push_back(lay_pep[t]);
-    }
-  }
-  // record-order prefix offsets (what fetch returns)
-  std::vector<uint64_t> nuc_off(T + 1), pep_off(T + 1);
-  nuc_off[0] = pep_off[0] = 0;
-  for (uint64_t t = 0; t < T; ++t) {
-    nuc_off[t + 1] = nuc_off[t] + rec_len[t];
-    pep_off[t + 1] = pep_off[t] + rec_len[t] / 3;
-  }
-  const uint64_t Tc = tn.size();
-  tn.push_back(B);
-  tp.push_back(P);
-  lap("pass2");
-  if (Ec >= 0xFFFFFFFFull || Tc >= 0xFFFFFFFFull) {
-    set_error("magot_plan_create: table too large for one plan (split it)");
-    return MAGOT_ERR_ARG;
-  }
-
-  // --- tiles ----------------------------------------------------------------
-  // A tile owns nucleotide bytes [T0, T1) and residues [R0, R1).  Residue
-  // ownership is rounded up to 16-residue (16-byte) store chunks, so nearly
-  // every peptide store is a full aligned chunk; the residues a tile owns past
-  // its last codon start are decoded from its kHalo bytes of look-ahead.
-  // Every query below is monotone over the cut (tile ends, decode ends and
-  // residue bounds only grow), so the searches are cursors that move forward:
-  // O(records + tiles) per cut instead of a binary search per query.
-  struct Cursor {  // upper_bound over a non-decreasing table, for non-decreasing queries
-    const uint64_t* v;
-    uint64_t n, j;
-    uint64_t operator()(uint64_t x) {
-      while (j < n && v[j] <= x) ++j;
-      return j;
-    }
-  };
-  auto pcount = [&](Cursor& c, uint64_t T) -> uint64_t {  // residues whose codon starts before T
-    const uint64_t j = c(T);
-    if (j == 0) return 0;
-    const uint64_t into = T - tn[j - 1];
-    return tp[j - 1] + std::min((into + 2) / 3, tp[j] - tp[j - 1]);
-  };
-  auto rec_of = [&](Cursor& c, uint64_t q) -> uint64_t {  // compacted record holding residue q < P
-    return c(q) - 1;
-  };
-  std::vector<uint64_t> tile_start, tile_q;
-  std::vector<uint32_t> tile_ex, tile_tx;
-  // cut the output into tiles of at most `tile` bytes (see tile_bytes)
-  auto cut = [&](uint64_t tile) -> int {
-    tile_start.clear();
-    tile_q.clear();
-    tile_ex.clear();
-    tile_tx.clear();
-    Cursor c_end{tn.data(), Tc, 0}, c_dec{tn.data(), Tc, 0};    // pcount(T1), pcount(dec_end - 2)
-    Cursor c_r0{tp.data(), Tc, 0}, c_r1{tp.data(), Tc, 0};      // rec_of(R0), rec_of(R1 - 1)
-    uint64_t e1 = 0, e2 = 0;
-    uint64_t T0 = 0, R0 = 0;
-    while (T0 < B) {
-      while (e1 < Ec && ex_out[e1 + 1] <= T0) ++e1;           // interval containing T0
-      const uint64_t j1 = R0 < P ? rec_of(c_r0, R0) : Tc;      // record holding residue R0
-      uint64_t T1 = std::min<uint64_t>(T0 + tile, B);
-      if (e1 + kExonCap < Ec) T1 = std::min<uint64_t>(T1, ex_out[e1 + kExonCap] - kHalo);
-      if (j1 + kTxCap - kChunk < Tc) T1 = std::min<uint64_t>(T1, tn[j1 + kTxCap - kChunk]);
-      // cut on a 128-byte line boundary where the tile keeps one (no
-      // nucleotide line is then written by two tiles), else on a chunk
-      if (T1 < B) T1 = (T1 & ~(uint64_t)(kTileAlign - 1)) > T0 ? T1 & ~(uint64_t)(kTileAlign - 1)
-                                                             : T1 & ~(uint64_t)(kChunk - 1);
-      if (T1 < T0 + kChunk) T1 = std::min<uint64_t>(T0 + kChunk, B);
-      const uint64_t dec_end = std::min<uint64_t>(T1 + kHalo, B);
-      // residues owned: every codon starting before T1, rounded up to a chunk,
-      // but only codons that end inside the decoded range and at most kPepSlots chunks
-      uint64_t R1 = P;
-      if (T1 < B) {
-        R1 = std::min<uint64_t>((pcount(c_end, T1) + kChunk - 1) & ~(uint64_t)(kChunk - 1), P);
-        R1 = std::min<uint64_t>(R1, pcount(c_dec, dec_end - 2));
-        R1 = std::min<uint64_t>(R1, (R0 & ~(uint64_t)(kChunk - 1)) + kPepSlots * kChunk);
-      }
-      if (R1 < R0) R1 = R0;
-      if (e2 < e1) e2 = e1;
-      while (e2 < Ec && ex_out[e2] < dec_end) ++e2;           // intervals touching the decode range
-      const uint64_t jl = R1 > R0 ? rec_of(c_r1, R1 - 1) : 0;  // record holding the last residue
-      const uint64_t j2 = R1 > R0 ? jl + 1 : j1;               // records holding residues [R0, R1)
-      if (e2 - e1 > (uint64_t)kExonCap || (R1 > R0 && j2 - j1 > (uint64_t)kTxCap) ||
-          (R1 > R0 && tn[jl] + 3 * (R1 - 1 - tp[jl]) + 3 > dec_end)) {
-        set_error("magot_plan_create: internal tiling error");
-        return MAGOT_ERR_STATE;
-      }
-      tile_start.push_back(T0);
-      tile_q.push_back(R0);
-      tile_ex.push_back((uint32_t)e1);
-      tile_ex.push_back((uint32_t)e2);
-      tile_tx.push_back((uint32_t)(R1 > R0 ? j1 : 0));
-      tile_tx.push_back((uint32_t)(R1 > R0 ? j2 : 0));
-      T0 = T1;
-      R0 = R1;
-    }
-    if (R0 != P) {
-      set_error("magot_plan_create: internal tiling error (residues)");
-      return MAGOT_ERR_STATE;
-    }
-    return MAGOT_OK;
-  };
-  // the large tile, or the small one for translating plans too small to fill
-  // the chip several times over (MAGOT_EXTRACT_LANE_CHUNKS=3|6 forces one, for
-  // A/Bs); nucleotide-only plans keep the large tile (C2: 0.0164 vs 0.0172 ms)
-  uint32_t lane_chunks = kLaneChunksLarge;
-  if (int rc = cut(tile_bytes(kLaneChunksLarge))) return rc;
-  const char* lc_env = std::getenv("MAGOT_EXTRACT_LANE_CHUNKS");
-  const int lc_force = lc_env ? std::atoi(lc_env) : 0;
-  if (lc_force == kLaneChunksSmall ||
-      (lc_force != kLaneChunksLarge && (outputs & MAGOT_OUT_PEP) &&
-       tile_start.size() < kSmallTilePlan)) {
-    lane_chunks = kLaneChunksSmall;
-    if (int rc = cut(tile_bytes(kLaneChunksSmall))) return rc;
-  }
-  tile_start.push_back(B);
-  tile_q.push_back(P);
-  lap("tiles");
-  const uint64_t n_tiles64 = tile_start.size() - 1;
-  if (n_tiles64 >= 0x7FFFFFFFull) {
-    set_error("magot_plan_create: output too large for one launch");
-    return MAGOT_ERR_ARG;
-  }
-  const uint32_t n_tiles = (uint32_t)n_tiles64;
-  // Launch order: tiles that may take the run-list path first -- a staged
-  // interval over a byte without a literal class (kSlowLitBit), or one short
-  // enough that a chunk can span three intervals.  Their chains of dependent
-  // run-list loads then overlap the rest of the launch; at the end of the grid
-  // they set its tail (C2: 0.0174 ms with the 23 such tiles where they fall,
-  // 0.0151 ms with none).  Every other tile keeps output order.
-  std::vector<uint8_t> slow_tile(n_tiles);
-  parallel_ranges(n_tiles, n_tiles >= (1u << 14) ? nth : 1u, [&](uint64_t t0, uint64_t t1, unsigned) {
-    for (uint64_t t = t0; t < t1; ++t) {
-      bool slow = false;
-      for (uint32_t e = tile_ex[2 * t]; e < tile_ex[2 * t + 1] && !slow; ++e)
-        slow = (ex_g[e] & kSlowLitBit) || ex_out[e + 1] - ex_out[e] < (uint64_t)kChunk;
-      slow_tile[t] = slow;
-    }
-  });
-  std::vector<TileRec> tiles(n_tiles);
-  std::vector<TileRec> tail;
-  uint32_t n_first = 0;
-  for (uint32_t t = 0; t < n_tiles; ++t) {
-    const TileRec r{tile_start[t], tile_start[t + 1], tile_q[t], tile_q[t + 1],
-                    tile_ex[2 * t], tile_ex[2 * t + 1], tile_tx[2 * t], tile_tx[2 * t + 1]};
-    if (slow_tile[t]) tiles[n_first++] = r;
-    else tail.push_back(r);
-  }
-  std::copy(tail.begin(), tail.end(), tiles.begin() + n_first);
-  // the blocks' inline capacities, from what this plan's tiles stage
-  // (MAGOT_TILE_BLOCK_ROWS=ex,tx forces them: tests and A/Bs), and each tile's
-  // place in the overflow arrays (rows past a block's inline part)
-  uint32_t force_ex = 0, force_tx = 0;
-  if (const char* e = std::getenv("MAGOT_TILE_BLOCK_ROWS")) {
-    unsigned fe = 0, fx = 0;
-    if (sscanf(e, "%u,%u", &fe, &fx) == 2) {
-      force_ex = std::min(fe, kBlkExMax);
-      force_tx = std::min(fx, kBlkTxMax);
-    }
-  }
-  const TileGeometry geo = tile_geometry(tiles.data(), n_tiles, force_ex, force_tx);
-  std::vector<uint32_t> ovf_at(2 * (size_t)n_tiles);
-  uint64_t n_ovf_ex = 0, n_ovf_tx = 0;
-  for (uint32_t t = 0; t < n_tiles; ++t) {
-    if (tiles[t].T1 - tiles[t].T0 > 0xFFFFull || tiles[t].Q1 - tiles[t].Q0 > 0xFFFFull) {
-      set_error("magot_plan_create: internal tiling error (tile block fields)");
-      return MAGOT_ERR_STATE;
-    }
-    ovf_at[2 * (size_t)t] = (uint32_t)n_ovf_ex;
-    ovf_at[2 * (size_t)t + 1] = (uint32_t)n_ovf_tx;
-    n_ovf_ex += tile_ovf_ex(geo, tiles[t]);
-    n_ovf_tx += tile_ovf_tx(geo, tiles[t]);
-  }
-  if (n_ovf_ex >= 0xFFFFFFFFull || n_ovf_tx >= 0xFFFFFFFFull) {
-    set_error("magot_plan_create: table too large for one plan (split it)");
-    return MAGOT_ERR_ARG;
-  }
-  lap("launch_ord");
+  AsyncAlloc out_alloc(ctx->device, out_bytes);
+  TilePlan pl;
+  if (int rc = plan_build(in, std::move(cnt), lap, &pl)) return rc;
+  const uint32_t n_tiles = (uint32_t)pl.tiles.size();
+  const TileGeometry geo = pl.geo;
 
   // --- device arena -----------------------------------------------------------
   std::unique_ptr<magot_plan> p(new magot_plan());
@@ -1459,8 +1094,8 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   // The device holds the tiles' packed blocks and their overflow rows, not
   // the u64 tables they are packed from.
   const uint64_t o_blocks = cv.take<uint8_t>((uint64_t)n_tiles * geo.stride);
-  const uint64_t o_ovf_ex = cv.take<uint64_t>(n_ovf_ex + 1);
-  const uint64_t o_ovf_tx = cv.take<TxRow>(n_ovf_tx + 1);
+  const uint64_t o_ovf_ex = cv.take<uint64_t>(pl.n_ovf_ex + 1);
+  const uint64_t o_ovf_tx = cv.take<TxRow>(pl.n_ovf_tx + 1);
   // genome order: {layout place, record-order offsets} per output, for the
   // reassembly copies (magot_plan_fetch / copy_outputs)
   const uint64_t lay_rows = by_genome ? T : 0;
@@ -1470,39 +1105,36 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   const uint64_t o_rec_pep = cv.take<uint64_t>(by_genome ? T + 1 : 0);
   MAGOT_HIP_TRY(hipMalloc(&p->arena, cv.used));
   p->arena_bytes = cv.used;
-  out_alloc.join();
+  const hipError_t out_err = out_alloc.take(&p->out_arena);
   MAGOT_HIP_TRY(out_err);
-  p->out_arena = out_arena;
   p->out_bytes = out_bytes;
-  out_arena = nullptr;  // the plan owns it now
   lap("malloc");
   char* base = static_cast<char*>(p->arena);
   // Blocks are packed by the host threads straight into the upload's pinned
   // buffers, tile ranges in parallel; a tile's overflow rows go to its place
   // in the (small) overflow arrays, uploaded after.
-  HostBuf<uint64_t> ovf_ex(n_ovf_ex + 1);
-  HostBuf<TxRow> ovf_tx(n_ovf_tx + 1);
-  ovf_ex[n_ovf_ex] = 0;
-  ovf_tx[n_ovf_tx] = TxRow{0, 0};
-  {
-    const TileTables tb{ex_g, ex_out.data(), tn.data(), tp.data(), g->span, lane_chunks};
-    if (int rc = upload_generated(
-            ctx, base + o_blocks, n_tiles, geo.stride, n_tiles >= (1u << 12) ? nth : 1u,
-            [&](uint64_t t0, uint64_t t1, uint8_t* dst) {
-              for (uint64_t t = t0; t < t1; ++t)
-                pack_tile_block(tb, geo, tiles[t], ovf_at[2 * t], ovf_at[2 * t + 1],
-                                dst + (t - t0) * geo.stride, ovf_ex.data(), ovf_tx.data());
-            }))
-      return rc;
-  }
+  HostBuf<uint64_t> ovf_ex(pl.n_ovf_ex + 1);
+  HostBuf<TxRow> ovf_tx(pl.n_ovf_tx + 1);
+  ovf_ex[pl.n_ovf_ex] = 0;
+  ovf_tx[pl.n_ovf_tx] = TxRow{0, 0};
+  const TileTables tb{pl.ex_g.data(), pl.ex_out.data(), pl.tn.data(), pl.tp.data(), g->span,
+                      pl.lane_chunks};
+  if (int rc = upload_generated(
+          ctx, base + o_blocks, n_tiles, geo.stride, n_tiles >= (1u << 12) ? pl.nth : 1u,
+          [&](uint64_t t0, uint64_t t1, uint8_t* dst) {
+            for (uint64_t t = t0; t < t1; ++t)
+              pack_tile_block(tb, geo, pl.tiles[t], pl.ovf_at[2 * t], pl.ovf_at[2 * t + 1],
+                              dst + (t - t0) * geo.stride, ovf_ex.data(), ovf_tx.data());
+          }))
+    return rc;
   lap("blocks");
-  std::vector<HostPiece> pieces = {{o_ovf_ex, ovf_ex.data(), (n_ovf_ex + 1) * 8},
-                                   {o_ovf_tx, ovf_tx.data(), (n_ovf_tx + 1) * sizeof(TxRow)}};
+  std::vector<HostPiece> pieces = {{o_ovf_ex, ovf_ex.data(), (pl.n_ovf_ex + 1) * 8},
+                                   {o_ovf_tx, ovf_tx.data(), (pl.n_ovf_tx + 1) * sizeof(TxRow)}};
   if (by_genome) {
-    pieces.push_back({o_lay_nuc, lay_nuc.data(), T * 8});
-    pieces.push_back({o_rec_nuc, nuc_off.data(), (T + 1) * 8});
-    pieces.push_back({o_lay_pep, lay_pep.data(), T * 8});
-    pieces.push_back({o_rec_pep, pep_off.data(), (T + 1) * 8});
+    pieces.push_back({o_lay_nuc, pl.lay_nuc.data(), T * 8});
+    pieces.push_back({o_rec_nuc, pl.nuc_off.data(), (T + 1) * 8});
+    pieces.push_back({o_lay_pep, pl.lay_pep.data(), T * 8});
+    pieces.push_back({o_rec_pep, pl.pep_off.data(), (T + 1) * 8});
   }
   if (int rc = upload_pieces(ctx, base, pieces)) return rc;
   if (by_genome) {
@@ -1519,8 +1151,8 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
     fprintf(stderr,
             "[plan] tiles %u, block rows %u + %u (%u bytes), overflow rows %llu + %llu, arena %llu "
             "bytes, uploaded %llu\n",
-            n_tiles, geo.ex_rows, geo.tx_rows, geo.stride, (unsigned long long)n_ovf_ex,
-            (unsigned long long)n_ovf_tx, (unsigned long long)cv.used, (unsigned long long)up);
+            n_tiles, geo.ex_rows, geo.tx_rows, geo.stride, (unsigned long long)pl.n_ovf_ex,
+            (unsigned long long)pl.n_ovf_tx, (unsigned long long)cv.used, (unsigned long long)up);
   }
 
   ExtractArgs& a = p->args;
@@ -1537,8 +1169,8 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   a.total_nuc = B;
   a.total_pep = P;
   a.n_tiles = n_tiles;
-  a.outputs = outputs;
-  a.lane_chunks = lane_chunks;
+  a.outputs = in.opt.outputs;
+  a.lane_chunks = pl.lane_chunks;
   if (const char* dbg = std::getenv("MAGOT_DEBUG_PATHS")) {
     const int v = std::atoi(dbg);
     if (v & 1) a.outputs |= kDebugSlowNuc;
@@ -1548,16 +1180,16 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   standard_lut(lut);
   std::memcpy(a.lut, lut, 64);
 
-  p->nuc_off = std::move(nuc_off);
-  p->pep_off = std::move(pep_off);
-  p->lay_nuc = std::move(lay_nuc);
-  p->lay_pep = std::move(lay_pep);
-  p->n_exons = E;
-  p->n_ex_c = Ec;
+  p->nuc_off = std::move(pl.nuc_off);
+  p->pep_off = std::move(pl.pep_off);
+  p->lay_nuc = std::move(pl.lay_nuc);
+  p->lay_pep = std::move(pl.lay_pep);
+  p->n_exons = n_exons;
+  p->n_ex_c = pl.Ec;
   p->n_tx = T;
   if (!by_genome) {  // magot_plan_orf6's rows (it refuses a genome-order plan)
-    p->host_ex_g = std::move(w_g.p);
-    p->host_ex_out = std::move(ex_out.p);
+    p->host_ex_g = std::move(pl.ex_g.p);
+    p->host_ex_out = std::move(pl.ex_out.p);
   }
   if (nuc_bytes) *nuc_bytes = B;
   if (pep_bytes) *pep_bytes = P;

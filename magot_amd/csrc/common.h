@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/magot.h"
+#include "hostutil.h"
 
 namespace magot {
 
@@ -195,7 +196,7 @@ constexpr uint32_t kDebugSlowPep = 1u << 9;
 // One extraction tile (a wave's work): nucleotide output bytes [T0, T1),
 // residues [Q0, Q1), staged intervals [e1, e2) and records [j1, j2).  Tiles
 // are stored in launch order, which is not output order: tiles that may take
-// the run-list path go first (magot_plan_create), so their extra dependent
+// the run-list path go first (launch_order, tileplan.cpp), so their extra dependent
 // loads overlap the rest of the launch instead of extending its tail.
 // Host only: the device reads a tile from its TileBlock.
 struct TileRec {
@@ -260,7 +261,7 @@ static_assert(kExonCap <= (int)kBlkExMax + 64 && kTxCap + 1 <= 1 + 64,
 static_assert(tile_bytes(kLaneChunksLarge) + 4 * kHalo < (1 << 13) &&
               (tile_bytes(kLaneChunksLarge) + kHalo + kChunk - 1) / kChunk < (int)kBlkNoChunk,
               "interval row fields");
-// The u64 tables a plan is packed from (magot_plan_create): interval starts
+// The u64 tables a plan is packed from (plan_build): interval starts
 // with flag bits, n+1 output offsets, record output / residue starts (n+1).
 struct TileTables {
   const uint64_t* ex_g;
@@ -287,6 +288,70 @@ TileGeometry tile_geometry(const TileRec* tiles, uint64_t n_tiles, uint32_t forc
 // to ovf_ex[oe ..) / ovf_tx[ot ..).
 void pack_tile_block(const TileTables& tb, const TileGeometry& g, const TileRec& r, uint32_t oe,
                      uint32_t ot, uint8_t* b, uint64_t* ovf_ex, TxRow* ovf_tx);
+
+// ---------------------------------------------------------------------------
+// The extraction planner (tileplan.cpp, host only)
+// ---------------------------------------------------------------------------
+// From the caller's interval and record tables to the tiles, their launch
+// order and the blocks' geometry: everything magot_plan_create needs before
+// it allocates and uploads.  Two stages, so that the output buffers, whose
+// size stage 1 gives, can be allocated while stage 2 runs.
+// What the planner reads of a packed genome.
+struct GenomeView {
+  const uint64_t* contig_base;
+  const uint64_t* contig_len;
+  uint64_t n_contigs;
+  uint64_t span;
+  const ExcRun* runs;   // host run list, sentinel appended
+  const uint32_t* dir;  // its block directory
+};
+struct PlanOptions {
+  uint32_t outputs;      // MAGOT_OUT_NUC | MAGOT_OUT_PEP
+  bool by_genome;        // MAGOT_OUT_GENOME_ORDER
+  int lane_chunks;       // MAGOT_EXTRACT_LANE_CHUNKS (0: the planner's choice)
+  uint32_t block_ex, block_tx;  // MAGOT_TILE_BLOCK_ROWS=ex,tx (0: the planner's choice)
+};
+// The tables are there and fit one plan, the output flags are known.
+int plan_check_tables(const magot_exon* exons, uint64_t n_exons, const magot_tx* txs,
+                      uint64_t n_tx, uint32_t outputs);
+// `outputs` as given to magot_plan_create, and the environment's overrides.
+PlanOptions plan_options(uint32_t outputs);
+struct PlanInput {
+  GenomeView g;
+  const magot_exon* exons;
+  uint64_t E;
+  const magot_tx* txs;
+  uint64_t T;
+  PlanOptions opt;
+};
+// Stage 1: record t's compacted (non-empty) intervals are [rec_ex[t],
+// rec_ex[t+1]) of Ec, its length rec_len[t]; B output bytes, P residues.
+struct PlanCount {
+  std::vector<uint64_t> rec_ex, rec_len;
+  uint64_t Ec = 0, B = 0, P = 0;
+  unsigned nth = 1;  // host threads over record ranges (large plans)
+};
+int plan_count(const PlanInput& in, PlanCount* out);
+// Stage 2: the u64 tables in layout order (TileTables), each record's place,
+// the tiles in launch order and where their blocks' overflow rows go.
+struct TilePlan {
+  HostBuf<uint64_t> ex_g, ex_out;    // Ec + 1 starts with flag bits, Ec + 2 output offsets
+  std::vector<uint64_t> tn, tp;      // records with a codon, Tc + 1 (sentinel B, P)
+  std::vector<uint64_t> nuc_off, pep_off;  // record-order prefix offsets, T + 1
+  std::vector<uint64_t> lay_nuc, lay_pep;  // each record's place in the layout, T
+  uint64_t Ec = 0, Tc = 0;
+  uint32_t lane_chunks = 0;
+  std::vector<TileRec> tiles;        // launch order
+  TileGeometry geo{};
+  std::vector<uint32_t> ovf_at;      // tile t's first overflow interval / record row
+  uint64_t n_ovf_ex = 0, n_ovf_tx = 0;
+  unsigned nth = 1;
+};
+int plan_build(const PlanInput& in, PlanCount&& cnt, Lap& lap, TilePlan* out);
+// The cut: the output [0, ex_out[Ec]) as tiles of at most `tile` bytes
+// (tile_bytes), appended to *tiles in output order.
+int cut_tiles(const uint64_t* ex_out, uint64_t Ec, const uint64_t* tn, const uint64_t* tp,
+              uint64_t Tc, uint64_t tile, std::vector<TileRec>* tiles);
 
 // Device plan.  Zero-length intervals and records without a codon are
 // compacted away on the host (they add no output); tiles are 16-byte aligned

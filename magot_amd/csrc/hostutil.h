@@ -1,0 +1,73 @@
+// Host-side helpers shared by the translation units that plan on the CPU
+// (abi.hip, tileplan.cpp): lap timing, the thread count, range-parallel loops
+// and uninitialised arrays.  No HIP here.
+#pragma once
+
+#include <algorithm>
+#include <chrono>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <thread>
+#include <vector>
+
+namespace magot {
+
+// Wall-clock laps on stderr while the environment variable `env` is set.
+struct Lap {
+  const char* tag;
+  const bool on;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  explicit Lap(const char* env = "MAGOT_GENOME_TIMING", const char* tag_ = "genome")
+      : tag(tag_), on(std::getenv(env) != nullptr) {}
+  void operator()(const char* what) {
+    if (!on) return;
+    const auto t1 = std::chrono::steady_clock::now();
+    fprintf(stderr, "[%s] %-10s %.4f s\n", tag, what,
+            std::chrono::duration<double>(t1 - t0).count());
+    t0 = t1;
+  }
+};
+
+// Host threads for staging copies and planning: the GPU's share of the host
+// (OMP_NUM_THREADS on the pool's boxes), at most 16.
+inline unsigned host_threads() {
+  unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  if (const char* e = std::getenv("OMP_NUM_THREADS")) {
+    const int v = atoi(e);
+    if (v > 0) hw = (unsigned)v;
+  }
+  return std::min(hw, 16u);
+}
+
+// fn(lo, hi, part) over `parts` contiguous ranges of [0, n), part 0 on the
+// calling thread; fn must not throw.
+template <class F>
+void parallel_ranges(uint64_t n, unsigned parts, F fn) {
+  if (parts <= 1 || n < 2) {
+    fn(0, n, 0u);
+    return;
+  }
+  std::vector<std::thread> pool;
+  pool.reserve(parts - 1);
+  for (unsigned k = 1; k < parts; ++k)
+    pool.emplace_back([&fn, n, parts, k]() { fn(n * k / parts, n * (k + 1) / parts, k); });
+  fn(0, n / parts, 0u);
+  for (std::thread& th : pool) th.join();
+}
+
+// A host array left uninitialised (POD rows the planner writes itself, in
+// parallel: no sequential zero fill, and its pages fault in on the writing threads).
+template <class T>
+struct HostBuf {
+  std::unique_ptr<T[]> p;
+  uint64_t n = 0;
+  explicit HostBuf(uint64_t count = 0) : p(count ? new T[count] : nullptr), n(count) {}
+  T& operator[](uint64_t i) { return p[i]; }
+  const T& operator[](uint64_t i) const { return p[i]; }
+  T* data() { return p.get(); }
+  const T* data() const { return p.get(); }
+};
+
+}  // namespace magot

@@ -1,5 +1,6 @@
-"""Build the tile block packer (magot_amd/csrc/tileblocks.cpp) and its
-stand-alone driver tile_blocks_check.cpp host-only with AddressSanitizer +
+"""Build the extraction planner, the tile block packer and the host genome
+packer they plan over (magot_amd/csrc/tileplan.cpp, tileblocks.cpp, pack.cpp)
+and their stand-alone driver tile_blocks_check.cpp host-only with AddressSanitizer +
 UndefinedBehaviorSanitizer and run the driver (no GPU, nothing loaded into
 Python).
 
@@ -16,8 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 BUILD = os.path.join(HERE, 'build')
 EXE = os.path.join(BUILD, 'tile_blocks_check')
-SOURCES = [os.path.join(ROOT, 'magot_amd', 'csrc', 'tileblocks.cpp'),
-           os.path.join(HERE, 'tile_blocks_check.cpp')]
+SOURCES = [os.path.join(ROOT, 'magot_amd', 'csrc', name)
+           for name in ('tileblocks.cpp', 'tileplan.cpp', 'pack.cpp')]
+SOURCES.append(os.path.join(HERE, 'tile_blocks_check.cpp'))
 FLAGS = ['-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '--offload-arch=gfx950',
          '-x', 'hip', '--offload-host-only', '-I' + os.path.join(ROOT, 'include'),
          '-Xarch_host', '-fsanitize=address', '-Xarch_host', '-fsanitize=undefined',

@@ -8,12 +8,15 @@ hold what nearly all of its tiles stage (tile_geometry); the boundary cases
 pin the capacity to the largest geometry, 64 interval rows and 14 record rows
 (MAGOT_TILE_BLOCK_ROWS), and two cases run with the planner's own choice.
 
-The tiles come from `cut`, a transcription of magot_plan_create's tile cut
-(binary searches instead of cursors); the GPU cases use it only to assert that
-a workload really stages the row counts it is meant to.
+`cut` is an independent model of the planner's tile cut (binary searches
+instead of cursors; tests/test_tileplan.py holds the planner to it).  The
+workloads here are sized with the planner itself (`real_cut`, `plan_debug`),
+so the GPU cases' "this workload stages m = ..." assertions speak about the
+plan they run.
 """
 
 from bisect import bisect_left, bisect_right
+import ctypes
 
 import numpy as np
 import pytest
@@ -94,11 +97,55 @@ def cut(ex_out, tn, tp, lc, T0=0, R0=0, max_tiles=1 << 30):
     return np.array(out, dtype=TILE_DTYPE)
 
 
+def real_cut(ex_out, tn, tp, lc):
+    """The planner's own cut of these tables (magot_debug_tile_cut), in output
+    order: rows of TILE_DTYPE."""
+    L = _lib.lib()
+    a = [np.array(x, dtype=np.uint64) for x in (ex_out, tn, tp)]
+    n = np.zeros(1, dtype=np.uint64)
+    args = [_lib.ptr(a[0]), len(ex_out) - 1, _lib.ptr(a[1]), _lib.ptr(a[2]), len(tn) - 1, lc]
+    _lib.check(L.magot_debug_tile_cut(*args, None, 0, _lib.ptr(n)), 'tile count')
+    tiles = np.zeros(int(n[0]), dtype=TILE_DTYPE)
+    _lib.check(L.magot_debug_tile_cut(*args, _lib.ptr(tiles), len(tiles), _lib.ptr(n)), 'tile cut')
+    return tiles
+
+
+PLAN_INFO = ('B', 'P', 'Ec', 'Tc', 'n_tiles', 'lane_chunks', 'ex_rows', 'tx_rows', 'stride')
+
+
+def plan_debug(contigs, exons, txs, outputs=_lib.OUT_NUC | _lib.OUT_PEP):
+    """What magot_plan_create plans for these contigs (bytes each) and tables,
+    without a device (magot_debug_plan): a dict of PLAN_INFO integers and the
+    tables ex_g, ex_out (Ec + 1), tn, tp (Tc + 1), lay_nuc, lay_pep (per
+    record) and tiles (launch order).  Raises MagotError as plan creation would."""
+    L = _lib.lib()
+    bufs = [np.frombuffer(bytes(c), dtype=np.uint8) for c in contigs]
+    ptrs = (ctypes.POINTER(ctypes.c_uint8) * max(len(bufs), 1))()
+    for i, b in enumerate(bufs):
+        if len(b):
+            ptrs[i] = b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+    lens = np.array([len(b) for b in bufs], dtype=np.uint64)
+    exons = np.ascontiguousarray(exons, dtype=_lib.EXON_DTYPE)
+    txs = np.ascontiguousarray(txs, dtype=_lib.TX_DTYPE)
+    info = np.zeros(len(PLAN_INFO), dtype=np.uint64)
+    head = [ptrs, _lib.ptr(lens), len(bufs), _lib.ptr(exons), len(exons), _lib.ptr(txs), len(txs),
+            outputs, _lib.ptr(info)]
+    _lib.check(L.magot_debug_plan(*head, *[None] * 7), 'magot_debug_plan (sizes)')
+    out = dict(zip(PLAN_INFO, (int(x) for x in info)))
+    u8 = lambda n: np.zeros(n, dtype=np.uint64)
+    out.update(ex_g=u8(out['Ec'] + 1), ex_out=u8(out['Ec'] + 1), tn=u8(out['Tc'] + 1),
+               tp=u8(out['Tc'] + 1), lay_nuc=u8(len(txs)), lay_pep=u8(len(txs)),
+               tiles=np.zeros(out['n_tiles'], dtype=TILE_DTYPE))
+    _lib.check(L.magot_debug_plan(*head, *[_lib.ptr(out[k]) for k in (
+        'ex_g', 'ex_out', 'tn', 'tp', 'lay_nuc', 'lay_pep', 'tiles')]), 'magot_debug_plan')
+    return out
+
+
 def find_length(make_lens, lc, want, lengths):
-    """The first L of `lengths` for which the cut of layout(make_lens(L)) has a
-    tile with want(m, nt) true."""
+    """The first L of `lengths` for which the planner's cut of
+    layout(make_lens(L)) has a tile with want(m, nt) true."""
     for L in lengths:
-        t = cut(*layout(make_lens(L)), lc)
+        t = real_cut(*layout(make_lens(L)), lc)
         m = t['e2'].astype(np.int64) - t['e1']
         nt = t['j2'].astype(np.int64) - t['j1']
         if any(want(int(a), int(b)) for a, b in zip(m, nt)):
@@ -366,12 +413,12 @@ def with_records(w, recs, genome=None):
 
 
 def staged(w, lc):
-    """(m, nt) of every tile the planner cuts for w."""
+    """(m, nt) of every tile of the plan magot_plan_create builds for w (lc:
+    the lane chunks the environment forces), and the tiles in output order."""
     ex, tx = w.plan_tables()
-    lens = ex['len'].astype(np.int64)
-    recs = [[int(x) for x in lens[int(b):int(b) + int(n)] if x]
-            for b, n in zip(tx['exon_begin'], tx['n_exons'])]
-    t = cut(*layout(recs), lc)
+    plan = plan_debug([seq for _, seq in w.contigs()], ex, tx)
+    assert plan['lane_chunks'] == lc
+    t = plan['tiles'][np.argsort(plan['tiles']['T0'], kind='stable')]
     return list(zip((t['e2'].astype(np.int64) - t['e1']).tolist(),
                     (t['j2'].astype(np.int64) - t['j1']).tolist())), t
 
