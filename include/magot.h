@@ -460,6 +460,62 @@ int magot_orf6_time_b2b(magot_ctx* ctx, magot_orf6* o, int iters, double* avg_ms
 void magot_orf6_destroy(magot_orf6* o);
 
 /*
+ * ORF calling over the streams of an executed magot_orf6, where they lie in
+ * HBM: dna2orfs (genome_tools.py:145-180) once its contigs are Sequences.
+ * A record's streams are visited in the reference's loop order j = 2*frame +
+ * (strand == '+') (genome_tools.py:155-156), a frame-0 stream without one
+ * leading 'X' (genome.py:819-821); a stream of n residues with s stops gives
+ * s + 1 ORFs, empty ones included (split('*'), genome_tools.py:157).  ORF
+ * number i of a stream starts at residue k, one past the stop before it (0
+ * for the first); its position is (frame on '+', record length - frame on
+ * '-') + 3 * k (genome_tools.py:158-164).  The output string is the ORF, or
+ * with MAGOT_ORF_FROM_ATG 'M' + what follows its first 'M' with every further
+ * 'M' removed, 'M' alone when it has none (genome_tools.py:165-169).  A stream
+ * whose translate() is None (record length <= 2 + frame) has no ORFs and
+ * flags its record (MAGOT_ORF_REC_NONE: the reference raises AttributeError
+ * there).  With MAGOT_ORF_LONGEST each record keeps the first ORF in loop
+ * order whose output string is longest (genome_tools.py:172-175); a record
+ * all of whose strings are empty has no candidate and is flagged
+ * (MAGOT_ORF_REC_NO_LONGEST: the reference's IndexError, genome_tools.py:179),
+ * and there is one row per unflagged record.
+ *   magot_orfcall_create  runs the passes (o must have been executed, else
+ *       MAGOT_ERR_STATE; o must outlive the handle) and reports the table's
+ *       rows and the payload's bytes.
+ *   magot_orfcall_fetch   the rows, in the plan's record order and loop order
+ *       inside a record whatever order the six-frame kernel laid the streams
+ *       out in: record, stream j, start residue k, output length, offset in
+ *       the concatenated payload; the payload; one flag byte per record.  Any
+ *       pointer may be NULL.
+ *   magot_orfcall_text    the tool's FASTA text in one device buffer: per row
+ *       '>' name '-pos:' position '\n' string '\n' (genome_tools.py:177), or
+ *       with MAGOT_ORF_LONGEST '>' name '_longestORF\n' string '\n'
+ *       (genome_tools.py:174).  Record r's name is names[name_off[r],
+ *       name_off[r+1]) (any bytes).  *out_len receives the size;
+ *       magot_orfcall_text_fetch copies the text down (one D2H).
+ *   magot_orfcall_time    mean device time of the calling passes (text == 0)
+ *       or of the text passes of the last magot_orfcall_text (text != 0),
+ *       an event pair around each of `iters` runs.
+ * magot_orfcall_tile: residues per tile of the calling passes (an ORF may
+ * span any number of tiles).
+ */
+#define MAGOT_ORF_FROM_ATG 1u
+#define MAGOT_ORF_LONGEST 2u
+#define MAGOT_ORF_REC_NONE 1u
+#define MAGOT_ORF_REC_NO_LONGEST 2u
+typedef struct magot_orfcall magot_orfcall;
+uint32_t magot_orfcall_tile(void);
+int magot_orfcall_create(magot_ctx* ctx, magot_orf6* o, uint32_t flags, magot_orfcall** out,
+                         uint64_t* n_orfs, uint64_t* payload_bytes);
+int magot_orfcall_fetch(magot_ctx* ctx, magot_orfcall* c, uint32_t* record, uint8_t* stream,
+                        uint32_t* start, uint32_t* length, uint64_t* payload_off,
+                        uint8_t* payload, uint8_t* record_flags);
+int magot_orfcall_text(magot_ctx* ctx, magot_orfcall* c, const uint64_t* name_off,
+                       const uint8_t* names, uint64_t* out_len);
+int magot_orfcall_text_fetch(magot_ctx* ctx, magot_orfcall* c, uint8_t* out, uint64_t cap);
+int magot_orfcall_time(magot_ctx* ctx, magot_orfcall* c, int text, int iters, double* avg_ms);
+void magot_orfcall_destroy(magot_orfcall* c);
+
+/*
  * Native batch planner for gff2fasta (genome_tools.py:324-330).
  * Parses GFF3/GTF text with read_gff's rules and default arguments
  * (genome.py:242-415: '#'/8-tab acceptance, version sniffing, ID synthesis

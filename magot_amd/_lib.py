@@ -49,6 +49,8 @@ EXPORTS = (
     'magot_copy_segments', 'magot_ctx_mark', 'magot_ctx_elapsed', 'magot_orf6_copy_outputs',
     'magot_genome_wire_export', 'magot_genome_wire_import',
     'magot_debug_tile_blocks', 'magot_debug_tile_cut', 'magot_debug_plan',
+    'magot_orfcall_tile', 'magot_orfcall_create', 'magot_orfcall_fetch', 'magot_orfcall_text',
+    'magot_orfcall_text_fetch', 'magot_orfcall_time', 'magot_orfcall_destroy',
 )
 
 ERR_ARG = -1
@@ -62,6 +64,10 @@ GFF_LONGEST = 4
 GFF_GENOMIC = 8
 GFF_FROM_EXONS = 16
 PACK_HOST = 1
+ORF_FROM_ATG = 1
+ORF_LONGEST = 2
+ORF_REC_NONE = 1
+ORF_REC_NO_LONGEST = 2
 
 
 class MagotError(RuntimeError):
@@ -191,6 +197,15 @@ def _declare(lib):
         'magot_fasta_read': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_uint32), _vp, _vp,
                                             ctypes.c_uint64, _u64p, _vp, ctypes.c_uint64]),
+        'magot_orfcall_tile': (ctypes.c_uint32, []),
+        'magot_orfcall_create': (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.POINTER(_vp),
+                                                _u64p, _u64p]),
+        'magot_orfcall_fetch': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        'magot_orfcall_text': (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64p]),
+        'magot_orfcall_text_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_orfcall_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_double)]),
+        'magot_orfcall_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -1722,6 +1722,7 @@ struct magot_orf6 {
   uint8_t* out = nullptr;
   uint64_t n_rec = 0, total = 0;
   std::vector<uint64_t> host_soff;
+  bool executed = false;  // the streams are in HBM (magot_orfcall_create asks)
   void launch(hipStream_t s) const { launch_orf6(args, true, s); }
 };
 
@@ -1918,6 +1919,7 @@ int magot_orf6_execute(magot_ctx* ctx, magot_orf6* o) {
   }
   o->launch(ctx->stream);
   MAGOT_HIP_TRY(hipGetLastError());
+  o->executed = true;
   return MAGOT_OK;
 }
 
@@ -1967,6 +1969,7 @@ int magot_orf6_time(magot_ctx* ctx, magot_orf6* o, int iters, double* avg_ms) {
     MAGOT_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     total += ms;
   }
+  o->executed = true;
   *avg_ms = total / iters;
   return MAGOT_OK;
 }
@@ -1984,6 +1987,7 @@ int magot_orf6_time_b2b(magot_ctx* ctx, magot_orf6* o, int iters, double* avg_ms
   MAGOT_HIP_TRY(hipEventSynchronize(ctx->ev1));
   float ms = 0;
   MAGOT_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  o->executed = true;
   *avg_ms = (double)ms / iters;
   return MAGOT_OK;
 }
@@ -1993,6 +1997,305 @@ void magot_orf6_destroy(magot_orf6* o) {
   if (o->ctx) (void)hipSetDevice(o->ctx->device);
   if (o->arena) (void)hipFree(o->arena);
   delete o;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// ORF calling over the six-frame streams (orfcall.hip; dna2orfs,
+// genome_tools.py:145-180)
+// ---------------------------------------------------------------------------
+
+struct magot_orfcall {
+  magot_ctx* ctx = nullptr;
+  magot_orf6* o6 = nullptr;
+  std::vector<void*> mem;   // device allocations of the calling passes
+  std::vector<void*> tmem;  // of the last magot_orfcall_text
+  OrfCallArgs a{};
+  OrfTextArgs t{};
+  uint64_t payload_bytes = 0, sel_bytes = 0, text_bytes = 0;
+  bool has_text = false;
+  bool longest() const { return (a.mode & MAGOT_ORF_LONGEST) != 0; }
+  uint64_t rows() const { return longest() ? a.n_sel : a.n_orfs; }
+};
+
+namespace {
+
+template <class T>
+hipError_t orf_alloc(std::vector<void*>* mem, T** p, uint64_t count) {
+  void* d = nullptr;
+  // 64 bytes of slack: the span copies read whole 16-byte chunks around a payload
+  if (hipError_t e = hipMalloc(&d, count * sizeof(T) + 64)) return e;
+  mem->push_back(d);
+  *p = static_cast<T*>(d);
+  return hipSuccess;
+}
+
+// scan scratch for `count` elements (kept when the one at hand is large enough)
+hipError_t orf_scan_tmp(std::vector<void*>* mem, void** tmp, size_t* bytes, uint64_t count) {
+  const size_t need = orfcall_scan_bytes(count);
+  if (*tmp && need <= *bytes) return hipSuccess;
+  uint8_t* d = nullptr;
+  if (hipError_t e = orf_alloc(mem, &d, need)) return e;
+  *tmp = d;
+  *bytes = need;
+  return hipSuccess;
+}
+
+hipError_t orf_read_u64(const uint64_t* dev, uint64_t* host, hipStream_t s) {
+  if (hipError_t e = hipMemcpyAsync(host, dev, 8, hipMemcpyDeviceToHost, s)) return e;
+  return hipStreamSynchronize(s);
+}
+
+// every calling pass again, over the buffers magot_orfcall_create sized
+hipError_t orf_run(const magot_orfcall* c, hipStream_t s) {
+  if (hipError_t e = launch_orfcall_streams(c->a, s)) return e;
+  if (hipError_t e = launch_orfcall_count(c->a, s)) return e;
+  if (hipError_t e = launch_orfcall_write(c->a, s)) return e;
+  if (!c->longest()) return hipSuccess;
+  if (hipError_t e = launch_orfcall_longest(c->a, s)) return e;
+  return launch_orfcall_compact(c->a, s);
+}
+
+void orf_free(std::vector<void*>* mem) {
+  for (void* d : *mem) (void)hipFree(d);
+  mem->clear();
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t magot_orfcall_tile(void) { return kOrfCallTile; }
+
+void magot_orfcall_destroy(magot_orfcall* c) {
+  if (!c) return;
+  if (c->ctx) (void)hipSetDevice(c->ctx->device);
+  orf_free(&c->tmem);
+  orf_free(&c->mem);
+  delete c;
+}
+
+int magot_orfcall_create(magot_ctx* ctx, magot_orf6* o, uint32_t flags, magot_orfcall** out,
+                         uint64_t* n_orfs, uint64_t* payload_bytes) {
+  if (int rc = bind(ctx)) return rc;
+  if (!o || !out || (flags & ~(MAGOT_ORF_FROM_ATG | MAGOT_ORF_LONGEST))) {
+    set_error("magot_orfcall_create: null argument or unknown flag");
+    return MAGOT_ERR_ARG;
+  }
+  *out = nullptr;
+  if (!o->executed) {
+    set_error("magot_orfcall_create: execute the six-frame plan first");
+    return MAGOT_ERR_STATE;
+  }
+  const uint64_t n = o->n_rec;
+  if (6 * n + 1 >= (1ull << 32)) {
+    set_error("magot_orfcall_create: too many records (stream indices are 32-bit)");
+    return MAGOT_ERR_ARG;
+  }
+  struct Guard {
+    magot_orfcall* c;
+    ~Guard() { magot_orfcall_destroy(c); }
+  } guard{new magot_orfcall()};
+  magot_orfcall* c = guard.c;
+  c->ctx = ctx;
+  c->o6 = o;
+  OrfCallArgs& a = c->a;
+  hipStream_t s = ctx->stream;
+  a.mode = flags;
+  a.res = o->out;
+  a.n_rec = n;
+  uint64_t *soff = nullptr, *noff = nullptr;
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &soff, 6 * n + 1));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &noff, n + 1));
+  MAGOT_HIP_TRY(hipMemcpyAsync(soff, o->host_soff.data(), (6 * n + 1) * 8, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(noff, o->plan->nuc_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  a.soff = soff;
+  a.noff = noff;
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.scnt, 6 * n + 1));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.tile_first, 6 * n + 1));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.flags, n + 1));
+  MAGOT_HIP_TRY(orf_scan_tmp(&c->mem, &a.scan_tmp, &a.scan_bytes, 6 * n + 1));
+  MAGOT_HIP_TRY(launch_orfcall_streams(a, s));
+  MAGOT_HIP_TRY(orf_read_u64(a.tile_first + 6 * n, &a.n_tiles, s));
+  const uint64_t nt = a.n_tiles;
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.tile_stream, nt));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.orfs, nt + 1));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.kept, nt + 1));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.extra, nt));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.tflags, nt));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.tseen, nt));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.obase, nt + 1));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.kbase, nt + 1));
+  MAGOT_HIP_TRY(orf_scan_tmp(&c->mem, &a.scan_tmp, &a.scan_bytes, nt + 1));
+  MAGOT_HIP_TRY(launch_orfcall_count(a, s));
+  MAGOT_HIP_TRY(orf_read_u64(a.obase + nt, &a.n_orfs, s));
+  MAGOT_HIP_TRY(orf_read_u64(a.kbase + nt, &c->payload_bytes, s));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.rec, a.n_orfs));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.j, a.n_orfs));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.k, a.n_orfs));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.len, a.n_orfs));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.poff, a.n_orfs));
+  MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.payload, c->payload_bytes));
+  MAGOT_HIP_TRY(launch_orfcall_write(a, s));
+  if (c->longest()) {
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.sel, n));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.valid, n + 1));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.sellen, n + 1));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.slot, n + 1));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.cpoff, n + 1));
+    MAGOT_HIP_TRY(launch_orfcall_longest(a, s));
+    MAGOT_HIP_TRY(orf_read_u64(a.slot + n, &a.n_sel, s));
+    MAGOT_HIP_TRY(orf_read_u64(a.cpoff + n, &c->sel_bytes, s));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.c_rec, a.n_sel));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.c_j, a.n_sel));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.c_k, a.n_sel));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.c_len, a.n_sel));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.c_poff, a.n_sel));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.c_payload, c->sel_bytes));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.src_off, a.n_sel));
+    MAGOT_HIP_TRY(orf_alloc(&c->mem, &a.dst_off, a.n_sel + 1));
+    MAGOT_HIP_TRY(launch_orfcall_compact(a, s));
+  }
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  if (n_orfs) *n_orfs = c->rows();
+  if (payload_bytes) *payload_bytes = c->longest() ? c->sel_bytes : c->payload_bytes;
+  guard.c = nullptr;
+  *out = c;
+  return MAGOT_OK;
+}
+
+int magot_orfcall_fetch(magot_ctx* ctx, magot_orfcall* c, uint32_t* record, uint8_t* stream,
+                        uint32_t* start, uint32_t* length, uint64_t* payload_off,
+                        uint8_t* payload, uint8_t* record_flags) {
+  if (int rc = bind(ctx)) return rc;
+  if (!c) {
+    set_error("magot_orfcall_fetch: null handle");
+    return MAGOT_ERR_ARG;
+  }
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const OrfCallArgs& a = c->a;
+  const bool lg = c->longest();
+  const uint64_t n = c->rows(), pb = lg ? c->sel_bytes : c->payload_bytes;
+  auto down = [](void* dst, const void* src, uint64_t bytes) {
+    return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  MAGOT_HIP_TRY(down(record, lg ? a.c_rec : a.rec, n * 4));
+  MAGOT_HIP_TRY(down(stream, lg ? a.c_j : a.j, n));
+  MAGOT_HIP_TRY(down(start, lg ? a.c_k : a.k, n * 4));
+  MAGOT_HIP_TRY(down(length, lg ? a.c_len : a.len, n * 4));
+  MAGOT_HIP_TRY(down(payload_off, lg ? a.c_poff : a.poff, n * 8));
+  MAGOT_HIP_TRY(down(payload, lg ? a.c_payload : a.payload, pb));
+  MAGOT_HIP_TRY(down(record_flags, a.flags, a.n_rec));
+  return MAGOT_OK;
+}
+
+int magot_orfcall_text(magot_ctx* ctx, magot_orfcall* c, const uint64_t* name_off,
+                       const uint8_t* names, uint64_t* out_len) {
+  if (int rc = bind(ctx)) return rc;
+  if (!c || !name_off || !out_len) {
+    set_error("magot_orfcall_text: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  const OrfCallArgs& a = c->a;
+  const uint64_t n = a.n_rec, ne = c->rows();
+  const bool lg = c->longest();
+  // each record's header, behind the newline that ends the entry before it
+  static const char kPos[] = "-pos:", kLongest[] = "_longestORF\n";
+  const char* const tail = lg ? kLongest : kPos;
+  const size_t tail_len = std::strlen(tail);
+  std::string hdr;
+  std::vector<uint64_t> hoff(n + 1);
+  for (uint64_t r = 0; r < n; ++r) {
+    if (name_off[r + 1] < name_off[r] || (name_off[r + 1] > name_off[r] && !names) ||
+        name_off[r + 1] - name_off[r] >= (1ull << 31)) {
+      set_error("magot_orfcall_text: bad name table");
+      return MAGOT_ERR_ARG;
+    }
+    hoff[r] = hdr.size();
+    hdr += "\n>";
+    if (name_off[r + 1] > name_off[r])
+      hdr.append(reinterpret_cast<const char*>(names) + name_off[r], name_off[r + 1] - name_off[r]);
+    hdr.append(tail, tail_len);
+  }
+  hoff[n] = hdr.size();
+  c->has_text = false;
+  orf_free(&c->tmem);
+  OrfTextArgs& t = c->t;
+  t = OrfTextArgs{};
+  hipStream_t s = ctx->stream;
+  t.longest = lg;
+  t.n = ne;
+  t.rec = lg ? a.c_rec : a.rec;
+  t.j = lg ? a.c_j : a.j;
+  t.k = lg ? a.c_k : a.k;
+  t.len = lg ? a.c_len : a.len;
+  t.poff = lg ? a.c_poff : a.poff;
+  t.payload = lg ? a.c_payload : a.payload;
+  t.noff = a.noff;
+  uint64_t* d_hoff = nullptr;
+  MAGOT_HIP_TRY(orf_alloc(&c->tmem, &d_hoff, n + 1));
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_hoff, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  t.hoff = d_hoff;
+  t.dig_off = (hdr.size() + 15) & ~15ull;
+  MAGOT_HIP_TRY(orf_alloc(&c->tmem, &t.text, t.dig_off + (lg ? 0 : kOrfDigits * ne)));
+  if (!hdr.empty())
+    MAGOT_HIP_TRY(hipMemcpyAsync(t.text, hdr.data(), hdr.size(), hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(orf_alloc(&c->tmem, &t.tlen, ne + 1));
+  MAGOT_HIP_TRY(orf_alloc(&c->tmem, &t.tstart, ne + 1));
+  MAGOT_HIP_TRY(orf_scan_tmp(&c->tmem, &t.scan_tmp, &t.scan_bytes, ne + 1));
+  MAGOT_HIP_TRY(launch_orftext_sizes(t, s));
+  MAGOT_HIP_TRY(orf_read_u64(t.tstart + ne, &c->text_bytes, s));  // also: hdr is uploaded
+  MAGOT_HIP_TRY(orf_alloc(&c->tmem, &t.out, c->text_bytes));
+  MAGOT_HIP_TRY(launch_orftext_copy(t, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  c->has_text = true;
+  *out_len = c->text_bytes;
+  return MAGOT_OK;
+}
+
+int magot_orfcall_text_fetch(magot_ctx* ctx, magot_orfcall* c, uint8_t* out, uint64_t cap) {
+  if (int rc = bind(ctx)) return rc;
+  if (!c || !c->has_text) {
+    set_error("magot_orfcall_text_fetch: call magot_orfcall_text first");
+    return c ? MAGOT_ERR_STATE : MAGOT_ERR_ARG;
+  }
+  if (cap < c->text_bytes || (c->text_bytes && !out)) {
+    set_error("magot_orfcall_text_fetch: output buffer too small");
+    return MAGOT_ERR_ARG;
+  }
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (c->text_bytes) MAGOT_HIP_TRY(hipMemcpy(out, c->t.out, c->text_bytes, hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+int magot_orfcall_time(magot_ctx* ctx, magot_orfcall* c, int text, int iters, double* avg_ms) {
+  if (int rc = bind(ctx)) return rc;
+  if (!c || !avg_ms || iters <= 0) {
+    set_error("magot_orfcall_time: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  if (text && !c->has_text) {
+    set_error("magot_orfcall_time: call magot_orfcall_text first");
+    return MAGOT_ERR_STATE;
+  }
+  double total = 0;
+  for (int i = 0; i < iters; ++i) {
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    if (text) {
+      MAGOT_HIP_TRY(launch_orftext_sizes(c->t, ctx->stream));
+      MAGOT_HIP_TRY(launch_orftext_copy(c->t, ctx->stream));
+    } else {
+      MAGOT_HIP_TRY(orf_run(c, ctx->stream));
+    }
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    MAGOT_HIP_TRY(hipEventSynchronize(ctx->ev1));
+    float ms = 0;
+    MAGOT_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    total += ms;
+  }
+  *avg_ms = total / iters;
+  return MAGOT_OK;
 }
 
 }  // extern "C"

@@ -500,6 +500,75 @@ void launch_text_assembly(const TextUnit* units, uint64_t n, const uint64_t* rsp
                           uint64_t* psrc, uint64_t* end, void* scan_tmp, size_t scan_bytes,
                           uint8_t* out, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// ORF calling over the six-frame streams (orfcall.hip; magot_orfcall_*)
+// ---------------------------------------------------------------------------
+constexpr uint32_t kOrfCallTile = 1024;  // residues per tile: 16 per lane of one wave
+constexpr uint8_t kOrfFlagNone = 1;       // a stream whose translate() is None
+constexpr uint8_t kOrfFlagNoLongest = 2;  // longest: every output string is empty
+constexpr uint32_t kOrfDigits = 12;       // scratch bytes per ORF: decimal position + '\n'
+struct OrfCallArgs {
+  uint32_t mode;             // MAGOT_ORF_*
+  const uint8_t* res;        // the six-frame kernel's output
+  const uint64_t* soff;      // 6n + 1 stream offsets, record order, loop order inside
+  const uint64_t* noff;      // n + 1 record offsets (for the record lengths)
+  uint64_t n_rec;
+  uint32_t* scnt;            // 6n + 1: tiles per stream (the last entry 0)
+  uint64_t* tile_first;      // 6n + 1: their prefix
+  uint8_t* flags;            // n: kOrfFlag*
+  uint64_t n_tiles;
+  uint32_t* tile_stream;     // n_tiles: 6 * record + j
+  uint32_t *orfs, *kept;     // n_tiles + 1: ORFs owned, output bytes
+  uint32_t* extra;           // from_atg: more bytes when the running ORF has had its M
+  uint8_t *tflags, *tseen;   // from_atg: the tile's marks; the carried bit
+  uint64_t *obase, *kbase;   // n_tiles + 1: prefixes of orfs / kept
+  uint64_t n_orfs;
+  uint32_t* rec;             // the table, n_orfs rows
+  uint8_t* j;
+  uint32_t *k, *len;
+  uint64_t* poff;
+  uint8_t* payload;
+  // longest
+  uint64_t* sel;             // n: the chosen ORF
+  uint32_t *valid, *sellen;  // n + 1
+  uint64_t *slot, *cpoff;    // n + 1: prefixes of valid / sellen
+  uint64_t n_sel;
+  uint32_t* c_rec;           // the chosen rows, n_sel
+  uint8_t* c_j;
+  uint32_t *c_k, *c_len;
+  uint64_t* c_poff;
+  uint8_t* c_payload;
+  uint64_t *src_off, *dst_off;  // n_sel, n_sel + 1: the payload's segment copy
+  void* scan_tmp;
+  size_t scan_bytes;
+};
+struct OrfTextArgs {
+  int longest;
+  uint64_t n;                // entries (ORFs, or chosen rows)
+  const uint32_t* rec;
+  const uint8_t* j;
+  const uint32_t *k, *len;
+  const uint64_t* poff;
+  const uint8_t* payload;
+  const uint64_t* noff;
+  const uint64_t* hoff;      // n_rec + 1: each record's '\n' + header in text
+  uint8_t* text;             // the headers, then kOrfDigits bytes per entry at dig_off
+  uint64_t dig_off;
+  uint32_t* tlen;            // n + 1
+  uint64_t* tstart;          // n + 1
+  uint8_t* out;
+  void* scan_tmp;
+  size_t scan_bytes;
+};
+size_t orfcall_scan_bytes(uint64_t n);
+hipError_t launch_orfcall_streams(const OrfCallArgs& a, hipStream_t s);
+hipError_t launch_orfcall_count(const OrfCallArgs& a, hipStream_t s);
+hipError_t launch_orfcall_write(const OrfCallArgs& a, hipStream_t s);
+hipError_t launch_orfcall_longest(const OrfCallArgs& a, hipStream_t s);
+hipError_t launch_orfcall_compact(const OrfCallArgs& a, hipStream_t s);
+hipError_t launch_orftext_sizes(const OrfTextArgs& a, hipStream_t s);
+hipError_t launch_orftext_copy(const OrfTextArgs& a, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

@@ -890,6 +890,105 @@ class Orf6Plan(object):
             pass
 
 
+# Residues per tile of the ORF-calling passes (kOrfCallTile, orfcall.hip;
+# magot_orfcall_tile() is checked against it): an ORF may span any number.
+ORFCALL_TILE = 1024
+
+ORF_TABLE_DTYPE = np.dtype([('record', '<u4'), ('stream', 'u1'), ('start', '<u4'),
+                            ('length', '<u4'), ('payload_off', '<u8')])
+
+
+class OrfCalls(object):
+    """ORFs called on the device from an executed Orf6Plan's streams
+    (magot_orfcall_*): dna2orfs (genome_tools.py:145-180) over the plan's
+    records.  ``table()`` gives one row per ORF (``longest``: per unflagged
+    record) in record order and the reference's loop order inside a record
+    (stream j = 2*frame + (strand == '+')), the concatenated output strings
+    and a flag byte per record (_lib.ORF_REC_NONE: a stream whose translate()
+    is None; _lib.ORF_REC_NO_LONGEST: no longest candidate).  ``text(names)``
+    gives the tool's FASTA text, assembled on the device."""
+
+    def __init__(self, orf6plan, from_atg=False, longest=False):
+        L = _lib.lib()
+        if L.magot_orfcall_tile() != ORFCALL_TILE:
+            raise MagotError('ORFCALL_TILE does not match the library')
+        self.ctx = orf6plan.ctx
+        self._keep = orf6plan
+        self.n_records = orf6plan.plan.n_tx
+        self.from_atg, self.longest = bool(from_atg), bool(longest)
+        flags = (_lib.ORF_FROM_ATG if from_atg else 0) | (_lib.ORF_LONGEST if longest else 0)
+        h = ctypes.c_void_p()
+        n, pb = ctypes.c_uint64(), ctypes.c_uint64()
+        check(L.magot_orfcall_create(self.ctx.handle, orf6plan.handle, flags, ctypes.byref(h),
+                                     ctypes.byref(n), ctypes.byref(pb)), 'magot_orfcall_create')
+        self.handle = h
+        self.n_orfs = n.value
+        self.payload_bytes = pb.value
+
+    def table(self):
+        """(rows ORF_TABLE_DTYPE[n_orfs], payload uint8[payload_bytes], record
+        flags uint8[n_records])."""
+        n = self.n_orfs
+        rec = np.empty(max(n, 1), np.uint32)
+        st = np.empty(max(n, 1), np.uint8)
+        k = np.empty(max(n, 1), np.uint32)
+        ln = np.empty(max(n, 1), np.uint32)
+        po = np.empty(max(n, 1), np.uint64)
+        pay = np.empty(max(self.payload_bytes, 1), np.uint8)
+        fl = np.zeros(max(self.n_records, 1), np.uint8)
+        check(_lib.lib().magot_orfcall_fetch(self.ctx.handle, self.handle, ptr(rec), ptr(st),
+                                             ptr(k), ptr(ln), ptr(po), ptr(pay), ptr(fl)),
+              'magot_orfcall_fetch')
+        rows = np.empty(n, ORF_TABLE_DTYPE)
+        rows['record'], rows['stream'], rows['start'] = rec[:n], st[:n], k[:n]
+        rows['length'], rows['payload_off'] = ln[:n], po[:n]
+        return rows, pay[:self.payload_bytes], fl[:self.n_records]
+
+    def flags(self):
+        """The flag byte of every record."""
+        fl = np.zeros(max(self.n_records, 1), np.uint8)
+        check(_lib.lib().magot_orfcall_fetch(self.ctx.handle, self.handle, None, None, None,
+                                             None, None, None, ptr(fl)), 'magot_orfcall_fetch')
+        return fl[:self.n_records]
+
+    def text(self, names):
+        """The FASTA text (a uint8 array) for one name per record (str or
+        bytes, any bytes): '>name-pos:P\nORF\n' per ORF, or with ``longest``
+        '>name_longestORF\nORF\n' per unflagged record."""
+        if len(names) != self.n_records:
+            raise ValueError('one name per record')
+        buf, off = _concat(names)
+        size = ctypes.c_uint64()
+        L = _lib.lib()
+        check(L.magot_orfcall_text(self.ctx.handle, self.handle, ptr(off),
+                                   ptr(buf) if len(buf) else None, ctypes.byref(size)),
+              'magot_orfcall_text')
+        out = np.empty(max(size.value, 1), np.uint8)
+        check(L.magot_orfcall_text_fetch(self.ctx.handle, self.handle, ptr(out), size.value),
+              'magot_orfcall_text_fetch')
+        return out[:size.value]
+
+    def time(self, iters, text=False):
+        """Mean device time (ms) of the calling passes, or with ``text`` of the
+        text passes of the last ``text()`` call."""
+        ms = ctypes.c_double()
+        check(_lib.lib().magot_orfcall_time(self.ctx.handle, self.handle, int(bool(text)),
+                                            int(iters), ctypes.byref(ms)), 'magot_orfcall_time')
+        return ms.value
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_orfcall_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's
@@ -966,4 +1065,4 @@ __all__ = ['DeviceGenome', 'ExtractionPlan', 'revcomp_batch', 'translate_batch',
            'OUT_NUC',
            'OUT_PEP', 'MagotError', 'GffPlan', 'orf6_batch', 'Orf6Plan', 'fasta_read',
            'FastaGenome', 'PartitionedGenome', 'device_genome', 'extract_records', 'plan_parts',
-           'copy_segments', 'orf6_sizes']
+           'copy_segments', 'orf6_sizes', 'OrfCalls', 'ORFCALL_TILE', 'ORF_TABLE_DTYPE']

@@ -10,11 +10,15 @@
     python -m magot_amd.genome_tools blast_csv2fasta <fasta> <blast.csv> [order=py2|insertion]
     python -m magot_amd.genome_tools exonerate2fasta <fasta> <exonerate.txt> [order=py2|insertion]
     python -m magot_amd.genome_tools get_seq_from_fasta <fasta> <seq_name> [truncate_names=False]
+    python -m magot_amd.genome_tools dna2orfs <fasta> <out.fasta> [from_atg=1] [longest=1]
+           [order=py2|insertion] [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
 ``eval``s the assembled call; here values are parsed as Python literals
-(``True``/``False``/numbers) and never executed.
+(``True``/``False``/numbers) and never executed.  ``dna2orfs`` takes its two
+switches by the reference's truthiness instead: any non-empty value, the text
+``False`` included, switches them on (genome_tools.py:149, 165).
 
 Record order defaults to ``py2`` so the bytes written match the reference's
 own goldens (test_data/test_suite.py:12-13); ``order=insertion`` gives the
@@ -549,11 +553,122 @@ def get_seq_from_fasta(genome_sequence, seq_name, truncate_names='False'):
     _write(g.get_scaffold_fasta(seq_name) + '\n')
 
 
+def _dna2orfs_native(fasta_location, from_atg, longest, order):
+    """dna2orfs' text (bytes) from the device: the FASTA packed natively, one
+    '+' whole-contig record per contig in output order, the six-frame kernel,
+    the ORF-calling passes and the text assembly; the host sees the final
+    bytes only.  None when the FASTA needs the Python reader, the genome
+    exceeds one device plane, or a record is flagged (the reference raises
+    there: the loop in dna2orfs reproduces it)."""
+    from . import py2order
+    dev = engine.FastaGenome.load(genome.read_buffer(fasta_location))
+    if dev is None:
+        return None
+    plan = o6 = calls = None
+    try:
+        if dev.total_bases > engine.PART_BASES:
+            return None
+        names = py2order.dict_order(dev.names) if order == 'py2' else list(dev.names)
+        if not names:
+            return b''
+        idx = np.array([dev.index[nm] for nm in names], dtype=np.int64)
+        ex = np.zeros(len(names), dtype=engine.EXON_DTYPE)
+        ex['contig'] = idx
+        ex['len'] = np.asarray(dev.lengths, dtype=np.uint64)[idx]
+        tx = np.zeros(len(names), dtype=engine.TX_DTYPE)
+        tx['exon_begin'] = np.arange(len(names))
+        tx['n_exons'] = 1
+        plan = engine.ExtractionPlan(dev, ex, tx, engine.OUT_NUC)
+        o6 = engine.Orf6Plan(plan)
+        o6.execute()
+        calls = engine.OrfCalls(o6, from_atg=from_atg, longest=longest)
+        if calls.flags().any():
+            return None
+        return calls.text(names).tobytes()
+    finally:
+        for obj in (calls, o6, plan, dev):
+            if obj is not None:
+                obj.close()
+
+
+def dna2orfs(fasta_location, output_file, from_atg=False, longest=False, order='py2',
+             native='True'):
+    """genome_tools.py:145-180: every contig translated in six frames, each
+    translation split at its stops, one FASTA record per ORF
+    ('>contig-pos:P'), or with ``longest`` the longest one per contig
+    ('>contig_longestORF'); ``from_atg`` cuts each ORF to 'M' + what follows
+    its first M (further Ms removed, as the reference's join does).
+
+    ``from_atg`` and ``longest`` follow the reference's truthiness: from the
+    command line every value is a non-empty string, so ``from_atg=False``
+    switches it on.  Contigs come in the reference's Python 2 dict order
+    unless ``order='insertion'``.
+
+    One deliberate deviation: the reference hands ``translate`` a plain
+    ``str`` contig and dies with a TypeError on the first one (SURVEY row
+    14); here contigs are Sequences, which is what every other line of the
+    function assumes.
+
+    The ORFs are called on the device (engine.OrfCalls).  A contig of <= 4
+    bases (translate() is None for frame 2: AttributeError) or, with
+    ``longest``, a contig with no non-empty ORF (IndexError), a genome above
+    one device plane and a FASTA that needs the Python reader take the loop
+    below, which writes what the reference writes up to the failure and
+    raises what it raises; ``native=False`` forces it."""
+    from_atg, longest = bool(from_atg), bool(longest)
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'insertion' or 'py2'")
+    if native == 'True' and isinstance(fasta_location, str) and os.path.isfile(fasta_location):
+        text = _dna2orfs_native(fasta_location, from_atg, longest, order)
+        if text is not None:
+            with open(output_file, 'wb') as out:
+                out.write(text)
+            return
+    from . import py2order
+    seqs = genome.Genome(fasta_location).genome_sequence
+    names = py2order.dict_order(list(seqs)) if order == 'py2' else list(seqs)
+    with open(output_file, 'wb') as out:
+        batch, bases = [], 0
+        for i, name in enumerate(names):
+            batch.append(name)
+            bases += len(seqs[name])
+            if bases < (1 << 28) and i + 1 < len(names):
+                continue
+            sixes = engine.orf6_batch([seqs[nm] for nm in batch])  # one launch per batch
+            for nm, six in zip(batch, sixes):
+                _dna2orfs_contig(out, nm, len(seqs[nm]), six, from_atg, longest)
+            batch, bases = [], 0
+
+
+def _dna2orfs_contig(out, name, length, six, from_atg, longest):
+    """genome_tools.py:152-179 for one contig from its six translations (loop
+    order: frame 0, 1, 2 x strand '-', '+')."""
+    candidates, best = [], 0
+    for j, translated in enumerate(six):
+        frame, plus = j >> 1, j & 1
+        if translated is None:
+            raise AttributeError("'NoneType' object has no attribute 'split'")
+        pos = frame if plus else length - frame
+        for orf in translated.split('*'):
+            start = pos
+            pos += (1 + len(orf)) * 3
+            output_orf = 'M' + ''.join(orf.split('M')[1:]) if from_atg else orf
+            if longest:
+                if len(output_orf) > best:
+                    candidates.append('>' + name + '_longestORF\n' + output_orf + '\n')
+                    best = len(output_orf)
+            else:
+                out.write(('>' + name + '-pos:' + str(start) + '\n' + output_orf +
+                           '\n').encode('latin-1'))
+    if longest:
+        out.write(candidates[-1].encode('latin-1'))
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep,
          'extract_upstream_downstream': extract_upstream_downstream,
          'coords2fasta': coords2fasta,
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,
-         'get_seq_from_fasta': get_seq_from_fasta}
+         'get_seq_from_fasta': get_seq_from_fasta, 'dna2orfs': dna2orfs}
 
 
 def parse_argv(argv):
