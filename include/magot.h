@@ -618,6 +618,86 @@ int magot_fasta_text_fetch(magot_ctx* ctx, magot_fasta_text* t, uint8_t* out, ui
 int magot_fasta_text_time(magot_ctx* ctx, magot_fasta_text* t, int iters, double* avg_ms);
 void magot_fasta_text_destroy(magot_fasta_text* t);
 
+/*
+ * mask_from_gff (genome_tools.py:394-428): every base under a GFF feature of
+ * one type lower-cased (soft) or replaced by 'N' (MAGOT_MASK_HARD), after the
+ * whole genome was upper-cased unless MAGOT_MASK_KEEP_CASE (the reference's
+ * overwrite_softmask "False"); both case changes are ASCII-only.
+ *
+ * Host planner (genome_tools.py:410-426).  magot_mask_plan scans the GFF text:
+ * every line with more than five tabs counts, '#' lines included
+ * (genome_tools.py:412); a line is used when fields[2] == feature_type
+ * (:414); int(fields[3]) and int(fields[4]) are read as magot_flank_plan reads
+ * them (:415-416).  The table holds {contig, 0-based start, length} pieces of
+ * the slices lst[start - 1:stop] (:418, :423), clipped to the contig, lines
+ * that change nothing dropped, in GFF order, unsorted and unmerged; a slice
+ * longer than magot_mask_piece() bases is cut into pieces of at most that
+ * many, so no device lane owns more.  In-range features are idempotent and
+ * commute, so the table is exact however they overlap.  MAGOT_ERR_UNSUPPORTED
+ * where the reference's sequential replay matters: a bad integer
+ * (ValueError), an unknown fields[0] (KeyError), a negative slice index
+ * (start < 1 or stop < 0) on a line that changes anything, a hard mask that
+ * changes the list's length (stop > len with start <= stop, :420-423).  The
+ * caller's line loop reproduces those.  seqids / contig_lens as for
+ * magot_gff_plan; contigs of 4 Gbases or more are refused (MAGOT_ERR_ARG).
+ *   magot_maskplan_table   the rows in place (valid until destroy; NULL when
+ *       empty), their count and the plan's flags; any pointer may be NULL.
+ *   magot_mask_fasta_check MAGOT_OK when the n_contigs contigs the native
+ *       reader (magot_genome_load_fasta / magot_fasta_read, truncate_names)
+ *       found in `text` are the entries the reference's own read loop builds
+ *       (genome_tools.py:398-409); MAGOT_ERR_UNSUPPORTED for sequence before
+ *       the first header (KeyError, :404), whitespace directly after '>' (the
+ *       name is line.split()[0][1:], :400), an empty contig (kept and
+ *       printed, :401) or a repeated name (reset, :401).
+ *
+ * Device object (genome_tools.py:427-428: '>' name '\n' sequence '\n' per
+ * contig, the sequence on one line).  `p` is a nucleotide extraction plan
+ * with one record per contig of the output, in output order, each gathering
+ * its contig whole on '+' (record r is contig rec_contig[r]; every contig of
+ * the mask plan in exactly one record, lengths checked); it reproduces every
+ * input byte.  Record r's name is names[name_off[r], name_off[r+1]).
+ *   magot_mask_create   uploads the pieces and headers and sizes the buffers;
+ *       *text_bytes is the size of the final text.  p must outlive the
+ *       handle; mp may be destroyed on return.
+ *   magot_mask_execute  enqueues, on the context stream, the zeroing of the
+ *       coverage plane (one bit per byte of p's nucleotide output),
+ *       mask_paint_kernel and mask_text_kernel (p must have been executed,
+ *       else MAGOT_ERR_STATE).
+ *   magot_mask_fetch    synchronises and copies the text down (one D2H).
+ *   magot_mask_coverage_fetch  the plane's words (bit i of word w = byte
+ *       32 * w + i of p's output, which holds record r at magot_plan_layout's
+ *       nuc_start[r]); *n_words alone when words == NULL.  For tests.
+ *   magot_mask_time     mean device time over `iters` runs of the zeroing +
+ *       paint (paint_ms) and of the text kernel (text_ms), an event pair
+ *       around each.
+ */
+#define MAGOT_MASK_HARD 1u
+#define MAGOT_MASK_KEEP_CASE 2u
+typedef struct magot_mask_interval {
+  uint32_t contig;
+  uint32_t start;
+  uint32_t len;
+} magot_mask_interval;
+typedef struct magot_maskplan magot_maskplan;
+typedef struct magot_mask magot_mask;
+uint32_t magot_mask_piece(void);
+int magot_mask_plan(const char* gff, uint64_t gff_len, const char* const* seqids,
+                    const uint64_t* contig_lens, uint32_t n_contigs, const char* feature_type,
+                    uint32_t flags, magot_maskplan** out, uint64_t* n_intervals);
+int magot_maskplan_table(const magot_maskplan* p, const magot_mask_interval** rows,
+                         uint64_t* n_intervals, uint32_t* flags);
+void magot_maskplan_destroy(magot_maskplan* p);
+int magot_mask_fasta_check(const char* text, uint64_t len, uint32_t n_contigs);
+int magot_mask_create(magot_ctx* ctx, const magot_plan* p, const magot_maskplan* mp,
+                      const uint32_t* rec_contig, const uint64_t* name_off, const uint8_t* names,
+                      magot_mask** out, uint64_t* text_bytes);
+int magot_mask_execute(magot_ctx* ctx, magot_mask* m);
+int magot_mask_fetch(magot_ctx* ctx, magot_mask* m, uint8_t* out, uint64_t cap);
+int magot_mask_coverage_fetch(magot_ctx* ctx, magot_mask* m, uint32_t* words, uint64_t cap_words,
+                              uint64_t* n_words);
+int magot_mask_time(magot_ctx* ctx, magot_mask* m, int iters, double* paint_ms, double* text_ms);
+void magot_mask_destroy(magot_mask* m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,9 @@ EXPORTS = (
     'magot_debug_tile_blocks', 'magot_debug_tile_cut', 'magot_debug_plan',
     'magot_orfcall_tile', 'magot_orfcall_create', 'magot_orfcall_fetch', 'magot_orfcall_text',
     'magot_orfcall_text_fetch', 'magot_orfcall_time', 'magot_orfcall_destroy',
+    'magot_mask_piece', 'magot_mask_plan', 'magot_maskplan_table', 'magot_maskplan_destroy',
+    'magot_mask_fasta_check', 'magot_mask_create', 'magot_mask_execute', 'magot_mask_fetch',
+    'magot_mask_coverage_fetch', 'magot_mask_time', 'magot_mask_destroy',
 )
 
 ERR_ARG = -1
@@ -68,6 +71,9 @@ ORF_FROM_ATG = 1
 ORF_LONGEST = 2
 ORF_REC_NONE = 1
 ORF_REC_NO_LONGEST = 2
+MASK_HARD = 1
+MASK_KEEP_CASE = 2
+MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
 class MagotError(RuntimeError):
@@ -206,6 +212,23 @@ def _declare(lib):
         'magot_orfcall_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_double)]),
         'magot_orfcall_destroy': (None, [_vp]),
+        'magot_mask_piece': (ctypes.c_uint32, []),
+        'magot_mask_plan': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p),
+                                           _u64p, ctypes.c_uint32, ctypes.c_char_p,
+                                           ctypes.c_uint32, ctypes.POINTER(_vp), _u64p]),
+        'magot_maskplan_table': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _u64p,
+                                                ctypes.POINTER(ctypes.c_uint32)]),
+        'magot_maskplan_destroy': (None, [_vp]),
+        'magot_mask_fasta_check': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint32]),
+        'magot_mask_create': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp),
+                                             _u64p]),
+        'magot_mask_execute': (ctypes.c_int, [_vp, _vp]),
+        'magot_mask_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_mask_coverage_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _u64p]),
+        'magot_mask_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_double)]),
+        'magot_mask_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

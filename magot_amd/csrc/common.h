@@ -569,6 +569,31 @@ hipError_t launch_orfcall_compact(const OrfCallArgs& a, hipStream_t s);
 hipError_t launch_orftext_sizes(const OrfTextArgs& a, hipStream_t s);
 hipError_t launch_orftext_copy(const OrfTextArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// mask_from_gff (maskplan.cpp, maskgen.hip; magot_mask_*)
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaskPiece = 2048;  // most bases of one interval piece (maskplan.cpp)
+struct MaskArgs {
+  uint32_t flags;                  // MAGOT_MASK_*
+  const uint8_t* src;              // the whole-contig extraction's nucleotide output
+  uint64_t src_bytes;              // its size = bits of the coverage plane
+  const magot_mask_interval* rows; // n_rows interval pieces
+  uint64_t n_rows;
+  const uint64_t* contig_src;      // per contig: its first byte in src
+  uint32_t* cov;                   // cov_words + 1 words (the text pass reads word pairs)
+  uint64_t cov_words;
+  uint64_t n_rec;                  // contigs in output order
+  const uint64_t* tstart;          // n_rec + 1: each record's first text byte, and the total
+  const uint64_t* rsrc;            // n_rec: each record's first byte in src
+  const uint32_t* hlen;            // n_rec: header bytes ('>' name '\n')
+  const uint64_t* hoff;            // n_rec: the header's place in hdr
+  const uint8_t* hdr;
+  uint8_t* out;
+  uint64_t text_bytes;
+};
+hipError_t launch_mask_paint(const MaskArgs& a, hipStream_t s);
+hipError_t launch_mask_text(const MaskArgs& a, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);
@@ -580,7 +605,14 @@ void set_error(const std::string& msg);
 
 }  // namespace magot
 
-#define MAGOT_HIP_TRY(expr)                                                      \
+// magot_mask_plan's result (maskplan.cpp), read by magot_mask_create (abi.hip)
+struct magot_maskplan {
+  uint32_t flags = 0;
+  std::vector<uint64_t> contig_lens;
+  std::vector<magot_mask_interval> rows;  // pieces of at most kMaskPiece bases, in GFF order
+};
+
+#define MAGOT_HIP_TRY(expr)                                                     \
   do {                                                                           \
     hipError_t e_ = (expr);                                                      \
     if (e_ != hipSuccess) {                                                      \

@@ -989,6 +989,148 @@ class OrfCalls(object):
             pass
 
 
+MASK_INTERVAL_DTYPE = _lib.MASK_INTERVAL_DTYPE
+
+
+def mask_fasta_check(text, n_contigs):
+    """True when the ``n_contigs`` contigs the native reader found in the
+    FASTA ``text`` (truncate_names) are the entries mask_from_gff's own read
+    loop builds (magot_mask_fasta_check, genome_tools.py:398-409).  Host only."""
+    data = _text_view(text)
+    rc = _lib.lib().magot_mask_fasta_check(_text_ptr(data), len(data), int(n_contigs))
+    if rc == _lib.ERR_UNSUPPORTED:
+        return False
+    check(rc, 'magot_mask_fasta_check')
+    return True
+
+
+class MaskPlan(object):
+    """mask_from_gff's GFF pass as an interval table (magot_mask_plan,
+    genome_tools.py:410-426): ``intervals`` holds MASK_INTERVAL_DTYPE pieces
+    {contig, 0-based start, len} of at most ``piece`` bases, in GFF order,
+    clipped, unsorted and unmerged.  ``MaskPlan.build`` returns None where
+    only the reference's sequential replay is exact (the caller's line loop).
+    Host only."""
+
+    def __init__(self, handle, hard, keep_case):
+        self.handle = handle
+        self.hard, self.keep_case = hard, keep_case
+        rows, n = ctypes.c_void_p(), ctypes.c_uint64()
+        check(_lib.lib().magot_maskplan_table(handle, ctypes.byref(rows), ctypes.byref(n), None),
+              'magot_maskplan_table')
+        self.intervals = _view(rows.value, n.value, MASK_INTERVAL_DTYPE).copy()
+        self.piece = int(_lib.lib().magot_mask_piece())
+
+    @classmethod
+    def build(cls, gff, names, lengths, feature_type='CDS', hard=False, keep_case=False):
+        L = _lib.lib()
+        text = _text_view(gff)
+        n = len(names)
+        arr = (ctypes.c_char_p * max(n, 1))(*[_as_bytes(x) for x in names])
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+        flags = (_lib.MASK_HARD if hard else 0) | (_lib.MASK_KEEP_CASE if keep_case else 0)
+        h = ctypes.c_void_p()
+        rc = L.magot_mask_plan(_text_ptr(text), len(text), arr, lens.ctypes.data_as(_lib._u64p),
+                               n, _as_bytes(feature_type), flags, ctypes.byref(h), None)
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None
+        check(rc, 'magot_mask_plan')
+        return cls(h, bool(hard), bool(keep_case))
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_maskplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def whole_contig_plan(genome, contigs):
+    """An ExtractionPlan gathering the contigs ``contigs`` (indices) of a
+    device genome whole, one '+' single-interval nucleotide record each."""
+    idx = np.asarray(contigs, dtype=np.int64)
+    ex = np.zeros(len(idx), dtype=EXON_DTYPE)
+    ex['contig'] = idx
+    ex['len'] = np.asarray(genome.lengths, dtype=np.uint64)[idx]
+    tx = np.zeros(len(idx), dtype=TX_DTYPE)
+    tx['exon_begin'] = np.arange(len(idx))
+    tx['n_exons'] = 1
+    return ExtractionPlan(genome, ex, tx, OUT_NUC)
+
+
+class GenomeMask(object):
+    """mask_from_gff's text built on the device (magot_mask_*,
+    genome_tools.py:394-428): ``extraction`` gathers every contig whole, one
+    record per contig in output order (``whole_contig_plan``); record r is
+    contig ``rec_contig[r]`` and is printed under ``names[r]``.  ``execute``
+    enqueues the coverage paint and the text pass behind the extraction;
+    ``fetch`` gives the text, ``coverage()`` the coverage plane (one bit per
+    byte of the extraction's output; ``extraction.layout()`` places the
+    records in it)."""
+
+    def __init__(self, extraction, maskplan, rec_contig, names):
+        if len(names) != extraction.n_tx or len(rec_contig) != extraction.n_tx:
+            raise ValueError('one name and one contig per record')
+        self.ctx = extraction.ctx
+        self._keep = extraction
+        rc_arr = np.ascontiguousarray(np.asarray(rec_contig, dtype=np.uint32))
+        buf, off = _concat(names)
+        h = ctypes.c_void_p()
+        tb = ctypes.c_uint64()
+        check(_lib.lib().magot_mask_create(self.ctx.handle, extraction.handle, maskplan.handle,
+                                           ptr(rc_arr) if len(rc_arr) else None, ptr(off),
+                                           ptr(buf) if len(buf) else None, ctypes.byref(h),
+                                           ctypes.byref(tb)), 'magot_mask_create')
+        self.handle = h
+        self.text_bytes = tb.value
+
+    def execute(self):
+        check(_lib.lib().magot_mask_execute(self.ctx.handle, self.handle), 'magot_mask_execute')
+
+    def fetch(self):
+        """The text (a uint8 array): '>' name '\\n' sequence '\\n' per record."""
+        out = np.empty(max(self.text_bytes, 1), np.uint8)
+        check(_lib.lib().magot_mask_fetch(self.ctx.handle, self.handle, ptr(out),
+                                          self.text_bytes), 'magot_mask_fetch')
+        return out[:self.text_bytes]
+
+    def coverage(self):
+        """The coverage plane as uint32 words (bit i of word w: byte 32 w + i
+        of the extraction's nucleotide output)."""
+        n = ctypes.c_uint64()
+        L = _lib.lib()
+        check(L.magot_mask_coverage_fetch(self.ctx.handle, self.handle, None, 0, ctypes.byref(n)),
+              'magot_mask_coverage_fetch')
+        words = np.zeros(max(n.value, 1), np.uint32)
+        check(L.magot_mask_coverage_fetch(self.ctx.handle, self.handle, ptr(words), n.value,
+                                          ctypes.byref(n)), 'magot_mask_coverage_fetch')
+        return words[:n.value]
+
+    def time(self, iters):
+        """(paint_ms, text_ms): mean device time of the plane's zeroing +
+        paint kernel and of the text kernel (magot_mask_time)."""
+        pm, tm = ctypes.c_double(), ctypes.c_double()
+        check(_lib.lib().magot_mask_time(self.ctx.handle, self.handle, int(iters),
+                                         ctypes.byref(pm), ctypes.byref(tm)), 'magot_mask_time')
+        return pm.value, tm.value
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_mask_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's

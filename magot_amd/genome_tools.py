@@ -12,6 +12,8 @@
     python -m magot_amd.genome_tools get_seq_from_fasta <fasta> <seq_name> [truncate_names=False]
     python -m magot_amd.genome_tools dna2orfs <fasta> <out.fasta> [from_atg=1] [longest=1]
            [order=py2|insertion] [native=False]
+    python -m magot_amd.genome_tools mask_from_gff <fasta> <gff> [mask_type=soft|hard]
+           [overwrite_softmask=True] [feature_type=CDS] [order=py2|insertion] [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -571,14 +573,7 @@ def _dna2orfs_native(fasta_location, from_atg, longest, order):
         names = py2order.dict_order(dev.names) if order == 'py2' else list(dev.names)
         if not names:
             return b''
-        idx = np.array([dev.index[nm] for nm in names], dtype=np.int64)
-        ex = np.zeros(len(names), dtype=engine.EXON_DTYPE)
-        ex['contig'] = idx
-        ex['len'] = np.asarray(dev.lengths, dtype=np.uint64)[idx]
-        tx = np.zeros(len(names), dtype=engine.TX_DTYPE)
-        tx['exon_begin'] = np.arange(len(names))
-        tx['n_exons'] = 1
-        plan = engine.ExtractionPlan(dev, ex, tx, engine.OUT_NUC)
+        plan = engine.whole_contig_plan(dev, [dev.index[nm] for nm in names])
         o6 = engine.Orf6Plan(plan)
         o6.execute()
         calls = engine.OrfCalls(o6, from_atg=from_atg, longest=longest)
@@ -664,11 +659,148 @@ def _dna2orfs_contig(out, name, length, six, from_atg, longest):
         out.write(candidates[-1].encode('latin-1'))
 
 
+_MASK_OVERWRITE = ('True', 'T', 'true', 't', 'TRUE')
+_MASK_KEEP = ('False', 'F', 'false', 'f', 'FALSE')
+_PY_SPACE = b' \t\n\r\x0b\x0c'
+
+
+def _py2_int(field):
+    """int() of a byte string as Python 2 reads it: surrounding whitespace,
+    one optional sign, decimal digits (no '_' separators)."""
+    s = field.strip(_PY_SPACE)
+    digits = s[1:] if s[:1] in (b'+', b'-') else s
+    if not digits or not digits.isdigit():
+        raise ValueError('invalid literal for int() with base 10: %r' % field.decode('latin-1'))
+    return int(s)
+
+
+def _file_lines(path):
+    """``for line in open(path)`` of Python 2: lines end after '\\n' only."""
+    data = bytes(genome.read_buffer(path))
+    lines = data.split(b'\n')
+    return [ln + b'\n' for ln in lines[:-1]] + ([lines[-1]] if lines[-1] else [])
+
+
+def _mask_native(genome_sequence, gff, hard, keep_case, feature_type, order, clock):
+    """mask_from_gff's text (a uint8 array) from the device: the FASTA packed
+    natively, the GFF scanned by magot_mask_plan, every contig gathered whole
+    in output order, the coverage paint and the text pass; one D2H.  None
+    when only the reference's sequential loop is exact (engine.MaskPlan,
+    engine.mask_fasta_check) or the genome exceeds one device plane."""
+    from . import py2order
+    fa = genome.read_buffer(genome_sequence)
+    dev = engine.FastaGenome.load(fa, truncate_names=True)
+    clock.lap('fasta_read')
+    if dev is None:
+        return None
+    plan = ex = mask = None
+    try:
+        if (not dev.names or dev.total_bases > engine.PART_BASES or
+                not engine.mask_fasta_check(fa, len(dev.names))):
+            return None
+        plan = engine.MaskPlan.build(genome.read_buffer(gff), dev.names,
+                                     [int(x) for x in dev.lengths], feature_type=feature_type,
+                                     hard=hard, keep_case=keep_case)
+        clock.lap('gff_scan')
+        if plan is None:
+            return None
+        names = py2order.dict_order(dev.names) if order == 'py2' else list(dev.names)
+        idx = [dev.index[nm] for nm in names]
+        ex = engine.whole_contig_plan(dev, idx)
+        mask = engine.GenomeMask(ex, plan, idx, names)
+        clock.lap('plan_create')
+        ex.execute()
+        mask.execute()
+        ex.sync()
+        clock.lap('kernels')
+        out = mask.fetch()
+        clock.lap('text_d2h')
+        return out
+    finally:
+        for obj in (mask, ex, plan, dev):
+            if obj is not None:
+                obj.close()
+
+
+def mask_from_gff(genome_sequence, gff, mask_type='soft', overwrite_softmask='True',
+                  feature_type='CDS', order='py2', native='True'):
+    """genome_tools.py:394-428: the genome with every base under a
+    ``feature_type`` line of the GFF lower-cased (``mask_type='soft'``) or
+    replaced by 'N' ('hard'), after the whole genome was upper-cased
+    (``overwrite_softmask`` 'True') or as it is ('False'); one
+    '>name\\nsequence\\n' record per contig, the sequence on one line.  Names
+    are cut at the first whitespace; contigs come in the reference's Python 2
+    dict order unless ``order='insertion'``.
+
+    On the device (engine.GenomeMask: a coverage plane painted from the
+    interval table, one text pass) whenever the features only decide "covered
+    or not" per base.  Everything whose result depends on the reference
+    replaying the features one after another on Python lists -- a negative
+    slice index (start < 1), a hard mask reaching past its contig (the list
+    changes length and shifts every later feature), its exceptions (KeyError,
+    ValueError), its two invalid-argument messages, and FASTA files whose
+    contigs the native reader sees differently (empty or repeated contigs,
+    '> name' headers, sequence before the first header) -- takes the line loop
+    below, which restates the reference; ``native=False`` forces it."""
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'insertion' or 'py2'")
+    if (native == 'True' and mask_type in ('soft', 'hard') and
+            overwrite_softmask in _MASK_OVERWRITE + _MASK_KEEP and
+            isinstance(genome_sequence, str) and isinstance(gff, str)):
+        clock = _Clock()
+        text = _mask_native(genome_sequence, gff, mask_type == 'hard',
+                            overwrite_softmask in _MASK_KEEP, feature_type, order, clock)
+        if text is not None:
+            _write_bytes(text)
+            clock.lap('write')
+            clock.emit()
+            return
+    from . import py2order
+    genome_dict = {}
+    working_seqid = ''
+    for line in _file_lines(genome_sequence):
+        if line[:1] == b'>':
+            working_seqid = line.split()[0][1:].decode('latin-1')
+            genome_dict[working_seqid] = bytearray()
+        else:
+            seq = line.replace(b'\r', b'').replace(b'\n', b'')
+            if overwrite_softmask in _MASK_OVERWRITE:
+                genome_dict[working_seqid].extend(seq.upper())  # ASCII only, as Python 2's
+            elif overwrite_softmask in _MASK_KEEP:
+                genome_dict[working_seqid].extend(seq)
+            else:
+                _write("Invalid option for 'overwrite_softmask', argument accepts 'True' or "
+                       "'False'\n")
+                return
+    for line in _file_lines(gff):
+        if line.count(b'\t') > 5:
+            fields = line.split(b'\t')
+            if fields[2].decode('latin-1') == feature_type:
+                start = _py2_int(fields[3])
+                stop = _py2_int(fields[4])
+                if mask_type == 'soft':
+                    contig = genome_dict[fields[0].decode('latin-1')]
+                    contig[start - 1:stop] = contig[start - 1:stop].lower()
+                elif mask_type == 'hard':
+                    # a replacement of another length moves every later base
+                    contig = genome_dict[fields[0].decode('latin-1')]
+                    contig[start - 1:stop] = b'N' * max(0, 1 + stop - start)
+                else:
+                    _write("Invalid option for mask_type, argument accepts 'soft' and 'hard'\n")
+                    return
+    names = py2order.dict_order(list(genome_dict)) if order == 'py2' else list(genome_dict)
+    parts = []
+    for name in names:
+        parts += [b'>', name.encode('latin-1'), b'\n', bytes(genome_dict[name]), b'\n']
+    _write_bytes(*parts)
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep,
          'extract_upstream_downstream': extract_upstream_downstream,
          'coords2fasta': coords2fasta,
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,
-         'get_seq_from_fasta': get_seq_from_fasta, 'dna2orfs': dna2orfs}
+         'get_seq_from_fasta': get_seq_from_fasta, 'dna2orfs': dna2orfs,
+         'mask_from_gff': mask_from_gff}
 
 
 def parse_argv(argv):
