@@ -698,6 +698,76 @@ int magot_mask_coverage_fetch(magot_ctx* ctx, magot_mask* m, uint32_t* words, ui
 int magot_mask_time(magot_ctx* ctx, magot_mask* m, int iters, double* paint_ms, double* text_ms);
 void magot_mask_destroy(magot_mask* m);
 
+/*
+ * position_dic (genome.py:981-1100) on the device: a bit track over a packed
+ * genome, one bit per base in the genome's forward coordinates (bit g & 31 of
+ * word g >> 5; contig c's base i is coordinate 64 + the lengths of the contigs
+ * before c + i); every bit outside the contigs is 0.  All passes run on the
+ * context stream.  The genome must outlive the track, the track its windows.
+ *   magot_track_create      a zeroed track over g; *n_words = its words.
+ *   magot_track_base_class  the A/T class (genome.py:1029: byte in "ATat") or,
+ *       with MAGOT_TRACK_GC, the C/G class of g's bases, OR-ed into the track
+ *       or, with MAGOT_TRACK_REPLACE, replacing it.  g must be the genome the
+ *       track was created over (MAGOT_ERR_ARG).
+ *   magot_track_paint       sets (value 1) or clears (value 0) the bases under
+ *       interval pieces {contig, 0-based start, len <= the mask piece}; rows
+ *       may overlap, nest and repeat.  A row outside its contig is
+ *       MAGOT_ERR_RANGE, a longer one MAGOT_ERR_ARG, before any launch.
+ *   magot_track_set_bytes / _get_bytes   one contig's bits from / to one byte
+ *       per base (any non-zero byte sets the bit; 0 / 1 come back): a numpy
+ *       bool array.  len must be the contig's length.
+ *   magot_track_fetch       the words; *n_words alone when words == NULL.
+ *   magot_track_windows_create   sliding windows (genome.py:1043-1053): contig
+ *       c has (len - window) / jump windows when len > window and skip[c] is 0
+ *       (skip may be NULL), else none; window i covers bases [i * jump,
+ *       i * jump + window).  Enqueues the sums (one rank difference per
+ *       window; the rank directory is rebuilt first when a producer ran since).
+ *       *n_windows = their total, first[c] (n_contigs + 1 entries) contig c's
+ *       first window.  window and jump must be >= 1 (MAGOT_ERR_ARG).
+ *   magot_track_windows_fetch    the sums, in window order.
+ *   magot_track_transitions      the windows whose test sum >= s_min differs
+ *       from the previous window's of the same contig (false before a contig's
+ *       first window), counted and written on the device; *n = how many.
+ *   magot_track_transitions_fetch   their window indices, ascending
+ *       (MAGOT_ERR_STATE before magot_track_transitions).
+ *   magot_track_count       ones[i] = set bits under row i (any length).
+ *   magot_track_time        mean device ms over `iters` runs of: the A/T class
+ *       pass (into a scratch plane), the rank directory, the window sums, the
+ *       transitions (count, scan, write) and one whole-contig count per
+ *       contig, in ms5[0..4]; w may be NULL (entries 2 and 3 are then 0).
+ *   magot_track_rank_block  bases per rank directory block.
+ */
+#define MAGOT_TRACK_GC 1u
+#define MAGOT_TRACK_REPLACE 2u
+typedef struct magot_track magot_track;
+typedef struct magot_track_windows magot_track_windows;
+uint32_t magot_track_rank_block(void);
+int magot_track_create(magot_ctx* ctx, const magot_genome* g, magot_track** out,
+                       uint64_t* n_words);
+int magot_track_base_class(magot_ctx* ctx, magot_track* t, const magot_genome* g, uint32_t flags);
+int magot_track_paint(magot_ctx* ctx, magot_track* t, const magot_mask_interval* rows,
+                      uint64_t n_rows, int value);
+int magot_track_set_bytes(magot_ctx* ctx, magot_track* t, uint32_t contig, const uint8_t* bytes,
+                          uint64_t len);
+int magot_track_get_bytes(magot_ctx* ctx, magot_track* t, uint32_t contig, uint8_t* bytes,
+                          uint64_t len);
+int magot_track_fetch(magot_ctx* ctx, magot_track* t, uint32_t* words, uint64_t cap_words,
+                      uint64_t* n_words);
+int magot_track_windows_create(magot_ctx* ctx, magot_track* t, uint64_t window, uint64_t jump,
+                               const uint8_t* skip, magot_track_windows** out,
+                               uint64_t* n_windows, uint64_t* first);
+int magot_track_windows_fetch(magot_ctx* ctx, magot_track_windows* w, uint32_t* sums,
+                              uint64_t cap);
+int magot_track_transitions(magot_ctx* ctx, magot_track_windows* w, uint32_t s_min, uint64_t* n);
+int magot_track_transitions_fetch(magot_ctx* ctx, magot_track_windows* w, uint64_t* index,
+                                  uint64_t cap);
+int magot_track_count(magot_ctx* ctx, magot_track* t, const magot_mask_interval* rows,
+                      uint64_t n_rows, uint32_t* ones);
+int magot_track_time(magot_ctx* ctx, magot_track* t, magot_track_windows* w, uint32_t s_min,
+                     int iters, double* ms5);
+void magot_track_windows_destroy(magot_track_windows* w);
+void magot_track_destroy(magot_track* t);
+
 #ifdef __cplusplus
 }
 #endif

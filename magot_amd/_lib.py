@@ -54,6 +54,11 @@ EXPORTS = (
     'magot_mask_piece', 'magot_mask_plan', 'magot_maskplan_table', 'magot_maskplan_destroy',
     'magot_mask_fasta_check', 'magot_mask_create', 'magot_mask_execute', 'magot_mask_fetch',
     'magot_mask_coverage_fetch', 'magot_mask_time', 'magot_mask_destroy',
+    'magot_track_rank_block', 'magot_track_create', 'magot_track_base_class', 'magot_track_paint',
+    'magot_track_set_bytes', 'magot_track_get_bytes', 'magot_track_fetch',
+    'magot_track_windows_create', 'magot_track_windows_fetch', 'magot_track_transitions',
+    'magot_track_transitions_fetch', 'magot_track_count', 'magot_track_time',
+    'magot_track_windows_destroy', 'magot_track_destroy',
 )
 
 ERR_ARG = -1
@@ -73,6 +78,8 @@ ORF_REC_NONE = 1
 ORF_REC_NO_LONGEST = 2
 MASK_HARD = 1
 MASK_KEEP_CASE = 2
+TRACK_GC = 1
+TRACK_REPLACE = 2
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -229,6 +236,24 @@ def _declare(lib):
                                            ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(ctypes.c_double)]),
         'magot_mask_destroy': (None, [_vp]),
+        'magot_track_rank_block': (ctypes.c_uint32, []),
+        'magot_track_create': (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), _u64p]),
+        'magot_track_base_class': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32]),
+        'magot_track_paint': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int]),
+        'magot_track_set_bytes': (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp,
+                                                 ctypes.c_uint64]),
+        'magot_track_get_bytes': (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp,
+                                                 ctypes.c_uint64]),
+        'magot_track_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _u64p]),
+        'magot_track_windows_create': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                                      _vp, ctypes.POINTER(_vp), _u64p, _vp]),
+        'magot_track_windows_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_track_transitions': (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _u64p]),
+        'magot_track_transitions_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_track_count': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp]),
+        'magot_track_time': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp]),
+        'magot_track_windows_destroy': (None, [_vp]),
+        'magot_track_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -593,6 +593,62 @@ struct MaskArgs {
 };
 hipError_t launch_mask_paint(const MaskArgs& a, hipStream_t s);
 hipError_t launch_mask_text(const MaskArgs& a, hipStream_t s);
+// The paint kernel alone, into a plane of n_bits bits that is not zeroed first:
+// the pieces' bits are OR-ed into what it holds (track.hip's paint).
+hipError_t launch_mask_paint_rows(const magot_mask_interval* rows, uint64_t n_rows,
+                                  const uint64_t* contig_src, uint32_t* cov, uint64_t n_bits,
+                                  hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// position_dic's bit track (track.hip; magot_track_*)
+// ---------------------------------------------------------------------------
+// One bit per base over the genome's forward coordinates [0, span): bit g & 31
+// of word g >> 5; every bit outside [kOrigin, extent) is zero.  The plane is
+// allocated in whole rank blocks (track_plane_words).
+// Rank directory: ones per block of kRankWords words and their exclusive
+// prefix.  16 words = 512 bases = 64 bytes: a rank reads one directory entry
+// and at most four 16-byte loads that never leave one 64-byte half line, and
+// the directory (4 bytes per block) adds 1/16 to the plane.
+constexpr int kRankWords = 16;
+constexpr uint64_t track_blocks(uint64_t span) { return (span / 32 + kRankWords - 1) / kRankWords; }
+constexpr uint64_t track_plane_words(uint64_t span) { return (track_blocks(span) + 1) * kRankWords; }
+struct TrackWindowArgs {
+  const uint32_t* track;
+  const uint32_t* rank;         // track_blocks + 1 entries
+  const uint64_t* contig_base;  // n_contigs
+  const uint64_t* first;        // n_contigs + 1: each contig's first window, and the total
+  uint64_t n_contigs;
+  uint64_t n_windows;
+  uint64_t W, jump;
+  uint32_t* sums;               // n_windows
+  uint32_t* flip_count;         // track_flip_groups(n_windows) + 1
+  uint64_t* flip_slot;          // the same number: exclusive prefix, the last entry the total
+  uint64_t* flip_index;         // the windows where the threshold test flips
+};
+constexpr uint64_t track_flip_groups(uint64_t n_windows) { return (n_windows + 63) / 64; }
+size_t track_scan_bytes(uint64_t n);
+// the A/T (gc false) or C/G class of the forward nibble plane, n_words = span / 32
+// words, the bases outside [lo, hi) cleared; OR-ed into `track` or replacing it
+hipError_t launch_track_class(const uint32_t* nib, uint64_t n_words, uint64_t lo, uint64_t hi,
+                              bool gc, bool replace, uint32_t* track, hipStream_t s);
+hipError_t launch_track_andnot(uint32_t* track, const uint32_t* clear, uint64_t n_words,
+                               hipStream_t s);
+// coordinates [lo, hi) from / to a byte per base staged at stage[(lo & 31) + i]
+// (32 * words touched bytes, 16-byte aligned)
+hipError_t launch_track_bytes_set(const uint8_t* stage, uint64_t lo, uint64_t hi, uint32_t* track,
+                                  hipStream_t s);
+hipError_t launch_track_bytes_get(const uint32_t* track, uint64_t lo, uint64_t hi, uint8_t* stage,
+                                  hipStream_t s);
+hipError_t launch_track_rank(const uint32_t* track, uint64_t n_blocks, uint32_t* count,
+                             uint32_t* rank, void* scan_tmp, size_t scan_bytes, hipStream_t s);
+hipError_t launch_track_windows(const TrackWindowArgs& a, hipStream_t s);
+hipError_t launch_track_flip_count(const TrackWindowArgs& a, uint32_t s_min, void* scan_tmp,
+                                   size_t scan_bytes, hipStream_t s);
+hipError_t launch_track_flip_write(const TrackWindowArgs& a, uint32_t s_min, uint64_t cap,
+                                   hipStream_t s);
+hipError_t launch_track_count(const magot_mask_interval* rows, uint64_t n_rows,
+                              const uint64_t* contig_base, const uint32_t* track,
+                              const uint32_t* rank, uint64_t span, uint32_t* ones, hipStream_t s);
 
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.

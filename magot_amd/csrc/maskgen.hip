@@ -189,13 +189,19 @@ __global__ __launch_bounds__(kMaskThreads) void mask_text_kernel(MaskArgs a) {
 
 }  // namespace
 
+hipError_t launch_mask_paint_rows(const magot_mask_interval* rows, uint64_t n_rows,
+                                  const uint64_t* contig_src, uint32_t* cov, uint64_t n_bits,
+                                  hipStream_t s) {
+  if (!n_rows) return hipSuccess;
+  const uint64_t blocks = (n_rows + kMaskThreads - 1) / kMaskThreads;
+  mask_paint_kernel<<<(unsigned)blocks, kMaskThreads, 0, s>>>(rows, n_rows, contig_src, cov,
+                                                               n_bits);
+  return hipGetLastError();
+}
+
 hipError_t launch_mask_paint(const MaskArgs& a, hipStream_t s) {
   if (hipError_t e = hipMemsetAsync(a.cov, 0, (a.cov_words + 1) * 4, s)) return e;
-  if (!a.n_rows) return hipSuccess;
-  const uint64_t blocks = (a.n_rows + kMaskThreads - 1) / kMaskThreads;
-  mask_paint_kernel<<<(unsigned)blocks, kMaskThreads, 0, s>>>(a.rows, a.n_rows, a.contig_src,
-                                                               a.cov, a.src_bytes);
-  return hipGetLastError();
+  return launch_mask_paint_rows(a.rows, a.n_rows, a.contig_src, a.cov, a.src_bytes, s);
 }
 
 hipError_t launch_mask_text(const MaskArgs& a, hipStream_t s) {

@@ -1131,6 +1131,184 @@ class GenomeMask(object):
             pass
 
 
+def interval_pieces(contig, start, length, piece):
+    """Intervals {contig, 0-based start, length} (arrays) cut into
+    MASK_INTERVAL_DTYPE rows of at most ``piece`` bases; empty ones dropped."""
+    contig = np.asarray(contig, dtype=np.int64)
+    start = np.asarray(start, dtype=np.int64)
+    length = np.asarray(length, dtype=np.int64)
+    n = (length + piece - 1) // piece
+    which = np.repeat(np.arange(len(n)), n)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    rows = np.zeros(len(which), dtype=MASK_INTERVAL_DTYPE)
+    rows['contig'] = contig[which]
+    rows['start'] = start[which] + k * piece
+    rows['len'] = np.minimum(length[which] - k * piece, piece)
+    return rows
+
+
+def _interval_rows(contig, start, length):
+    rows = np.zeros(len(contig), dtype=MASK_INTERVAL_DTYPE)
+    rows['contig'], rows['start'], rows['len'] = contig, start, length
+    return rows
+
+
+class TrackWindows(object):
+    """The sliding-window sums of a GenomeTrack, resident on the device
+    (magot_track_windows_create): ``first[c]`` is contig c's first window of
+    ``n_windows``; ``sums()`` brings them all down, ``transitions(s_min)``
+    only the windows where ``sum >= s_min`` flips."""
+
+    def __init__(self, track, window, jump, skip=None):
+        self.ctx = track.ctx
+        self._keep = track
+        nc = len(track.genome.names)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(np.asarray(skip, dtype=bool).astype(np.uint8))
+            if len(sk) != nc:
+                raise ValueError('one skip flag per contig')
+        self.first = np.zeros(nc + 1, dtype=np.uint64)
+        h, n = ctypes.c_void_p(), ctypes.c_uint64()
+        check(_lib.lib().magot_track_windows_create(
+            self.ctx.handle, track.handle, int(window), int(jump),
+            ptr(sk) if sk is not None and nc else None, ctypes.byref(h), ctypes.byref(n),
+            ptr(self.first)), 'magot_track_windows_create')
+        self.handle = h
+        self.n_windows = n.value
+        self.window, self.jump = int(window), int(jump)
+
+    def sums(self):
+        out = np.empty(max(self.n_windows, 1), np.uint32)
+        check(_lib.lib().magot_track_windows_fetch(self.ctx.handle, self.handle, ptr(out),
+                                                   self.n_windows), 'magot_track_windows_fetch')
+        return out[:self.n_windows]
+
+    def transitions(self, s_min):
+        """Ascending window indices where ``sum >= s_min`` differs from the
+        previous window of the same contig (false before its first)."""
+        n = ctypes.c_uint64()
+        L = _lib.lib()
+        check(L.magot_track_transitions(self.ctx.handle, self.handle, int(s_min), ctypes.byref(n)),
+              'magot_track_transitions')
+        out = np.empty(max(n.value, 1), np.uint64)
+        check(L.magot_track_transitions_fetch(self.ctx.handle, self.handle, ptr(out), n.value),
+              'magot_track_transitions_fetch')
+        return out[:n.value]
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_track_windows_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GenomeTrack(object):
+    """position_dic's per-base track on the device (magot_track_*,
+    genome.py:981-1100): one bit per base of a DeviceGenome.  Producers:
+    ``base_class`` (A/T or C/G content), ``paint`` (intervals), ``set_bytes``
+    (a contig's bool array).  Consumers: ``get_bytes``, ``count``
+    (ones under intervals), ``windows`` (TrackWindows: sums and threshold
+    transitions).  genome -> base_class -> windows -> transitions never brings
+    anything per base to the host."""
+
+    def __init__(self, genome):
+        if not isinstance(genome, DeviceGenome):
+            raise MagotError('GenomeTrack needs a genome in one device plane')
+        self.ctx = genome.ctx
+        self.genome = genome
+        h, n = ctypes.c_void_p(), ctypes.c_uint64()
+        check(_lib.lib().magot_track_create(self.ctx.handle, genome.handle, ctypes.byref(h),
+                                            ctypes.byref(n)), 'magot_track_create')
+        self.handle = h
+        self.n_words = n.value
+        self.piece = int(_lib.lib().magot_mask_piece())
+
+    def base_class(self, gc=False, replace=False, genome=None):
+        """OR the A/T (``gc``: C/G) class of the genome's bases into the track,
+        or replace the track with it."""
+        g = self.genome if genome is None else genome
+        flags = (_lib.TRACK_GC if gc else 0) | (_lib.TRACK_REPLACE if replace else 0)
+        check(_lib.lib().magot_track_base_class(self.ctx.handle, self.handle, g.handle, flags),
+              'magot_track_base_class')
+
+    def paint(self, contig, start, length, value=1):
+        """Set (``value`` 1) or clear (0) the bases of every interval."""
+        rows = interval_pieces(contig, start, length, self.piece)
+        self.paint_rows(rows, value)
+
+    def paint_rows(self, rows, value=1):
+        rows = np.ascontiguousarray(rows, dtype=MASK_INTERVAL_DTYPE)
+        check(_lib.lib().magot_track_paint(self.ctx.handle, self.handle,
+                                           ptr(rows) if len(rows) else None, len(rows),
+                                           int(value)), 'magot_track_paint')
+
+    def set_bytes(self, contig, arr):
+        a = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+        check(_lib.lib().magot_track_set_bytes(self.ctx.handle, self.handle, int(contig),
+                                               ptr(a) if len(a) else None, len(a)),
+              'magot_track_set_bytes')
+
+    def get_bytes(self, contig, out=None):
+        """The contig's bits as a bool array (into ``out``, a contiguous bool
+        or uint8 array of the contig's length, when given)."""
+        n = int(self.genome.lengths[contig])
+        if out is None:
+            out = np.empty(n, dtype=bool)
+        a = out.view(np.uint8).reshape(-1)
+        check(_lib.lib().magot_track_get_bytes(self.ctx.handle, self.handle, int(contig),
+                                               ptr(a) if len(a) else None, len(a)),
+              'magot_track_get_bytes')
+        return out
+
+    def words(self):
+        out = np.zeros(max(self.n_words, 1), np.uint32)
+        check(_lib.lib().magot_track_fetch(self.ctx.handle, self.handle, ptr(out), self.n_words,
+                                           None), 'magot_track_fetch')
+        return out[:self.n_words]
+
+    def count(self, contig, start, length):
+        """Ones under each interval (any length), a uint32 array."""
+        return self.count_rows(_interval_rows(contig, start, length))
+
+    def count_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=MASK_INTERVAL_DTYPE)
+        out = np.zeros(max(len(rows), 1), np.uint32)
+        check(_lib.lib().magot_track_count(self.ctx.handle, self.handle,
+                                           ptr(rows) if len(rows) else None, len(rows), ptr(out)),
+              'magot_track_count')
+        return out[:len(rows)]
+
+    def windows(self, window, jump=1, skip=None):
+        return TrackWindows(self, window, jump, skip)
+
+    def time(self, iters, windows=None, s_min=1):
+        """Mean device ms per pass: {'class', 'rank', 'windows', 'transitions',
+        'count'} (magot_track_time)."""
+        ms = np.zeros(5, np.float64)
+        check(_lib.lib().magot_track_time(self.ctx.handle, self.handle,
+                                          windows.handle if windows is not None else None,
+                                          int(s_min), int(iters), ptr(ms)), 'magot_track_time')
+        return dict(zip(('class', 'rank', 'windows', 'transitions', 'count'), ms.tolist()))
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_track_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's
@@ -1207,4 +1385,5 @@ __all__ = ['DeviceGenome', 'ExtractionPlan', 'revcomp_batch', 'translate_batch',
            'OUT_NUC',
            'OUT_PEP', 'MagotError', 'GffPlan', 'orf6_batch', 'Orf6Plan', 'fasta_read',
            'FastaGenome', 'PartitionedGenome', 'device_genome', 'extract_records', 'plan_parts',
-           'copy_segments', 'orf6_sizes', 'OrfCalls', 'ORFCALL_TILE', 'ORF_TABLE_DTYPE']
+           'copy_segments', 'orf6_sizes', 'OrfCalls', 'ORFCALL_TILE', 'ORF_TABLE_DTYPE',
+           'GenomeTrack', 'TrackWindows', 'interval_pieces']

@@ -2,7 +2,8 @@
 
 Public names and signatures follow the reference (``genome.py``):
 ``Genome``, ``GenomeSequence``, ``AnnotationSet``, ``BaseAnnotation``,
-``ParentAnnotation``, ``Sequence``, ``read_gff``, ``ensure_file``.
+``ParentAnnotation``, ``Sequence``, ``read_gff``, ``ensure_file``,
+``position_dic`` (per-base tracks and sliding windows: ``engine.GenomeTrack``).
 
 How a call is executed
 ----------------------
@@ -23,6 +24,8 @@ reproduces the CPython 2.7 dict order the reference's own goldens use
 (``py2order``).
 """
 
+import copy
+import io
 import os
 import sys
 
@@ -1245,6 +1248,413 @@ class Genome(object):
             self.annotations.genome = self
 
 
+# ---------------------------------------------------------------------------
+# position_dic (genome.py:981-1100)
+# ---------------------------------------------------------------------------
+
+def _is_bool_track(arr):
+    return (isinstance(arr, np.ndarray) and arr.dtype == np.bool_ and arr.ndim == 1 and
+            arr.flags.c_contiguous and arr.flags.writeable)
+
+
+def _at_positions(seq):
+    """bool per character of ``seq``: in "ATat" (genome.py:1029)."""
+    if isinstance(seq, str):
+        try:
+            seq = seq.encode('latin-1')
+        except UnicodeEncodeError:
+            return np.array([ch in 'ATat' for ch in seq], dtype=bool)
+    if isinstance(seq, (bytes, bytearray)):
+        b = np.frombuffer(seq, dtype=np.uint8)
+        return (b == 65) | (b == 84) | (b == 97) | (b == 116)
+    return np.array([ch in 'ATat' for ch in seq], dtype=bool)
+
+
+def _min_passing_sum(window_size, operation, threshold):
+    """The smallest integer sum s in [0, window_size] whose value (s, or
+    s * 1.0 / window_size) is >= threshold, window_size + 1 when none is: the
+    value grows with s (a correctly rounded division by a positive constant is
+    monotone), so a bisection finds it."""
+    def passes(s):
+        return bool((s if operation == 'sum' else s * 1.0 / window_size) >= threshold)
+    lo, hi = 0, window_size + 1
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if passes(mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+def _regions_from_flips(flips, window_size, window_jump, contig_len):
+    """genome.py:1061-1085 replayed over the windows where the threshold test
+    changes (nothing happens at any other window): the coords lists of one
+    contig.  ``position > coords_list[-1][1]`` compares a window index with a
+    base coordinate, as the reference does."""
+    coords_list = []
+    window_in = False
+    for position in flips:
+        window_start = position * window_jump
+        if not window_in:
+            window_in = True
+            if len(coords_list) == 0:
+                coords_list.append([1 + window_start])
+            elif position > coords_list[-1][1]:
+                coords_list.append([1 + window_start])
+        else:
+            window_in = False
+            if len(coords_list[-1]) == 1:
+                coords_list[-1].append(window_start + window_size)
+            else:
+                coords_list[-1][1] = window_start + window_size
+    if len(coords_list) > 0 and len(coords_list[-1]) == 1:
+        coords_list[-1].append(contig_len)
+    return coords_list
+
+
+def _window_sums_host(arr, n, window_size, window_jump):
+    """numpy.sum(arr[i * jump:i * jump + window]) for i < n: one cumsum for
+    bool and integer arrays (exact), the slices themselves otherwise."""
+    if n <= 0:
+        return []
+    if arr.dtype.kind in 'biu' and window_size >= 1 and window_jump >= 1:
+        acc = np.uint64 if arr.dtype.kind == 'u' else np.int64
+        c = np.concatenate([np.zeros(1, acc), np.cumsum(arr, dtype=acc)])
+        starts = np.arange(n, dtype=np.int64) * window_jump
+        return (c[starts + window_size] - c[starts]).tolist()
+    return [np.sum(arr[i * window_jump:i * window_jump + window_size]) for i in range(n)]
+
+
+class position_dic(dict):
+    """genome.py:981-1100: seqid -> one numpy value per base.  The host arrays
+    are the truth (users index and change them directly); the per-base loops
+    of the reference run on the device (engine.GenomeTrack) for bool tracks,
+    through an upload of the arrays, and as numpy restatements otherwise or
+    with ``native=False``.  ``last_path`` names the path the last call took:
+    (method, 'native' or 'host', why the device path was declined or None)."""
+
+    def __init__(self, genome_sequence, dtype=bool):
+        dict.__init__(self)
+        for seqid in genome_sequence:
+            self[seqid] = np.zeros(len(genome_sequence[seqid]), dtype=dtype)
+        # the coordinate layout of the device track (contig order and lengths)
+        self._source = genome_sequence
+        self.last_path = None
+
+    # -- device layout -------------------------------------------------------
+    def _device_layout(self, genome_sequence=None):
+        """(device genome, None) when every array is a contiguous bool array
+        over a contig of the genome (``genome_sequence``, or the one this was
+        built from) of its length, in one device plane; else (None, why)."""
+        src = self.__dict__.get('_source') if genome_sequence is None else genome_sequence
+        if src is None or not hasattr(src, 'items'):
+            return None, 'no genome to lay the track over'
+        if len(self) == 0:
+            return None, 'no contigs'
+        for seqid in self:
+            if not _is_bool_track(self[seqid]):
+                return None, 'an array that is not a contiguous bool array'
+            try:
+                if seqid not in src or len(src[seqid]) != len(self[seqid]):
+                    return None, 'a contig the genome lacks, or of another length'
+            except TypeError:
+                return None, 'a contig the genome lacks, or of another length'
+        try:
+            dev = _device_genome_for(src)
+        except UnicodeEncodeError:
+            return None, 'a sequence outside latin-1'
+        if not isinstance(dev, engine.DeviceGenome):
+            return None, 'a genome in several device planes'
+        return dev, None
+
+    def _upload(self, dev):
+        track = engine.GenomeTrack(dev)
+        for seqid in self:
+            if self[seqid].any():
+                track.set_bytes(dev.index[seqid], self[seqid])
+        return track
+
+    # -- producers -----------------------------------------------------------
+    def fill_from_annotations(self, annotation_set, feature, fill_type="coords", fill_with="1",
+                              native=True):
+        """accepts "start" and "coords" for fill_type.  Host only: a numpy
+        slice assignment is already one pass over the bases."""
+        self.last_path = ('fill_from_annotations', 'host', 'slice assignment')
+        for annotation in eval("annotation_set." + feature):
+            annotation_obj = eval("annotation_set." + feature)[annotation]
+            seqid = annotation_obj.seqid
+            coords = annotation_obj.get_coords()
+            if fill_type == "coords":
+                first, stop = coords[0] - 1, coords[1]
+                if first >= stop:
+                    continue
+                arr = self[seqid]
+                if first >= 0 and stop <= len(arr):
+                    arr[first:stop] = eval(fill_with)
+                else:  # a negative index wraps, one past the end raises: as they come
+                    for position in range(first, stop):
+                        self[seqid][position] = eval(fill_with)
+            elif fill_type == "start":
+                self[seqid][coords[0] - 1] = eval(fill_with)
+
+    def at_content(self, genome_sequence, native=True):
+        why = 'native=False'
+        if native:
+            dev, why = self._device_layout(genome_sequence)
+            if dev is not None:
+                track = self._upload(dev)
+                try:
+                    track.base_class(gc=False, replace=False)
+                    for seqid in self:
+                        track.get_bytes(dev.index[seqid], out=self[seqid])
+                finally:
+                    track.close()
+                self.last_path = ('at_content', 'native', None)
+                return
+        self.last_path = ('at_content', 'host', why)
+        for seqid in self:
+            arr = self[seqid]
+            seq = genome_sequence[seqid]
+            n = min(len(arr), len(seq))
+            arr[:n][_at_positions(seq[:n])] = 1
+            if n < len(arr):
+                seq[n]  # the reference's IndexError, after the positions before it
+
+    # -- consumers -----------------------------------------------------------
+    def count_from_annotations(self, annotation_set, feature, native=True):
+        table = eval("annotation_set." + feature)
+        why = 'native=False'
+        if native:
+            spans = []
+            why = self._count_declined(table, spans)
+            if why is None:
+                dev, why = self._device_layout()
+            if why is None:
+                contig = [dev.index[table[a].seqid] for a in table]
+                start = [c[0] - 1 for c in spans]
+                length = [max(0, c[1] - c[0] + 1) for c in spans]
+                track = self._upload(dev)
+                try:
+                    ones = track.count(contig, start, length).tolist() if len(table) else []
+                finally:
+                    track.close()
+                self.last_path = ('count_from_annotations', 'native', None)
+                return [[table[a].ID, n - k, k] for a, n, k in zip(table, length, ones)]
+        self.last_path = ('count_from_annotations', 'host', why)
+        count_list = []
+        for annotation in table:
+            annotation_obj = table[annotation]
+            seqid = annotation_obj.seqid
+            coords = annotation_obj.get_coords()
+            first, stop = coords[0] - 1, coords[1]
+            count0 = count1 = 0
+            if first < stop:
+                arr = self[seqid]
+                if first >= 0 and stop <= len(arr):
+                    part = arr[first:stop]
+                    count0 = int(np.count_nonzero(part == 0))
+                    count1 = int(np.count_nonzero(part == 1))
+                else:
+                    for position in range(first, stop):
+                        if self[seqid][position] == 0:
+                            count0 = count0 + 1
+                        elif self[seqid][position] == 1:
+                            count1 = count1 + 1
+            count_list.append([annotation_obj.ID, count0, count1])
+        return count_list
+
+    def _count_declined(self, table, spans):
+        """Why the features cannot be counted on the device, or None with
+        their coords appended to ``spans``."""
+        for a in table:
+            obj = table[a]
+            try:
+                coords = obj.get_coords()
+                arr = self.get(obj.seqid)
+                if not (isinstance(coords[0], int) and isinstance(coords[1], int)):
+                    return 'coordinates that are not integers'
+            except Exception:  # the host loop raises it where the reference does
+                return 'a feature whose coordinates raise'
+            if arr is None:
+                return 'a feature on an unknown contig'
+            if coords[0] - 1 < coords[1] and (coords[0] < 1 or coords[1] > len(arr)):
+                return 'a feature outside its contig'
+            spans.append(coords)
+        return None
+
+    def sliding_window_calculate(self, window_size, window_jump=1, operation="sum", output="dict",
+                                 threshold=1, seqs_to_exclude=[], native=True):
+        """operation may be "sum", "average", or "set". Output may be "dict","coords", or
+        "annotation_set"."""
+        if not (operation in ('sum', 'average') and output in ('dict', 'annotation_set')):
+            self.last_path = ('sliding_window_calculate', 'host', 'operation or output')
+            return self._windows_reference(window_size, window_jump, operation, output,
+                                           threshold, seqs_to_exclude)
+        why = 'native=False'
+        windows = track = None
+        if native:
+            ints = all(isinstance(v, int) and not isinstance(v, bool)
+                       for v in (window_size, window_jump))
+            if not ints or window_size < 1 or window_jump < 1:
+                why = 'a window or jump that is not a positive integer'
+            elif output == 'annotation_set' and not isinstance(threshold, (int, float, np.number)):
+                why = 'a threshold that is not a number'
+            else:
+                dev, why = self._device_layout()
+        try:
+            if native and why is None:
+                track = self._upload(dev)
+                here = set(dev.index[s] for s in self if s not in seqs_to_exclude)
+                windows = track.windows(window_size, window_jump,
+                                        skip=[i not in here for i in range(len(dev.names))])
+                first = [int(x) for x in windows.first]
+                if output == 'dict':
+                    sums = windows.sums()
+                else:
+                    s_min = _min_passing_sum(window_size, operation, threshold)
+                    flips = windows.transitions(s_min)
+                    cut = np.searchsorted(flips, windows.first)
+            self.last_path = ('sliding_window_calculate', 'native' if why is None else 'host', why)
+            if output == "dict":
+                new_dic = {}
+            else:
+                annotation_set = AnnotationSet()
+                annotation_set.region = {}
+            for seqid in self:
+                if len(self[seqid]) > window_size and seqid not in seqs_to_exclude:
+                    contig_len = len(self[seqid])
+                    n = len(self[seqid][:-1 * window_size]) // window_jump
+                    if windows is not None:
+                        c = dev.index[seqid]
+                        if output == 'dict':
+                            part = sums[first[c]:first[c + 1]].astype(np.int64)
+                        else:
+                            seq_flips = (flips[cut[c]:cut[c + 1]].astype(np.int64)
+                                         - first[c]).tolist()
+                    else:
+                        part = np.asarray(_window_sums_host(self[seqid], n, window_size,
+                                                            window_jump))
+                        if output != 'dict':
+                            values = part if operation == 'sum' else part * 1.0 / window_size
+                            inside = np.asarray(values >= threshold, dtype=bool).reshape(-1)
+                            before = np.concatenate([np.zeros(1, bool), inside[:-1]])
+                            seq_flips = np.flatnonzero(inside != before).tolist()
+                    if output == "dict":
+                        if operation == 'average':
+                            part = part * 1.0 / window_size
+                        new_dic[seqid] = part.tolist()
+                    if verbose and n > 0:
+                        step = 10000000 // _gcd(window_jump, 10000000)
+                        for position in range(0, n, step):
+                            _emit("processed " + seqid + " to position " + str(position))
+                    if output == "annotation_set":
+                        for coords in _regions_from_flips(seq_flips, window_size, window_jump,
+                                                          contig_len):
+                            ID = seqid + "-window" + str(coords[0])
+                            annotation_set.region[ID] = BaseAnnotation(
+                                ID, seqid, tuple(coords), "region", annotation_set=annotation_set)
+                    if verbose:
+                        _emit("processed " + seqid)
+                        if output == 'annotation_set':
+                            for region in annotation_set.region:
+                                if annotation_set.region[region].seqid == seqid:
+                                    _emit(str(annotation_set.region[region].coords))
+        finally:
+            for obj in (windows, track):
+                if obj is not None:
+                    obj.close()
+        if output == "dict":
+            return new_dic
+        return copy.deepcopy(annotation_set)
+
+    def _windows_reference(self, window_size, window_jump, operation, output, threshold,
+                           seqs_to_exclude):
+        """genome.py:1032-1100 window by window, for operation "set", output
+        "coords" or a file, and whatever else the reference meets there (its
+        NameError on the misspelt ``thredshold`` included)."""
+        if output == "dict":
+            new_dic = {}
+        elif output == "annotation_set":
+            annotation_set = AnnotationSet()
+            annotation_set.region = {}
+        elif output == "coords":
+            coords_list = []
+        for seqid in self:
+            if len(self[seqid]) > window_size and seqid not in seqs_to_exclude:
+                if output == "dict":
+                    new_dic[seqid] = []
+                window_in = False
+                coords_list = []
+                for position in range(len(self[seqid][:-1 * window_size]) // window_jump):
+                    window_start = position * window_jump
+                    if operation == "set":
+                        if output != "dict":
+                            raise UnboundLocalError(
+                                "local variable 'new_dic' referenced before assignment")
+                        new_dic[seqid].append(
+                            set(self[seqid][window_start:window_start + window_size].tolist()))
+                        continue
+                    window_sum = np.sum(self[seqid][window_start:window_start + window_size])
+                    if operation == "sum":
+                        value = window_sum
+                    elif operation == "average":
+                        value = window_sum * 1.0 / window_size
+                    else:
+                        raise UnboundLocalError(
+                            "local variable 'value' referenced before assignment")
+                    if output == "dict":
+                        new_dic[seqid].append(value)
+                    elif output == 'annotation_set':
+                        if value >= threshold:
+                            if window_in is False:
+                                window_in = True
+                                if len(coords_list) == 0:
+                                    coords_list.append([1 + window_start])
+                                elif position > coords_list[-1][1]:
+                                    coords_list.append([1 + window_start])
+                        else:
+                            if window_in is True:
+                                window_in = False
+                                if len(coords_list[-1]) == 1:
+                                    coords_list[-1].append(window_start + window_size)
+                                else:
+                                    coords_list[-1][1] = window_start + window_size
+                    elif output == "coords":
+                        if threshold[0] <= value:
+                            raise NameError("global name 'thredshold' is not defined")
+                    elif isinstance(output, io.IOBase):
+                        output.write(seqid + '\t' + str(value) + '\n')
+                    if window_start % 10000000 == 0 and verbose:
+                        _emit("processed " + seqid + " to position " + str(position))
+                if output == "annotation_set":
+                    if len(coords_list) > 0:
+                        if len(coords_list[-1]) == 1:
+                            coords_list[-1].append(len(self[seqid]))
+                        for coords in coords_list:
+                            ID = seqid + "-window" + str(coords[0])
+                            annotation_set.region[ID] = BaseAnnotation(
+                                ID, seqid, tuple(coords), "region", annotation_set=annotation_set)
+                if verbose:
+                    _emit("processed " + seqid)
+                    if output == 'annotation_set':
+                        for region in annotation_set.region:
+                            if annotation_set.region[region].seqid == seqid:
+                                _emit(str(annotation_set.region[region].coords))
+        if output == "dict":
+            return new_dic
+        elif output == "annotation_set":
+            return copy.deepcopy(annotation_set)
+        elif output == "coords":
+            return coords_list
+
+
+def _gcd(a, b):
+    while b:
+        a, b = b, a % b
+    return a
+
+
 __all__ = ['Genome', 'GenomeSequence', 'AnnotationSet', 'BaseAnnotation', 'ParentAnnotation',
            'Sequence', 'read_gff', 'read_exonerate', 'read_blast_csv', 'read_cegma_gff',
-           'vulgar2gff', 'ensure_file', 'DEFAULT_ORDER']
+           'vulgar2gff', 'ensure_file', 'DEFAULT_ORDER', 'position_dic']

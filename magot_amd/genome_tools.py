@@ -14,6 +14,7 @@
            [order=py2|insertion] [native=False]
     python -m magot_amd.genome_tools mask_from_gff <fasta> <gff> [mask_type=soft|hard]
            [overwrite_softmask=True] [feature_type=CDS] [order=py2|insertion] [native=False]
+    python -m magot_amd.genome_tools at_content_from_fasta <fasta> [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -795,7 +796,86 @@ def mask_from_gff(genome_sequence, gff, mask_type='soft', overwrite_softmask='Tr
     _write_bytes(*parts)
 
 
-TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep,
+def _at_content_native(fasta, clock):
+    """at_content_from_fasta's text (bytes) from the device: the FASTA packed
+    natively under its whole header lines, the A/T and the C/G class of every
+    base as bit tracks, one count per contig of each.  None where the line
+    loop sees other records than the native reader: a file that does not
+    start with a header, a '>' inside a line or an empty record (the file's
+    '>' bytes are then not one per contig), a repeated name, or a genome above
+    one device plane."""
+    fa = genome.read_buffer(fasta)
+    if bytes(fa[:1]) != b'>':
+        return None
+    dev = engine.FastaGenome.load(fa, truncate_names=False)
+    clock.lap('fasta_read')
+    if dev is None:
+        return None
+    track = None
+    try:
+        n = len(dev.names)
+        if (n == 0 or dev.total_bases > engine.PART_BASES or len(set(dev.names)) != n or
+                int(np.count_nonzero(np.frombuffer(fa, dtype=np.uint8) == 62)) != n):
+            return None
+        clock.lap('header_check')
+        track = engine.GenomeTrack(dev)
+        whole = (np.arange(n), np.zeros(n, np.int64), [int(x) for x in dev.lengths])
+        track.base_class(gc=False, replace=True)
+        ats = track.count(*whole)
+        track.base_class(gc=True, replace=True)
+        gcs = track.count(*whole)
+        clock.lap('kernels')
+        return b''.join(b'%s\t%d\t%d\n' % (nm.encode('latin-1'), a, g)
+                        for nm, a, g in zip(dev.names, ats.tolist(), gcs.tolist()))
+    finally:
+        for obj in (track, dev):
+            if obj is not None:
+                obj.close()
+
+
+def at_content_from_fasta(fasta, native='True'):
+    """genome_tools.py:506-524: ``name \\t ATs \\t GCs`` per record, counted
+    without regard to case; the name is the header line without '>' and its
+    line end.  On the device (engine.GenomeTrack: the base-class pass and the
+    count pass) for a FASTA file whose records the native reader sees as the
+    reference's line loop does; otherwise, and with ``native=False``, the line
+    loop below, which restates the reference and raises what it raises (a
+    file that starts with sequence: UnboundLocalError)."""
+    if native == 'True' and isinstance(fasta, str) and os.path.isfile(fasta):
+        clock = _Clock()
+        text = _at_content_native(fasta, clock)
+        if text is not None:
+            _write_bytes(text)
+            clock.lap('write')
+            clock.emit()
+            return
+    firstline = True
+    out = []
+    with open(fasta, 'rb') as fh:
+        lines = fh.read().split(b'\n')
+    lines = [ln + b'\n' for ln in lines[:-1]] + ([lines[-1]] if lines[-1] else [])
+    try:
+        for line in lines:
+            if line == b'\n':
+                continue
+            elif b'>' in line:
+                if firstline:
+                    firstline = False
+                else:
+                    out.append(name + b'%d\t%d\n' % (ats, gcs))
+                name = line[1:].replace(b'\n', b'').replace(b'\r', b'') + b'\t'
+                ats = 0
+                gcs = 0
+            else:
+                up = line.upper()  # ASCII only, as Python 2's
+                ats = ats + up.count(b'A') + up.count(b'T')
+                gcs = gcs + up.count(b'G') + up.count(b'C')
+        out.append(name + b'%d\t%d\n' % (ats, gcs))
+    finally:
+        _write_bytes(*out)  # what was printed before an exception stays printed
+
+
+TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
          'extract_upstream_downstream': extract_upstream_downstream,
          'coords2fasta': coords2fasta,
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,
