@@ -768,6 +768,64 @@ int magot_track_time(magot_ctx* ctx, magot_track* t, magot_track_windows* w, uin
 void magot_track_windows_destroy(magot_track_windows* w);
 void magot_track_destroy(magot_track* t);
 
+/*
+ * depth_from_gff (genome_tools.py:598-652) on the device: the depth column of
+ * a `samtools depth` table as one int32 per line, and interval sums over it.
+ *
+ * Grammar of a line: name SEP pos SEP depth (SEP token)* [SEP] [CR] LF; SEP
+ * one or more of space and tab; name 1..255 bytes of 0x21..0x7E; pos and depth
+ * 1..10 digits, value <= 2^31 - 1; the last line may lack its LF.  A line
+ * whose name differs from the line before starts a run; line k (from 0) of a
+ * run must have pos k + 1; no two runs carry one name.  For such a table the
+ * reference's array of a contig is the depth column of its run.
+ *   magot_depth_parse   streams the text in chunks of about chunk_bytes (0: a
+ *       default sized for transfer; cut after an LF) through pinned staging,
+ *       each upload overlapped with the parse of the chunk before, and builds
+ *       the sum directory.  A table outside the grammar is declined: *out =
+ *       NULL, *reason a MAGOT_DEPTH_* code and *line the first offending line
+ *       (1-based; 0 for the two whole-table limits).  Otherwise *reason = 0,
+ *       *n_lines and *n_runs describe the track.  max_runs 0: 2^20.
+ *   magot_depth_runs    the runs in file order: first line (0-based), offset
+ *       of the name in the text, name length.
+ *   magot_depth_values  lines [start, start + n) of the depth column.
+ *   magot_depth_sums    sums[i] = the sum of lines [start[i], start[i] +
+ *       length[i]) (0 when length[i] <= 0; otherwise a row outside the table
+ *       is MAGOT_ERR_RANGE, before any launch); with group_offsets (n_groups +
+ *       1 ascending entries, a CSR over the rows) also group_sums[g] = the sum
+ *       of its rows' sums.  group_offsets and group_sums may be NULL.
+ *   magot_depth_time    mean device ms over `iters` runs of: the line index
+ *       and the parse of the last chunk (still on the device; *chunk_len its
+ *       bytes), the directory, and one whole-run sum per run, in ms4[0..3].
+ *   magot_depth_block   depths per directory block.
+ */
+#define MAGOT_DEPTH_EMPTY_LINE 1u
+#define MAGOT_DEPTH_LEADING_BLANK 2u
+#define MAGOT_DEPTH_BAD_BYTE 3u
+#define MAGOT_DEPTH_NAME_LONG 4u
+#define MAGOT_DEPTH_FEW_FIELDS 5u
+#define MAGOT_DEPTH_SIGN 6u
+#define MAGOT_DEPTH_NOT_NUMBER 7u
+#define MAGOT_DEPTH_NUMBER_RANGE 8u
+#define MAGOT_DEPTH_POS_SEQUENCE 9u
+#define MAGOT_DEPTH_REPEATED_CONTIG 10u
+#define MAGOT_DEPTH_LINE_LONG 11u /* a line longer than a chunk */
+#define MAGOT_DEPTH_TOO_MANY_LINES 12u
+#define MAGOT_DEPTH_TOO_MANY_RUNS 13u
+typedef struct magot_depth magot_depth;
+uint32_t magot_depth_block(void);
+int magot_depth_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t chunk_bytes,
+                      uint32_t max_runs, magot_depth** out, uint64_t* n_lines, uint64_t* n_runs,
+                      uint32_t* reason, uint64_t* line);
+int magot_depth_runs(const magot_depth* t, uint64_t* first, uint64_t* offset, uint32_t* name_len,
+                     uint64_t cap);
+int magot_depth_values(magot_ctx* ctx, magot_depth* t, uint64_t start, uint64_t n, int32_t* out);
+int magot_depth_sums(magot_ctx* ctx, magot_depth* t, const int64_t* start, const int64_t* length,
+                     uint64_t n_rows, const uint64_t* group_offsets, uint64_t n_groups,
+                     int64_t* sums, int64_t* group_sums);
+int magot_depth_time(magot_ctx* ctx, magot_depth* t, int iters, double* ms4,
+                     uint64_t* chunk_len);
+void magot_depth_destroy(magot_depth* t);
+
 #ifdef __cplusplus
 }
 #endif

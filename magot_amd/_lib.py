@@ -59,6 +59,8 @@ EXPORTS = (
     'magot_track_windows_create', 'magot_track_windows_fetch', 'magot_track_transitions',
     'magot_track_transitions_fetch', 'magot_track_count', 'magot_track_time',
     'magot_track_windows_destroy', 'magot_track_destroy',
+    'magot_depth_block', 'magot_depth_parse', 'magot_depth_runs', 'magot_depth_values',
+    'magot_depth_sums', 'magot_depth_time', 'magot_depth_destroy',
 )
 
 ERR_ARG = -1
@@ -80,6 +82,12 @@ MASK_HARD = 1
 MASK_KEEP_CASE = 2
 TRACK_GC = 1
 TRACK_REPLACE = 2
+# magot_depth_parse's reasons (MAGOT_DEPTH_*), by code
+DEPTH_REASONS = (None, 'empty line', 'leading blank', 'byte outside the grammar',
+                 'name longer than 255 bytes', 'fewer than three fields', 'sign on a number',
+                 'not a number', 'number out of range', 'position out of sequence',
+                 'repeated contig', 'line longer than a chunk', 'more than 2^31-1 lines',
+                 'too many runs')
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -254,6 +262,16 @@ def _declare(lib):
         'magot_track_time': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp]),
         'magot_track_windows_destroy': (None, [_vp]),
         'magot_track_destroy': (None, [_vp]),
+        'magot_depth_block': (ctypes.c_uint32, []),
+        'magot_depth_parse': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.c_uint32, ctypes.POINTER(_vp), _u64p, _u64p,
+                                             ctypes.POINTER(ctypes.c_uint32), _u64p]),
+        'magot_depth_runs': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_depth_values': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+        'magot_depth_sums': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp,
+                                            ctypes.c_uint64, _vp, _vp]),
+        'magot_depth_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p]),
+        'magot_depth_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -8,6 +8,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <unordered_set>
 
 #include "common.h"
 
@@ -3120,6 +3121,399 @@ int magot_track_time(magot_ctx* ctx, magot_track* t, magot_track_windows* w, uin
       total[k] += ms;
     }
   for (int k = 0; k < 5; ++k) ms5[k] = total[k] / iters;
+  return MAGOT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// depth_from_gff's integer track (depth.hip; genome_tools.py:598-652)
+// ---------------------------------------------------------------------------
+
+struct magot_depth {
+  magot_ctx* ctx = nullptr;
+  void* arena_mem = nullptr;  // everything but the text buffers
+  int32_t* arena = nullptr;
+  uint64_t arena_cap = 0, n_lines = 0;
+  int64_t* block_sum = nullptr;
+  int64_t* dir = nullptr;
+  uint32_t* blk_count = nullptr;
+  uint32_t* blk_first = nullptr;
+  void* scan_tmp = nullptr;
+  size_t scan_bytes = 0;
+  DepthCarry* carry = nullptr;          // two that alternate, and a scratch one for the timed pass
+  unsigned long long* status = nullptr;  // [1]: scratch
+  uint32_t* n_heads = nullptr;           // [1]: scratch
+  DepthHead* heads = nullptr;
+  uint32_t heads_cap = 0;
+  // text staging: chunk k goes through slot k & 1
+  uint8_t* dev[2] = {nullptr, nullptr};
+  uint8_t* pin[2] = {nullptr, nullptr};
+  hipEvent_t up_done[2] = {nullptr, nullptr}, parse_done[2] = {nullptr, nullptr};
+  hipStream_t copy = nullptr;
+  // the last chunk, still in dev[last_slot] (magot_depth_time)
+  int last_slot = 0, last_in = 0;
+  uint64_t last_len = 0, last_off = 0;
+  std::vector<DepthHead> runs;  // in file order
+};
+
+namespace {
+
+constexpr uint64_t kDepthChunkDefault = 64ull << 20;
+constexpr uint64_t kDepthChunkMin = 1024, kDepthChunkMax = 1ull << 30;
+constexpr uint64_t kDepthMaxLines = 0x7fffffffull;
+
+void depth_free_staging(magot_depth* t, bool text_too) {
+  for (int s = 0; s < 2; ++s) {
+    if (t->pin[s]) (void)hipHostFree(t->pin[s]);
+    t->pin[s] = nullptr;
+    if (text_too && t->dev[s]) {
+      (void)hipFree(t->dev[s]);
+      t->dev[s] = nullptr;
+    }
+  }
+}
+
+int depth_handle(magot_ctx* ctx, const magot_depth* t, const char* who) {
+  if (int rc = bind(ctx)) return rc;
+  if (!t || t->ctx != ctx) {
+    set_error(std::string(who) + ": null track, or a track of another context");
+    return MAGOT_ERR_ARG;
+  }
+  return MAGOT_OK;
+}
+
+DepthParseArgs depth_args(const magot_depth* t, int slot, uint64_t n, uint64_t off, int in,
+                          int out, bool scratch) {
+  DepthParseArgs a{};
+  a.text = t->dev[slot];
+  a.n = (int64_t)n;
+  a.file_off = off;
+  a.blk_first = t->blk_first;
+  a.in = t->carry + in;
+  a.out = t->carry + out;
+  a.arena = t->arena;
+  a.arena_cap = t->arena_cap;
+  a.heads = t->heads;
+  a.n_heads = t->n_heads + (scratch ? 1 : 0);
+  a.heads_cap = scratch ? 0u : t->heads_cap;
+  a.status = t->status + (scratch ? 1 : 0);
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+void magot_depth_destroy(magot_depth* t) {
+  if (!t) return;
+  if (t->ctx) (void)hipSetDevice(t->ctx->device);
+  depth_free_staging(t, true);
+  for (int s = 0; s < 2; ++s) {
+    if (t->up_done[s]) (void)hipEventDestroy(t->up_done[s]);
+    if (t->parse_done[s]) (void)hipEventDestroy(t->parse_done[s]);
+  }
+  if (t->copy) (void)hipStreamDestroy(t->copy);
+  if (t->arena_mem) (void)hipFree(t->arena_mem);
+  delete t;
+}
+
+uint32_t magot_depth_block(void) { return (uint32_t)kDepthBlock; }
+
+int magot_depth_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t chunk_bytes,
+                      uint32_t max_runs, magot_depth** out, uint64_t* n_lines, uint64_t* n_runs,
+                      uint32_t* reason, uint64_t* line) {
+  if (int rc = bind(ctx)) return rc;
+  if (!out || !reason || !line || (len && !text)) {
+    set_error("magot_depth_parse: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  *out = nullptr;
+  *reason = 0;
+  *line = 0;
+  if (n_lines) *n_lines = 0;
+  if (n_runs) *n_runs = 0;
+  struct Guard {
+    magot_depth* t;
+    ~Guard() { magot_depth_destroy(t); }
+  } guard{new magot_depth()};
+  magot_depth* t = guard.t;
+  t->ctx = ctx;
+  uint64_t chunk = chunk_bytes ? chunk_bytes : kDepthChunkDefault;
+  chunk = std::min(std::max(chunk, kDepthChunkMin), kDepthChunkMax);
+  chunk = std::min(chunk, std::max<uint64_t>(len, 1));
+  const int n_slots = len > chunk ? 2 : 1;
+  // a line of the grammar has at least 6 bytes ("a 1 0" and its LF)
+  t->arena_cap = (depth_blocks(len / 6 + 2) + 1) * kDepthBlock;
+  t->heads_cap = max_runs ? max_runs : (1u << 20);
+  const uint64_t text_blocks = depth_text_blocks(chunk);
+  t->scan_bytes = depth_scan_bytes(std::max(text_blocks, depth_blocks(t->arena_cap)) + 1);
+  Carve cv;
+  const uint64_t o_arena = cv.take<int32_t>(t->arena_cap);
+  const uint64_t o_sum = cv.take<int64_t>(depth_blocks(t->arena_cap) + 1);
+  const uint64_t o_dir = cv.take<int64_t>(depth_blocks(t->arena_cap) + 1);
+  const uint64_t o_count = cv.take<uint32_t>(text_blocks + 1);
+  const uint64_t o_first = cv.take<uint32_t>(text_blocks + 1);
+  const uint64_t o_tmp = cv.take<uint8_t>(t->scan_bytes);
+  const uint64_t o_heads = cv.take<DepthHead>(t->heads_cap);
+  const uint64_t o_small = cv.take<uint8_t>(3 * sizeof(DepthCarry) + 64);
+  MAGOT_HIP_TRY(hipMalloc(&t->arena_mem, cv.used + 256));
+  char* base = static_cast<char*>(t->arena_mem);
+  t->arena = reinterpret_cast<int32_t*>(base + o_arena);
+  t->block_sum = reinterpret_cast<int64_t*>(base + o_sum);
+  t->dir = reinterpret_cast<int64_t*>(base + o_dir);
+  t->blk_count = reinterpret_cast<uint32_t*>(base + o_count);
+  t->blk_first = reinterpret_cast<uint32_t*>(base + o_first);
+  t->scan_tmp = base + o_tmp;
+  t->heads = reinterpret_cast<DepthHead*>(base + o_heads);
+  t->carry = reinterpret_cast<DepthCarry*>(base + o_small);
+  t->status = reinterpret_cast<unsigned long long*>(base + o_small + 3 * sizeof(DepthCarry));
+  t->n_heads = reinterpret_cast<uint32_t*>(t->status + 2);
+  // the carries and the head counters zero, the status words all ones
+  MAGOT_HIP_TRY(hipMemsetAsync(t->carry, 0, 3 * sizeof(DepthCarry) + 64, ctx->stream));
+  MAGOT_HIP_TRY(hipMemsetAsync(t->status, 0xff, 16, ctx->stream));
+  MAGOT_HIP_TRY(hipStreamCreateWithFlags(&t->copy, hipStreamNonBlocking));
+  for (int s = 0; s < n_slots; ++s) {
+    MAGOT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->dev[s]), chunk + 256));
+    MAGOT_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->pin[s]), chunk, hipHostMallocDefault));
+    MAGOT_HIP_TRY(hipEventCreateWithFlags(&t->up_done[s], hipEventDisableTiming));
+    MAGOT_HIP_TRY(hipEventCreateWithFlags(&t->parse_done[s], hipEventDisableTiming));
+  }
+  // the zeroing above is on the context stream; the first upload is not
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+
+  uint64_t off = 0, k = 0;
+  bool line_long = false;
+  while (off < len) {
+    uint64_t end = std::min(off + chunk, len);
+    if (end < len) {  // cut after the window's last LF
+      const void* lf = memrchr(text + off, '\n', end - off);
+      if (!lf) {
+        line_long = true;
+        break;
+      }
+      end = (uint64_t)(static_cast<const char*>(lf) - text) + 1;
+    }
+    const int s = (int)(k & 1);
+    const uint64_t n = end - off;
+    if (k >= 2) MAGOT_HIP_TRY(hipEventSynchronize(t->up_done[s]));  // pin[s] was read
+    std::memcpy(t->pin[s], text + off, n);
+    if (k >= 2) MAGOT_HIP_TRY(hipStreamWaitEvent(t->copy, t->parse_done[s], 0));
+    MAGOT_HIP_TRY(hipMemcpyAsync(t->dev[s], t->pin[s], n, hipMemcpyHostToDevice, t->copy));
+    MAGOT_HIP_TRY(hipEventRecord(t->up_done[s], t->copy));
+    MAGOT_HIP_TRY(hipStreamWaitEvent(ctx->stream, t->up_done[s], 0));
+    MAGOT_HIP_TRY(launch_depth_line_index(t->dev[s], n, t->blk_count, t->blk_first, t->scan_tmp,
+                                          t->scan_bytes, ctx->stream));
+    MAGOT_HIP_TRY(launch_depth_parse(depth_args(t, s, n, off, (int)(k & 1), (int)((k + 1) & 1),
+                                                false), ctx->stream));
+    MAGOT_HIP_TRY(hipEventRecord(t->parse_done[s], ctx->stream));
+    t->last_slot = s;
+    t->last_in = (int)(k & 1);
+    t->last_len = n;
+    t->last_off = off;
+    off = end;
+    ++k;
+  }
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  MAGOT_HIP_TRY(hipStreamSynchronize(t->copy));
+  depth_free_staging(t, false);
+
+  unsigned long long status = 0;
+  uint32_t heads = 0;
+  DepthCarry last;
+  MAGOT_HIP_TRY(hipMemcpy(&status, t->status, 8, hipMemcpyDeviceToHost));
+  MAGOT_HIP_TRY(hipMemcpy(&heads, t->n_heads, 4, hipMemcpyDeviceToHost));
+  MAGOT_HIP_TRY(hipMemcpy(&last, t->carry + (k & 1), sizeof(last), hipMemcpyDeviceToHost));
+  // the first offending line, whichever check finds it
+  uint64_t bad_line = ~0ull;
+  uint32_t bad = 0;
+  if (status != ~0ull) {
+    bad_line = (uint64_t)(status >> 8);
+    bad = (uint32_t)(status & 0xff);
+  }
+  if (line_long && last.lines < bad_line) {
+    bad_line = last.lines;
+    bad = MAGOT_DEPTH_LINE_LONG;
+  }
+  if (heads <= t->heads_cap) {
+    t->runs.resize(heads);
+    if (heads)
+      MAGOT_HIP_TRY(hipMemcpy(t->runs.data(), t->heads, heads * sizeof(DepthHead),
+                              hipMemcpyDeviceToHost));
+    std::sort(t->runs.begin(), t->runs.end(),
+              [](const DepthHead& a, const DepthHead& b) { return a.line < b.line; });
+    std::unordered_set<std::string> seen;
+    for (const DepthHead& h : t->runs) {
+      if (h.line >= bad_line) break;
+      if (h.offset + h.name_len > len) {
+        set_error("magot_depth_parse: a run head outside the text");
+        return MAGOT_ERR_STATE;
+      }
+      if (!seen.emplace(text + h.offset, h.name_len).second) {
+        bad_line = h.line;
+        bad = MAGOT_DEPTH_REPEATED_CONTIG;
+        break;
+      }
+    }
+  }
+  if (bad) {
+    *reason = bad;
+    *line = bad_line + 1;
+    return MAGOT_OK;
+  }
+  if (last.lines > kDepthMaxLines || heads > t->heads_cap) {
+    *reason = last.lines > kDepthMaxLines ? MAGOT_DEPTH_TOO_MANY_LINES : MAGOT_DEPTH_TOO_MANY_RUNS;
+    return MAGOT_OK;
+  }
+  t->n_lines = last.lines;
+  if (t->n_lines > t->arena_cap) {
+    set_error("magot_depth_parse: more lines than the arena holds");
+    return MAGOT_ERR_STATE;
+  }
+  MAGOT_HIP_TRY(launch_depth_directory(t->arena, t->n_lines, t->block_sum, t->dir, t->scan_tmp,
+                                       t->scan_bytes, ctx->stream));
+  if (n_lines) *n_lines = t->n_lines;
+  if (n_runs) *n_runs = t->runs.size();
+  guard.t = nullptr;
+  *out = t;
+  return MAGOT_OK;
+}
+
+int magot_depth_runs(const magot_depth* t, uint64_t* first, uint64_t* offset, uint32_t* name_len,
+                     uint64_t cap) {
+  if (!t || cap < t->runs.size() || (t->runs.size() && (!first || !offset || !name_len))) {
+    set_error("magot_depth_runs: null argument, or output buffers too small");
+    return MAGOT_ERR_ARG;
+  }
+  for (size_t i = 0; i < t->runs.size(); ++i) {
+    first[i] = t->runs[i].line;
+    offset[i] = t->runs[i].offset;
+    name_len[i] = t->runs[i].name_len;
+  }
+  return MAGOT_OK;
+}
+
+int magot_depth_values(magot_ctx* ctx, magot_depth* t, uint64_t start, uint64_t n, int32_t* out) {
+  if (int rc = depth_handle(ctx, t, "magot_depth_values")) return rc;
+  if (start > t->n_lines || n > t->n_lines - start || (n && !out)) {
+    set_error("magot_depth_values: lines outside the table, or null output");
+    return MAGOT_ERR_RANGE;
+  }
+  if (!n) return MAGOT_OK;
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  MAGOT_HIP_TRY(hipMemcpy(out, t->arena + start, n * 4, hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+int magot_depth_sums(magot_ctx* ctx, magot_depth* t, const int64_t* start, const int64_t* length,
+                     uint64_t n_rows, const uint64_t* group_offsets, uint64_t n_groups,
+                     int64_t* sums, int64_t* group_sums) {
+  if (int rc = depth_handle(ctx, t, "magot_depth_sums")) return rc;
+  if (n_rows && (!start || !length)) {
+    set_error("magot_depth_sums: null row table");
+    return MAGOT_ERR_ARG;
+  }
+  if (!group_offsets) n_groups = 0;
+  if (n_groups && !group_sums) {
+    set_error("magot_depth_sums: null group output");
+    return MAGOT_ERR_ARG;
+  }
+  for (uint64_t i = 0; i < n_rows; ++i)
+    if (length[i] > 0 && (start[i] < 0 || (uint64_t)start[i] > t->n_lines ||
+                          (uint64_t)length[i] > t->n_lines - (uint64_t)start[i])) {
+      set_error("magot_depth_sums: row " + std::to_string(i) + " is outside the table");
+      return MAGOT_ERR_RANGE;
+    }
+  for (uint64_t g = 0; g < n_groups; ++g)
+    if (group_offsets[g] > group_offsets[g + 1] || group_offsets[g + 1] > n_rows) {
+      set_error("magot_depth_sums: group " + std::to_string(g) + " is not a range of rows");
+      return MAGOT_ERR_ARG;
+    }
+  if (!n_rows && !n_groups) return MAGOT_OK;
+  Carve cv;
+  const uint64_t o_start = cv.take<int64_t>(n_rows);
+  const uint64_t o_len = cv.take<int64_t>(n_rows);
+  const uint64_t o_sums = cv.take<int64_t>(n_rows);
+  const uint64_t o_off = cv.take<uint64_t>(n_groups + 1);
+  const uint64_t o_group = cv.take<int64_t>(n_groups);
+  DevBuf d;
+  MAGOT_HIP_TRY(hipMalloc(&d.p, cv.used + 256));
+  char* base = static_cast<char*>(d.p);
+  int64_t* d_sums = reinterpret_cast<int64_t*>(base + o_sums);
+  if (n_rows) {
+    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_start, start, n_rows * 8, hipMemcpyHostToDevice,
+                                 ctx->stream));
+    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_len, length, n_rows * 8, hipMemcpyHostToDevice,
+                                 ctx->stream));
+  }
+  if (n_groups)
+    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_off, group_offsets, (n_groups + 1) * 8,
+                                 hipMemcpyHostToDevice, ctx->stream));
+  MAGOT_HIP_TRY(launch_depth_sums(t->arena, t->dir, t->n_lines,
+                                  reinterpret_cast<const int64_t*>(base + o_start),
+                                  reinterpret_cast<const int64_t*>(base + o_len), n_rows, d_sums,
+                                  ctx->stream));
+  MAGOT_HIP_TRY(launch_depth_groups(d_sums, reinterpret_cast<const uint64_t*>(base + o_off),
+                                    n_groups, reinterpret_cast<int64_t*>(base + o_group),
+                                    ctx->stream));
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (n_rows && sums) MAGOT_HIP_TRY(hipMemcpy(sums, d_sums, n_rows * 8, hipMemcpyDeviceToHost));
+  if (n_groups)
+    MAGOT_HIP_TRY(hipMemcpy(group_sums, base + o_group, n_groups * 8, hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+int magot_depth_time(magot_ctx* ctx, magot_depth* t, int iters, double* ms4,
+                     uint64_t* chunk_len) {
+  if (int rc = depth_handle(ctx, t, "magot_depth_time")) return rc;
+  if (iters <= 0 || !ms4) {
+    set_error("magot_depth_time: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  if (chunk_len) *chunk_len = t->last_len;
+  // one whole-run row per run for the sum pass
+  const uint64_t nr = t->runs.size();
+  std::vector<int64_t> rows(2 * nr);
+  for (uint64_t i = 0; i < nr; ++i) {
+    rows[i] = (int64_t)t->runs[i].line;
+    rows[nr + i] = (int64_t)((i + 1 < nr ? t->runs[i + 1].line : t->n_lines) - t->runs[i].line);
+  }
+  DevBuf d;
+  if (nr) {
+    MAGOT_HIP_TRY(hipMalloc(&d.p, 3 * nr * 8));
+    MAGOT_HIP_TRY(hipMemcpy(d.p, rows.data(), 2 * nr * 8, hipMemcpyHostToDevice));
+  }
+  int64_t* dr = static_cast<int64_t*>(d.p);
+  double total[4] = {0, 0, 0, 0};
+  for (int i = 0; i < iters; ++i)
+    for (int k = 0; k < 4; ++k) {
+      if (k < 2 && !t->last_len) continue;
+      MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+      switch (k) {
+        case 0:
+          MAGOT_HIP_TRY(launch_depth_line_index(t->dev[t->last_slot], t->last_len, t->blk_count,
+                                                t->blk_first, t->scan_tmp, t->scan_bytes,
+                                                ctx->stream));
+          break;
+        case 1:  // the same depths into the same lines; heads, status and carry into scratch
+          MAGOT_HIP_TRY(launch_depth_parse(depth_args(t, t->last_slot, t->last_len, t->last_off,
+                                                      t->last_in, 2, true), ctx->stream));
+          break;
+        case 2:
+          MAGOT_HIP_TRY(launch_depth_directory(t->arena, t->n_lines, t->block_sum, t->dir,
+                                               t->scan_tmp, t->scan_bytes, ctx->stream));
+          break;
+        default:
+          MAGOT_HIP_TRY(launch_depth_sums(t->arena, t->dir, t->n_lines, dr, dr + nr, nr,
+                                          dr + 2 * nr, ctx->stream));
+      }
+      MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+      MAGOT_HIP_TRY(hipEventSynchronize(ctx->ev1));
+      float ms = 0;
+      MAGOT_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+      total[k] += ms;
+    }
+  for (int k = 0; k < 4; ++k) ms4[k] = total[k] / iters;
   return MAGOT_OK;
 }
 

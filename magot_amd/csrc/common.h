@@ -650,6 +650,56 @@ hipError_t launch_track_count(const magot_mask_interval* rows, uint64_t n_rows,
                               const uint64_t* contig_base, const uint32_t* track,
                               const uint32_t* rank, uint64_t span, uint32_t* ones, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// depth_from_gff's integer track (depth.hip; magot_depth_*)
+// ---------------------------------------------------------------------------
+// The depth column of a `samtools depth` table as one int32 per line, in line
+// order (the arena, allocated in whole directory blocks plus one), and the
+// directory: int64 sums per kDepthBlock depths and their exclusive prefix.
+// 256 depths = 1 KiB: a prefix reads one directory entry and at most 64
+// 16-byte loads of one block; the directory adds 1/128 to the arena.
+constexpr int kDepthBlock = 256;
+constexpr int kTextBlock = 4096;  // text bytes per workgroup of the line index and the parse
+constexpr uint64_t depth_blocks(uint64_t n_lines) { return (n_lines + kDepthBlock - 1) / kDepthBlock; }
+constexpr uint64_t depth_text_blocks(uint64_t n) { return (n + kTextBlock - 1) / kTextBlock; }
+// what links a chunk to the next: the lines so far, and the last line's name
+// and position
+struct DepthCarry {
+  uint64_t lines;
+  uint32_t has_prev, name_len, pos, pad;
+  uint8_t name[256];
+};
+struct DepthHead {  // a run's first line
+  uint64_t line, offset;  // offset: of the name in the file
+  uint32_t name_len, pad;
+};
+struct DepthParseArgs {
+  const uint8_t* text;  // the chunk, 16-byte aligned, starting at a line start
+  int64_t n;            // its bytes (> 0)
+  uint64_t file_off;    // its place in the file
+  const uint32_t* blk_first;  // depth_text_blocks(n) + 1: LFs before each text block, the total
+  const DepthCarry* in;
+  DepthCarry* out;      // not `in`
+  int32_t* arena;
+  uint64_t arena_cap;   // lines the arena holds
+  DepthHead* heads;
+  uint32_t* n_heads;    // counts every run head, stored or not
+  uint32_t heads_cap;
+  unsigned long long* status;  // min of (line << 8 | MAGOT_DEPTH_* reason); ~0 when clean
+};
+size_t depth_scan_bytes(uint64_t n);
+hipError_t launch_depth_line_index(const uint8_t* text, uint64_t n, uint32_t* count,
+                                   uint32_t* first, void* scan_tmp, size_t scan_bytes,
+                                   hipStream_t s);
+hipError_t launch_depth_parse(const DepthParseArgs& a, hipStream_t s);
+hipError_t launch_depth_directory(const int32_t* arena, uint64_t n_lines, int64_t* block_sum,
+                                  int64_t* dir, void* scan_tmp, size_t scan_bytes, hipStream_t s);
+hipError_t launch_depth_sums(const int32_t* arena, const int64_t* dir, uint64_t n_lines,
+                             const int64_t* start, const int64_t* length, uint64_t n_rows,
+                             int64_t* sums, hipStream_t s);
+hipError_t launch_depth_groups(const int64_t* sums, const uint64_t* offsets, uint64_t n_groups,
+                               int64_t* out, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

@@ -1309,6 +1309,127 @@ class GenomeTrack(object):
             pass
 
 
+class DepthTrack(object):
+    """depth_from_gff's per-base track on the device (magot_depth_*,
+    genome_tools.py:598-652): the depth column of a ``samtools depth`` table
+    as one int32 per line.  For a table inside the native grammar (magot.h)
+    every contig is one run of lines with positions 1, 2, ..: ``names``,
+    ``lengths`` and ``first`` (the run's first line) are the contig table,
+    and the reference's array of a contig is lines [first, first + length).
+
+    ``parse`` always returns a track; one with ``declined == (reason,
+    line_no)`` (the first offending line, 1-based; None for a whole-table
+    limit) holds nothing else."""
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.declined = None
+        self.names, self.index = [], {}
+        self.lengths = self.first = np.zeros(0, np.int64)
+        self.n_lines = 0
+        self.block = int(_lib.lib().magot_depth_block())
+
+    @classmethod
+    def parse(cls, buffer, chunk_bytes=None, max_runs=None, ctx=None):
+        """The table in ``buffer`` (bytes, mmap, numpy), streamed to the device
+        in chunks of about ``chunk_bytes`` (default: sized for transfer)."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(buffer)
+        h = ctypes.c_void_p()
+        n_lines, n_runs, line = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        reason = ctypes.c_uint32()
+        check(_lib.lib().magot_depth_parse(self.ctx.handle, _text_ptr(view), len(view),
+                                           int(chunk_bytes or 0), int(max_runs or 0),
+                                           ctypes.byref(h), ctypes.byref(n_lines),
+                                           ctypes.byref(n_runs), ctypes.byref(reason),
+                                           ctypes.byref(line)), 'magot_depth_parse')
+        if reason.value:
+            self.declined = (_lib.DEPTH_REASONS[reason.value], line.value or None)
+            return self
+        self.handle = h
+        self.n_lines = n_lines.value
+        n = n_runs.value
+        first = np.zeros(max(n, 1), np.uint64)
+        offset = np.zeros(max(n, 1), np.uint64)
+        name_len = np.zeros(max(n, 1), np.uint32)
+        check(_lib.lib().magot_depth_runs(self.handle, ptr(first), ptr(offset), ptr(name_len), n),
+              'magot_depth_runs')
+        self.first = first[:n].astype(np.int64)
+        self.lengths = np.diff(np.append(self.first, self.n_lines))
+        self.names = [view[o:o + k].tobytes().decode('latin-1')
+                      for o, k in zip(offset[:n].tolist(), name_len[:n].tolist())]
+        self.index = {nm: i for i, nm in enumerate(self.names)}
+        return self
+
+    def _contig(self, contig):
+        return self.index[contig] if isinstance(contig, str) else int(contig)
+
+    def values(self, contig):
+        """An int32 copy of one contig's depths (for tests)."""
+        c = self._contig(contig)
+        out = np.zeros(max(int(self.lengths[c]), 1), np.int32)
+        check(_lib.lib().magot_depth_values(self.ctx.handle, self.handle, int(self.first[c]),
+                                            int(self.lengths[c]), ptr(out)), 'magot_depth_values')
+        return out[:int(self.lengths[c])]
+
+    def _rows(self, contig, start, length):
+        c = np.asarray(contig, dtype=np.int64).reshape(-1)
+        s = np.ascontiguousarray(self.first[c] + np.asarray(start, dtype=np.int64).reshape(-1))
+        return s, np.ascontiguousarray(np.asarray(length, dtype=np.int64).reshape(-1))
+
+    def sums(self, contig, start, length):
+        """int64 sum of each interval: ``length`` depths from 0-based ``start``
+        of contig (index) ``contig``; a length <= 0 gives 0.  The caller clips
+        to the contig, as a numpy slice does."""
+        return self.group_sums(contig, start, length, None)[0]
+
+    def group_sums(self, contig, start, length, group_offsets):
+        """(sums, group sums): ``group_offsets`` is a CSR over the rows
+        (n_groups + 1 ascending row indices)."""
+        s, ln = self._rows(contig, start, length)
+        if len(s) != len(ln):
+            raise MagotError('DepthTrack: one start and one length per row')
+        out = np.zeros(max(len(s), 1), np.int64)
+        off = groups = None
+        n_groups = 0
+        if group_offsets is not None:
+            off = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+            n_groups = len(off) - 1
+            groups = np.zeros(max(n_groups, 1), np.int64)
+        check(_lib.lib().magot_depth_sums(self.ctx.handle, self.handle,
+                                          ptr(s) if len(s) else None, ptr(ln) if len(s) else None,
+                                          len(s), ptr(off) if n_groups > 0 else None,
+                                          max(n_groups, 0), ptr(out),
+                                          ptr(groups) if n_groups > 0 else None),
+              'magot_depth_sums')
+        return out[:len(s)], (None if groups is None else groups[:max(n_groups, 0)])
+
+    def time(self, iters):
+        """Mean device ms per pass: {'line_index', 'parse', 'directory',
+        'sums'}, the first two over the last chunk ('chunk_bytes' bytes of
+        text), the others over the whole table (magot_depth_time)."""
+        ms = np.zeros(4, np.float64)
+        n = ctypes.c_uint64()
+        check(_lib.lib().magot_depth_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                          ctypes.byref(n)), 'magot_depth_time')
+        out = dict(zip(('line_index', 'parse', 'directory', 'sums'), ms.tolist()))
+        out['chunk_bytes'] = n.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_depth_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's

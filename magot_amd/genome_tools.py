@@ -15,6 +15,8 @@
     python -m magot_amd.genome_tools mask_from_gff <fasta> <gff> [mask_type=soft|hard]
            [overwrite_softmask=True] [feature_type=CDS] [order=py2|insertion] [native=False]
     python -m magot_amd.genome_tools at_content_from_fasta <fasta> [native=False]
+    python -m magot_amd.genome_tools depth_from_gff <depth.txt> <gff> [features=['CDS','upstream']]
+           [stream_length=1000] [order=py2|insertion] [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -875,12 +877,299 @@ def at_content_from_fasta(fasta, native='True'):
         _write_bytes(*out)  # what was printed before an exception stays printed
 
 
+class _DepthDecline(Exception):
+    """Why depth_from_gff leaves a call to its host loop."""
+
+
+def _depth_order(table, aset, order):
+    """The iteration order of one of the annotation set's tables."""
+    from . import py2order
+    keys = list(table)
+    if order == 'py2':
+        keys = py2order.order_after_copies(keys, aset.__dict__.get('_magot_copies', 0))
+    return keys
+
+
+def _depth_features(features):
+    """``eval(features)`` for literals (nothing is executed here); a bare
+    word is a NameError, as it is there."""
+    try:
+        return ast.literal_eval(features)
+    except ValueError:
+        raise NameError('name %r is not defined' % features)
+
+
+def _depth_native(depth_file, aset, features_list, stream_length, order, clock):
+    """depth_from_gff's text (a list of bytes) with every sum from the device
+    (engine.DepthTrack); raises _DepthDecline with the reason otherwise."""
+    from . import py2order
+    if not (isinstance(features_list, (list, tuple, set, frozenset)) and
+            all(isinstance(f, str) for f in features_list)):
+        raise _DepthDecline('features is not a container of strings')
+    try:
+        L = _py2_int(stream_length.encode('latin-1'))
+    except (ValueError, AttributeError, UnicodeEncodeError):
+        raise _DepthDecline('stream_length is not an integer')
+    if L < 0:
+        raise _DepthDecline('stream_length < 0: a negative slice bound')
+    if aset is None or not isinstance(aset.__dict__.get('CDS'), dict) or not aset.CDS:
+        raise _DepthDecline('no CDS')
+    want_cds, want_up = 'CDS' in features_list, 'upstream' in features_list
+    cds_ids = _depth_order(aset.CDS, aset, order)
+    try:
+        table = aset.__dict__[aset[aset.CDS[cds_ids[0]].parent].feature_type]
+    except (KeyError, TypeError, AttributeError):
+        raise _DepthDecline("the first CDS's parent is not in the set")
+    track = engine.DepthTrack.parse(genome.read_buffer(depth_file))
+    clock.lap('depth_parse')
+    try:
+        if track.declined is not None:
+            raise _DepthDecline('depth file: %s at line %s' % track.declined)
+        lengths = track.lengths.tolist()
+
+        def clip(seqid, a, b):
+            """(contig, start, length) of arr[a:b], or None for a missing contig"""
+            c = track.index.get(seqid)
+            if c is None:
+                return None
+            lo, hi = slice(a, b).indices(lengths[c])[:2]
+            return (c, lo, max(0, hi - lo))
+
+        # CDS rows, sorted by parent: the device sums them per row and per parent
+        cds_rows, parents, member = [], [], {}
+        if want_cds:
+            for cid in cds_ids:
+                cds = aset.CDS[cid]
+                if not isinstance(cds.parent, str):
+                    raise _DepthDecline('a CDS without a parent')
+                if not (isinstance(cds.coords[0], int) and isinstance(cds.coords[1], int)):
+                    raise _DepthDecline('a coordinate is not an integer')
+                if cds.coords[0] < 1 or cds.coords[1] < 0:
+                    raise _DepthDecline('a CDS start < 1 or end < 0: a negative slice bound')
+                if cds.parent not in member:
+                    member[cds.parent] = []
+                    parents.append(cds.parent)
+                row = clip(cds.seqid, cds.coords[0] - 1, cds.coords[1])
+                member[cds.parent].append(len(cds_rows))
+                cds_rows.append((row, cds.parent, cds.seqid))
+            if cds_rows[0][0] is None:
+                raise _DepthDecline('the first CDS is on a contig missing from the depth file')
+        up_rows = []
+        if want_up:
+            for tid in _depth_order(table, aset, order):
+                tx = table[tid]
+                if tx.strand not in ('+', '-'):
+                    raise _DepthDecline("a transcript strand other than '+' / '-'")
+                try:
+                    lo, hi = tx.get_coords()
+                except Exception:
+                    raise _DepthDecline('a transcript without coordinates')
+                if not (isinstance(lo, int) and isinstance(hi, int)):
+                    raise _DepthDecline('a coordinate is not an integer')
+                if lo < 1 or hi < 0:
+                    raise _DepthDecline('a transcript start < 1 or end < 0: a negative slice bound')
+                if not isinstance(tid, str) or not isinstance(tx.seqid, str):
+                    raise _DepthDecline('a transcript without a name')
+                if tx.strand == '+':
+                    row = clip(tx.seqid, max(0, lo - 1 - L), lo - 1)
+                else:
+                    row = clip(tx.seqid, hi, hi + L)
+                up_rows.append((row, tid, tx.seqid))
+            if not want_cds and up_rows and up_rows[0][0] is None:
+                raise _DepthDecline('the first transcript is on a contig missing from the depth file')
+        clock.lap('rows')
+
+        # device rows: the present CDS rows parent by parent, then the flanks
+        rows, offsets, cds_at = [], [0], {}
+        for parent in parents:
+            for k in member[parent]:
+                if cds_rows[k][0] is not None:
+                    cds_at[k] = len(rows)
+                    rows.append(cds_rows[k][0])
+            offsets.append(len(rows))
+        up_at = {}
+        for k, (row, _, _) in enumerate(up_rows):
+            if row is not None:
+                up_at[k] = len(rows)
+                rows.append(row)
+        if rows:
+            tab = np.array(rows, dtype=np.int64).reshape(-1, 3)
+            sums, groups = track.group_sums(tab[:, 0], tab[:, 1], tab[:, 2], offsets)
+            sums, groups = sums.tolist(), groups.tolist()
+        else:
+            sums, groups = [], [0] * len(parents)
+        clock.lap('kernels')
+    finally:
+        track.close()
+
+    # the reference's carry-over: a feature on a missing contig adds the sum
+    # before it once more
+    out, missing, covsum = [], [], None
+    if want_cds:
+        out.append(b'#CDS counts\n')
+        total = dict(zip(parents, groups))
+        for k, (row, parent, seqid) in enumerate(cds_rows):
+            if row is not None:
+                covsum = sums[cds_at[k]]
+            else:
+                missing.append(parent + ' on ' + seqid)
+                total[parent] += covsum
+        shown = py2order.dict_order(parents) if order == 'py2' else parents
+        out += [('%s\t%d\n' % (parent, total[parent])).encode('latin-1') for parent in shown]
+    if want_up:
+        out.append(b'#upstream ' + stream_length.encode('latin-1') + b'bp counts\n')
+        for k, (row, tid, seqid) in enumerate(up_rows):
+            if row is not None:
+                covsum = sums[up_at[k]]
+            else:
+                missing.append(tid + ' on ' + seqid)
+            out.append(('%s\t%d\n' % (tid, covsum)).encode('latin-1'))
+    out += _depth_missing(missing, order)
+    return out
+
+
+def _depth_missing(missing, order):
+    """genome_tools.py:649-652: ``list(set(missing_list))``."""
+    from . import py2order
+    if not missing:
+        return []
+    seen = list(dict.fromkeys(missing))
+    if order == 'py2':
+        seen = py2order.dict_order(seen)
+    return [b'#missing from depth file\n'] + [(m + '\n').encode('latin-1') for m in seen]
+
+
+def _depth_host(depth_file, aset, features_list, stream_length, order, out):
+    """genome_tools.py:602-652 line for line; what it prints goes to ``out``."""
+    from . import py2order
+    missing = []
+    lines = _file_lines(depth_file)
+    lens = {}
+    for line in lines:
+        seqid = line.split()[0]
+        if seqid in lens:
+            lens[seqid] = lens[seqid] + 1
+        else:
+            lens[seqid] = 1
+    arrays = {}
+    for seqid in lens:
+        arrays[seqid.decode('latin-1')] = np.zeros(lens[seqid], dtype=np.int64)
+    for line in lines:
+        fields = line.split()
+        if len(fields) > 1:
+            value = _py2_int(fields[2])
+            arrays[fields[0].decode('latin-1')][_py2_int(fields[1]) - 1] = value
+    unbound = UnboundLocalError("local variable 'covsum' referenced before assignment")
+    covsum = None
+    if 'CDS' in features_list:
+        out.append(b'#CDS counts\n')
+        totals = {}
+        for cid in _depth_order(aset.CDS, aset, order):
+            cds = aset.CDS[cid]
+            if cds.seqid in arrays:
+                covsum = int(arrays[cds.seqid][cds.coords[0] - 1:cds.coords[1]].sum())
+            else:
+                missing.append(cds.parent + ' on ' + cds.seqid)
+            if covsum is None:
+                raise unbound
+            if cds.parent in totals:
+                totals[cds.parent] = totals[cds.parent] + covsum
+            else:
+                totals[cds.parent] = covsum
+        shown = py2order.dict_order(list(totals)) if order == 'py2' else list(totals)
+        for parent in shown:
+            out.append((parent + '\t' + str(totals[parent]) + '\n').encode('latin-1'))
+    if 'upstream' in features_list:
+        out.append(('#upstream ' + stream_length + 'bp counts\n').encode('latin-1'))
+        first = _depth_order(aset.CDS, aset, order)[0]
+        table = aset.__dict__[aset[aset.CDS[first].parent].feature_type]
+        start = stop = None
+        for tid in _depth_order(table, aset, order):
+            tx = table[tid]
+            if tx.strand == '+':
+                stop = tx.get_coords()[0] - 1
+                start = stop - _py2_int(stream_length.encode('latin-1'))
+                if start < 0:
+                    start = 0
+            elif tx.strand == '-':
+                start = tx.get_coords()[1]
+                stop = start + _py2_int(stream_length.encode('latin-1'))
+            if tx.seqid in arrays:
+                if start is None:
+                    raise UnboundLocalError("local variable 'start' referenced before assignment")
+                covsum = int(arrays[tx.seqid][start:stop].sum())
+            else:
+                missing.append(tid + ' on ' + tx.seqid)
+            if covsum is None:
+                raise unbound
+            out.append((tid + '\t' + str(covsum) + '\n').encode('latin-1'))
+    out += _depth_missing(missing, order)
+
+
+def depth_from_gff(depth_file, gff, features="['CDS','intron','upstream','downstream']",
+                   stream_length='1000', order='py2', native='True'):
+    """genome_tools.py:598-652: from a ``samtools depth`` table (``seqid \\t
+    position \\t depth``, one line per base) and a GFF, the summed depth under
+    every transcript's CDS ('CDS' in ``features``) and over the
+    ``stream_length`` bases upstream of every transcript ('upstream'), then
+    the features whose contig the table lacks.  'intron' and 'downstream' do
+    nothing, as in the reference.  Reference quirks kept: a contig's array has
+    as many slots as the table has lines for it; a feature on a missing contig
+    repeats (a CDS: adds once more) the sum before it.
+
+    On the device (engine.DepthTrack: the table parsed into an int32 per line
+    chunk by chunk, a sum directory, one sum per CDS and flank and one total
+    per transcript) when the table is inside the native grammar -- every
+    contig one run of lines with positions 1, 2, .. -- and no feature makes
+    the reference wrap a slice or raise: a start < 1, an end < 0, a negative
+    ``stream_length``, a strand other than '+'/'-', a first feature on a
+    missing contig, no CDS, ``features`` that is no container of strings.
+    Everything else, and ``native=False``, takes the host loop, which restates
+    the reference and raises what it raises; what was printed before stays
+    printed.  ``depth_from_gff.last_path`` names the path the last call took
+    and why.
+
+    Tables come in the reference's Python 2 dict order unless
+    ``order='insertion'``.  The lines after '#missing from depth file' are a
+    Python 2 *set's*: py2order.dict_order over the first occurrences is
+    believed to model it (CPython 2.7's setobject.c uses the same hash, probe
+    sequence and growth rule as its dict), but no Python 2 has been run to
+    confirm it."""
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'insertion' or 'py2'")
+    clock = _Clock()
+    aset = genome.read_gff(gff)
+    clock.lap('gff_read')
+    depth_from_gff.last_path = ('depth_from_gff', 'host', 'features is not a literal')
+    features_list = _depth_features(features)
+    why = "native != 'True'"
+    if native == 'True' and isinstance(depth_file, str) and os.path.isfile(depth_file):
+        try:
+            out = _depth_native(depth_file, aset, features_list, stream_length, order, clock)
+            depth_from_gff.last_path = ('depth_from_gff', 'native', None)
+            _write_bytes(*out)
+            clock.lap('write')
+            clock.emit()
+            return
+        except _DepthDecline as e:
+            why = str(e)
+    depth_from_gff.last_path = ('depth_from_gff', 'host', why)
+    out = []
+    try:
+        _depth_host(depth_file, aset, features_list, stream_length, order, out)
+    finally:
+        _write_bytes(*out)  # what was printed before an exception stays printed
+
+
+depth_from_gff.last_path = None
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
          'extract_upstream_downstream': extract_upstream_downstream,
          'coords2fasta': coords2fasta,
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,
          'get_seq_from_fasta': get_seq_from_fasta, 'dna2orfs': dna2orfs,
-         'mask_from_gff': mask_from_gff}
+         'mask_from_gff': mask_from_gff, 'depth_from_gff': depth_from_gff}
 
 
 def parse_argv(argv):

@@ -313,3 +313,37 @@ def _make(config, seed, genome_bases, n_tx, iupac_rate, with_genome=True):
         genome = _genome(rng, G, iupac_rate=rate) if with_genome else None
         return Workload(config, genome, L, *tx, outputs='nuc+pep')
     raise ValueError(config)
+
+
+def write_depth_table(path, names, lengths, seed=SEED_BASE, rows=1 << 22):
+    """A ``samtools depth`` table (``name \\t position \\t depth``) with one
+    line per base of every contig, written ``rows`` lines at a time without a
+    Python loop over lines.  Positions are zero-padded to the width of the
+    contig's length and depths (uniform 0..999) to three digits, so every line
+    of a contig has one length; leading zeros are inside DepthTrack's grammar
+    and mean nothing to ``int``.  Returns (lines, bytes)."""
+    rng = np.random.default_rng(seed)
+    lines = size = 0
+    with open(path, 'wb') as fh:
+        for nm, n in zip(names, lengths):
+            n = int(n)
+            name = np.frombuffer(nm.encode('latin-1'), dtype=np.uint8)
+            k, w = len(name), len(str(n))
+            for lo in range(0, n, rows):
+                m = min(rows, n - lo)
+                out = np.empty((m, k + w + 6), dtype=np.uint8)
+                out[:, :k] = name
+                out[:, k] = out[:, k + w + 1] = 9
+                out[:, -1] = 10
+                pos = np.arange(lo + 1, lo + m + 1, dtype=np.int32)
+                for d in range(w):
+                    out[:, k + w - d] = 48 + pos % 10
+                    pos //= 10
+                depth = rng.integers(0, 1000, m, dtype=np.int32)
+                for d in range(3):
+                    out[:, k + w + 4 - d] = 48 + depth % 10
+                    depth //= 10
+                fh.write(out.data)
+                lines += m
+                size += out.size
+    return lines, size
