@@ -826,6 +826,45 @@ int magot_depth_time(magot_ctx* ctx, magot_depth* t, int iters, double* ms4,
                      uint64_t* chunk_len);
 void magot_depth_destroy(magot_depth* t);
 
+/*
+ * fqstats (genome_tools.py:85-124) on the device: the lengths of a FASTQ's
+ * sequence lines as a histogram, and the tool's figures from it.
+ *
+ * A line ends at LF only; line k (from 0) is a sequence line when k % 4 == 1,
+ * whatever it holds; its length is its bytes without the LF (a CR counts), and
+ * one less than its bytes for a last line without LF.  Lines may be of any
+ * length; no text is declined.
+ *   magot_fq_dense      lengths below it are counted in one uint64 bin each,
+ *       longer ones kept in a list.
+ *   magot_fq_parse      streams the text in chunks of chunk_bytes (0: a default
+ *       sized for transfer; 1 KB at the least, 1 GB at the most; cut anywhere,
+ *       in a line or between a CR and its LF) through pinned staging, each upload
+ *       overlapped with the passes over the chunk before, and reduces the
+ *       histogram to the figures on the device.
+ *   magot_fq_stats      out8: reads, bases, desc[reads / 2], desc[reads / 4],
+ *       desc[reads * 3 / 4] (desc: the lengths in descending order), and n25,
+ *       n50, n75: the first length of desc at which the running sum is above
+ *       bases / 4, bases / 2, bases * 3 / 4.  Bit k of *flags: n25 / n50 / n75
+ *       (k = 0, 1, 2) was set (never when bases is 0).  With no reads
+ *       everything but out8[0] is 0.
+ *   magot_fq_histogram  the lengths that occur, ascending, and how often:
+ *       *n entries; with lengths and counts NULL only *n is set, otherwise
+ *       cap must be at least *n.
+ *   magot_fq_time       mean device ms over `iters` runs of: the line index and
+ *       the length pass of the last chunk (still on the device; *chunk_len its
+ *       bytes; into a histogram of their own), the reduction, and a device
+ *       copy of chunk_len bytes, in ms4[0..3].
+ */
+typedef struct magot_fq magot_fq;
+uint64_t magot_fq_dense(void);
+int magot_fq_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t chunk_bytes,
+                   magot_fq** out);
+int magot_fq_stats(const magot_fq* t, uint64_t* out8, uint32_t* flags);
+int magot_fq_histogram(magot_ctx* ctx, magot_fq* t, int64_t* lengths, uint64_t* counts,
+                       uint64_t cap, uint64_t* n);
+int magot_fq_time(magot_ctx* ctx, magot_fq* t, int iters, double* ms4, uint64_t* chunk_len);
+void magot_fq_destroy(magot_fq* t);
+
 #ifdef __cplusplus
 }
 #endif

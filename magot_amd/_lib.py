@@ -61,6 +61,8 @@ EXPORTS = (
     'magot_track_windows_destroy', 'magot_track_destroy',
     'magot_depth_block', 'magot_depth_parse', 'magot_depth_runs', 'magot_depth_values',
     'magot_depth_sums', 'magot_depth_time', 'magot_depth_destroy',
+    'magot_fq_dense', 'magot_fq_parse', 'magot_fq_stats', 'magot_fq_histogram', 'magot_fq_time',
+    'magot_fq_destroy',
 )
 
 ERR_ARG = -1
@@ -272,6 +274,13 @@ def _declare(lib):
                                             ctypes.c_uint64, _vp, _vp]),
         'magot_depth_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p]),
         'magot_depth_destroy': (None, [_vp]),
+        'magot_fq_dense': (ctypes.c_uint64, []),
+        'magot_fq_parse': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                          ctypes.POINTER(_vp)]),
+        'magot_fq_stats': (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        'magot_fq_histogram': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _u64p]),
+        'magot_fq_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p]),
+        'magot_fq_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

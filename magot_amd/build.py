@@ -19,7 +19,7 @@ ARCH = os.environ.get('MAGOT_OFFLOAD_ARCH', 'gfx950')
 
 SOURCES = ['abi.hip', 'extract.hip', 'seqops.hip', 'pack.cpp', 'gffplan.cpp', 'fasta.cpp',
            'render.hip', 'devpack.hip', 'wire.hip', 'tileblocks.cpp', 'tileplan.cpp',
-           'orfcall.hip', 'maskplan.cpp', 'maskgen.hip', 'track.hip', 'depth.hip']
+           'orfcall.hip', 'maskplan.cpp', 'maskgen.hip', 'track.hip', 'depth.hip', 'fastq.hip']
 HEADERS = ['common.h', 'hostutil.h', 'wavecopy.h', os.path.join('..', '..', 'include', 'magot.h')]
 
 CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function',

@@ -3518,3 +3518,319 @@ int magot_depth_time(magot_ctx* ctx, magot_depth* t, int iters, double* ms4,
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// fqstats' read-length histogram (fastq.hip; genome_tools.py:85-124)
+// ---------------------------------------------------------------------------
+
+struct magot_fq {
+  magot_ctx* ctx = nullptr;
+  void* mem = nullptr;  // everything but the text buffers
+  unsigned long long* hist = nullptr;
+  int64_t* longs = nullptr;    // as appended; sorted descending behind them
+  uint64_t longs_cap = 0, n_longs = 0;
+  FqBlock* blk = nullptr;
+  FqBlock* pre = nullptr;
+  FqItem* cum = nullptr;
+  void* scan_tmp = nullptr;
+  void* sort_tmp = nullptr;
+  size_t scan_bytes = 0, sort_bytes = 0;
+  FqCarry* carry = nullptr;               // two that alternate, and a scratch one for the timed pass
+  unsigned long long* cursor = nullptr;   // the list's
+  uint64_t* out = nullptr;                // launch_fq_reduce's nine words; [9..17]: scratch
+  // text staging: chunk k goes through slot k & 1
+  uint8_t* dev[2] = {nullptr, nullptr};
+  uint8_t* pin[2] = {nullptr, nullptr};
+  hipEvent_t up_done[2] = {nullptr, nullptr}, pass_done[2] = {nullptr, nullptr};
+  hipStream_t copy = nullptr;
+  // the last chunk, still in dev[last_slot] (magot_fq_time)
+  int last_slot = 0, last_in = 0;
+  uint64_t last_len = 0, last_off = 0, file_bytes = 0;
+  uint64_t stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  bool fetched = false;  // the histogram below
+  std::vector<int64_t> lengths;
+  std::vector<uint64_t> counts;
+};
+
+namespace {
+
+void fq_free_staging(magot_fq* t, bool text_too) {
+  for (int s = 0; s < 2; ++s) {
+    if (t->pin[s]) (void)hipHostFree(t->pin[s]);
+    t->pin[s] = nullptr;
+    if (text_too && t->dev[s]) {
+      (void)hipFree(t->dev[s]);
+      t->dev[s] = nullptr;
+    }
+  }
+}
+
+int fq_handle(magot_ctx* ctx, const magot_fq* t, const char* who) {
+  if (int rc = bind(ctx)) return rc;
+  if (!t || t->ctx != ctx) {
+    set_error(std::string(who) + ": null handle, or a handle of another context");
+    return MAGOT_ERR_ARG;
+  }
+  return MAGOT_OK;
+}
+
+FqChunkArgs fq_args(const magot_fq* t, int slot, uint64_t n, uint64_t off, int in, int out) {
+  FqChunkArgs a{};
+  a.text = t->dev[slot];
+  a.n = (int64_t)n;
+  a.file_off = (int64_t)off;
+  a.blk = t->blk;
+  a.pre = t->pre;
+  a.in = t->carry + in;
+  a.out = t->carry + out;
+  a.hist = t->hist;
+  a.longs = t->longs;
+  a.n_longs = t->cursor;
+  a.longs_cap = t->longs_cap;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+void magot_fq_destroy(magot_fq* t) {
+  if (!t) return;
+  if (t->ctx) (void)hipSetDevice(t->ctx->device);
+  fq_free_staging(t, true);
+  for (int s = 0; s < 2; ++s) {
+    if (t->up_done[s]) (void)hipEventDestroy(t->up_done[s]);
+    if (t->pass_done[s]) (void)hipEventDestroy(t->pass_done[s]);
+  }
+  if (t->copy) (void)hipStreamDestroy(t->copy);
+  if (t->mem) (void)hipFree(t->mem);
+  delete t;
+}
+
+uint64_t magot_fq_dense(void) { return kFqDense; }
+
+int magot_fq_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t chunk_bytes,
+                   magot_fq** out) {
+  if (int rc = bind(ctx)) return rc;
+  if (!out || (len && !text)) {
+    set_error("magot_fq_parse: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  *out = nullptr;
+  struct Guard {
+    magot_fq* t;
+    ~Guard() { magot_fq_destroy(t); }
+  } guard{new magot_fq()};
+  magot_fq* t = guard.t;
+  t->ctx = ctx;
+  t->file_bytes = len;
+  uint64_t chunk = chunk_bytes ? chunk_bytes : kDepthChunkDefault;
+  chunk = std::min(std::max(chunk, kDepthChunkMin), kDepthChunkMax);
+  chunk = std::min(chunk, std::max<uint64_t>(len, 1));
+  const int n_slots = len > chunk ? 2 : 1;
+  t->longs_cap = fq_long_cap(len);
+  const uint64_t text_blocks = depth_text_blocks(chunk);
+  t->scan_bytes = fq_scan_bytes(text_blocks + 1, t->longs_cap + kFqDense);
+  t->sort_bytes = fq_sort_bytes(t->longs_cap);
+  Carve cv;
+  const uint64_t o_hist = cv.take<unsigned long long>(kFqDense);
+  const uint64_t o_longs = cv.take<int64_t>(2 * t->longs_cap);
+  const uint64_t o_blk = cv.take<FqBlock>(text_blocks + 1);
+  const uint64_t o_pre = cv.take<FqBlock>(text_blocks + 1);
+  const uint64_t o_cum = cv.take<FqItem>(t->longs_cap + kFqDense);
+  const uint64_t o_scan = cv.take<uint8_t>(t->scan_bytes);
+  const uint64_t o_sort = cv.take<uint8_t>(t->sort_bytes);
+  const uint64_t o_small = cv.take<uint8_t>(256);
+  MAGOT_HIP_TRY(hipMalloc(&t->mem, cv.used + 256));
+  char* base = static_cast<char*>(t->mem);
+  t->hist = reinterpret_cast<unsigned long long*>(base + o_hist);
+  t->longs = reinterpret_cast<int64_t*>(base + o_longs);
+  t->blk = reinterpret_cast<FqBlock*>(base + o_blk);
+  t->pre = reinterpret_cast<FqBlock*>(base + o_pre);
+  t->cum = reinterpret_cast<FqItem*>(base + o_cum);
+  t->scan_tmp = base + o_scan;
+  t->sort_tmp = base + o_sort;
+  // 256 bytes: three carries, the list's cursor, the nine result words twice
+  static_assert(3 * sizeof(FqCarry) + 8 + 18 * 8 <= 256, "the small block");
+  t->carry = reinterpret_cast<FqCarry*>(base + o_small);
+  t->cursor = reinterpret_cast<unsigned long long*>(base + o_small + 3 * sizeof(FqCarry));
+  t->out = reinterpret_cast<uint64_t*>(t->cursor + 1);
+  struct {
+    FqCarry carry[3];
+    uint64_t words[19];
+  } small{};
+  for (FqCarry& c : small.carry) c.last_lf = -1;  // no LF yet
+  MAGOT_HIP_TRY(hipMemsetAsync(t->hist, 0, kFqDense * 8, ctx->stream));
+  MAGOT_HIP_TRY(hipMemcpy(t->carry, &small, sizeof(small), hipMemcpyHostToDevice));
+  MAGOT_HIP_TRY(hipStreamCreateWithFlags(&t->copy, hipStreamNonBlocking));
+  for (int s = 0; s < n_slots; ++s) {
+    MAGOT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->dev[s]), chunk + 256));
+    MAGOT_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->pin[s]), chunk, hipHostMallocDefault));
+    MAGOT_HIP_TRY(hipEventCreateWithFlags(&t->up_done[s], hipEventDisableTiming));
+    MAGOT_HIP_TRY(hipEventCreateWithFlags(&t->pass_done[s], hipEventDisableTiming));
+  }
+  // the zeroing above is on the context stream; the first upload is not
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+
+  uint64_t off = 0, k = 0;
+  while (off < len) {  // cut wherever the chunk ends
+    const uint64_t n = std::min(chunk, len - off);
+    const int s = (int)(k & 1);
+    if (k >= 2) MAGOT_HIP_TRY(hipEventSynchronize(t->up_done[s]));  // pin[s] was read
+    std::memcpy(t->pin[s], text + off, n);
+    if (k >= 2) MAGOT_HIP_TRY(hipStreamWaitEvent(t->copy, t->pass_done[s], 0));
+    MAGOT_HIP_TRY(hipMemcpyAsync(t->dev[s], t->pin[s], n, hipMemcpyHostToDevice, t->copy));
+    MAGOT_HIP_TRY(hipEventRecord(t->up_done[s], t->copy));
+    MAGOT_HIP_TRY(hipStreamWaitEvent(ctx->stream, t->up_done[s], 0));
+    const FqChunkArgs a = fq_args(t, s, n, off, (int)(k & 1), (int)((k + 1) & 1));
+    MAGOT_HIP_TRY(launch_fq_line_index(a, t->scan_tmp, t->scan_bytes, ctx->stream));
+    MAGOT_HIP_TRY(launch_fq_lengths(a, fq_grid(n, ctx->n_cu), ctx->stream));
+    MAGOT_HIP_TRY(hipEventRecord(t->pass_done[s], ctx->stream));
+    t->last_slot = s;
+    t->last_in = (int)(k & 1);
+    t->last_len = n;
+    t->last_off = off;
+    off += n;
+    ++k;
+  }
+  // a last line without its LF, from the carry the last chunk left
+  MAGOT_HIP_TRY(launch_fq_tail(fq_args(t, 0, 0, len, (int)(k & 1), 2), len, ctx->stream));
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  MAGOT_HIP_TRY(hipStreamSynchronize(t->copy));
+  fq_free_staging(t, false);
+
+  unsigned long long n_longs = 0;
+  MAGOT_HIP_TRY(hipMemcpy(&n_longs, t->cursor, 8, hipMemcpyDeviceToHost));
+  if (n_longs > t->longs_cap) {
+    set_error("magot_fq_parse: more long lines than the text has room for");
+    return MAGOT_ERR_STATE;
+  }
+  t->n_longs = n_longs;
+  FqReduceArgs r{};
+  r.hist = t->hist;
+  r.longs = t->longs + t->longs_cap;
+  r.n_longs = t->n_longs;
+  r.cum = t->cum;
+  r.out = t->out;
+  MAGOT_HIP_TRY(launch_fq_sort(t->longs, t->longs + t->longs_cap, t->n_longs, t->sort_tmp,
+                               t->sort_bytes, ctx->stream));
+  MAGOT_HIP_TRY(launch_fq_reduce(r, t->scan_tmp, t->scan_bytes, ctx->stream));
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  MAGOT_HIP_TRY(hipMemcpy(t->stats, t->out, sizeof(t->stats), hipMemcpyDeviceToHost));
+  guard.t = nullptr;
+  *out = t;
+  return MAGOT_OK;
+}
+
+int magot_fq_stats(const magot_fq* t, uint64_t* out8, uint32_t* flags) {
+  if (!t || !out8 || !flags) {
+    set_error("magot_fq_stats: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  for (int k = 0; k < 8; ++k) out8[k] = t->stats[k];
+  *flags = (uint32_t)t->stats[8];
+  return MAGOT_OK;
+}
+
+int magot_fq_histogram(magot_ctx* ctx, magot_fq* t, int64_t* lengths, uint64_t* counts,
+                       uint64_t cap, uint64_t* n) {
+  if (int rc = fq_handle(ctx, t, "magot_fq_histogram")) return rc;
+  if (!n) {
+    set_error("magot_fq_histogram: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  if (!t->fetched) {
+    std::vector<unsigned long long> hist(kFqDense);
+    std::vector<int64_t> longs(t->n_longs);
+    MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    MAGOT_HIP_TRY(hipMemcpy(hist.data(), t->hist, kFqDense * 8, hipMemcpyDeviceToHost));
+    if (t->n_longs)
+      MAGOT_HIP_TRY(hipMemcpy(longs.data(), t->longs + t->longs_cap, t->n_longs * 8,
+                              hipMemcpyDeviceToHost));
+    for (uint64_t b = 0; b < kFqDense; ++b)
+      if (hist[b]) {
+        t->lengths.push_back((int64_t)b);
+        t->counts.push_back(hist[b]);
+      }
+    for (uint64_t i = t->n_longs; i-- > 0;) {  // descending on the device
+      if (!t->lengths.empty() && t->lengths.back() == longs[i]) {
+        ++t->counts.back();
+      } else {
+        t->lengths.push_back(longs[i]);
+        t->counts.push_back(1);
+      }
+    }
+    t->fetched = true;
+  }
+  *n = t->lengths.size();
+  if (!lengths && !counts) return MAGOT_OK;  // the size alone
+  if (!lengths || !counts || cap < t->lengths.size()) {
+    set_error("magot_fq_histogram: null output, or output buffers too small");
+    return MAGOT_ERR_ARG;
+  }
+  std::copy(t->lengths.begin(), t->lengths.end(), lengths);
+  std::copy(t->counts.begin(), t->counts.end(), counts);
+  return MAGOT_OK;
+}
+
+int magot_fq_time(magot_ctx* ctx, magot_fq* t, int iters, double* ms4, uint64_t* chunk_len) {
+  if (int rc = fq_handle(ctx, t, "magot_fq_time")) return rc;
+  if (iters <= 0 || !ms4) {
+    set_error("magot_fq_time: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  if (chunk_len) *chunk_len = t->last_len;
+  // a histogram, a list and a cursor of their own for the timed length pass,
+  // and the copy's target
+  Carve cv;
+  const uint64_t o_hist = cv.take<unsigned long long>(kFqDense);
+  const uint64_t o_longs = cv.take<int64_t>(t->longs_cap);
+  const uint64_t o_cursor = cv.take<unsigned long long>(1);
+  const uint64_t o_copy = cv.take<uint8_t>(t->last_len);
+  DevBuf d;
+  MAGOT_HIP_TRY(hipMalloc(&d.p, cv.used + 256));
+  char* base = static_cast<char*>(d.p);
+  MAGOT_HIP_TRY(hipMemsetAsync(base, 0, o_copy, ctx->stream));
+  FqChunkArgs a = fq_args(t, t->last_slot, t->last_len, t->last_off, t->last_in, 2);
+  a.hist = reinterpret_cast<unsigned long long*>(base + o_hist);
+  a.longs = reinterpret_cast<int64_t*>(base + o_longs);
+  a.n_longs = reinterpret_cast<unsigned long long*>(base + o_cursor);
+  FqReduceArgs r{};
+  r.hist = t->hist;
+  r.longs = t->longs + t->longs_cap;
+  r.n_longs = t->n_longs;
+  r.cum = t->cum;
+  r.out = t->out + 9;
+  double total[4] = {0, 0, 0, 0};
+  for (int i = 0; i < iters; ++i)
+    for (int k = 0; k < 4; ++k) {
+      if (k != 2 && !t->last_len) continue;
+      if (k == 2) MAGOT_HIP_TRY(hipMemsetAsync(r.out, 0, 9 * 8, ctx->stream));
+      MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+      switch (k) {
+        case 0:
+          MAGOT_HIP_TRY(launch_fq_line_index(a, t->scan_tmp, t->scan_bytes, ctx->stream));
+          break;
+        case 1:
+          MAGOT_HIP_TRY(launch_fq_lengths(a, fq_grid(t->last_len, ctx->n_cu), ctx->stream));
+          break;
+        case 2:
+          MAGOT_HIP_TRY(launch_fq_sort(t->longs, t->longs + t->longs_cap, t->n_longs,
+                                       t->sort_tmp, t->sort_bytes, ctx->stream));
+          MAGOT_HIP_TRY(launch_fq_reduce(r, t->scan_tmp, t->scan_bytes, ctx->stream));
+          break;
+        default:
+          MAGOT_HIP_TRY(hipMemcpyAsync(base + o_copy, t->dev[t->last_slot], t->last_len,
+                                       hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+      MAGOT_HIP_TRY(hipEventSynchronize(ctx->ev1));
+      float ms = 0;
+      MAGOT_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+      total[k] += ms;
+    }
+  for (int k = 0; k < 4; ++k) ms4[k] = total[k] / iters;
+  return MAGOT_OK;
+}
+
+}  // extern "C"

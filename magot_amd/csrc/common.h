@@ -700,6 +700,57 @@ hipError_t launch_depth_sums(const int32_t* arena, const int64_t* dir, uint64_t 
 hipError_t launch_depth_groups(const int64_t* sums, const uint64_t* offsets, uint64_t n_groups,
                                int64_t* out, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// fqstats' read-length histogram (fastq.hip; magot_fq_*)
+// ---------------------------------------------------------------------------
+// Lengths below kFqDense are counted in uint64 hist[kFqDense]; a longer one is
+// appended to a list (such a line has at least kFqDense bytes of text, so the
+// list is bounded by the file's size).
+constexpr uint64_t kFqDense = 1ull << 20;
+constexpr uint64_t fq_long_cap(uint64_t file_bytes) { return file_bytes / kFqDense + 2; }
+// per text block, and after the scan the blocks before it: LFs, and the file
+// offset of the last LF (-1: none)
+struct FqBlock {
+  uint64_t lines;
+  int64_t last_lf;
+};
+typedef FqBlock FqCarry;  // the same over the chunks before: what links a chunk to the next
+struct FqItem {  // running totals of the descending walk
+  uint64_t count, bases;
+};
+struct FqChunkArgs {
+  const uint8_t* text;  // the chunk, 16-byte aligned; cut anywhere
+  int64_t n;            // its bytes (> 0)
+  int64_t file_off;     // its place in the file
+  FqBlock* blk;         // depth_text_blocks(n) + 1: the blocks' own values, the last one empty
+  FqBlock* pre;         // their exclusive scan; entry depth_text_blocks(n) is the chunk's total
+  const FqCarry* in;
+  FqCarry* out;         // not `in`
+  unsigned long long* hist;       // kFqDense bins
+  int64_t* longs;                 // lengths >= kFqDense
+  unsigned long long* n_longs;    // counts every one, stored or not
+  uint64_t longs_cap;
+};
+struct FqReduceArgs {
+  const unsigned long long* hist;
+  const int64_t* longs;  // descending
+  uint64_t n_longs;
+  FqItem* cum;           // n_longs + kFqDense
+  uint64_t* out;         // 9: reads, bases, median, 25 % and 75 % marks, n25, n50, n75, and
+                         // which of the last three were set (bits 0..2); zero before the launch
+};
+size_t fq_scan_bytes(uint64_t n_blocks, uint64_t n_items);
+size_t fq_sort_bytes(uint64_t n);
+unsigned fq_grid(uint64_t n, int n_cu);
+hipError_t launch_fq_line_index(const FqChunkArgs& a, void* scan_tmp, size_t scan_bytes,
+                                hipStream_t s);
+hipError_t launch_fq_lengths(const FqChunkArgs& a, unsigned grid, hipStream_t s);
+hipError_t launch_fq_tail(const FqChunkArgs& a, uint64_t file_bytes, hipStream_t s);
+hipError_t launch_fq_sort(const int64_t* in, int64_t* out, uint64_t n, void* tmp, size_t bytes,
+                          hipStream_t s);
+hipError_t launch_fq_reduce(const FqReduceArgs& a, void* scan_tmp, size_t scan_bytes,
+                            hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

@@ -1430,6 +1430,88 @@ class DepthTrack(object):
             pass
 
 
+class ReadLengths(object):
+    """fqstats' read lengths on the device (magot_fq_*, genome_tools.py:85-124):
+    the lengths of a FASTQ's sequence lines -- line k (from 0) with k % 4 == 1,
+    ended by LF only, whatever they hold -- as a histogram, and the tool's
+    figures reduced from it there.  Lines may be of any length and the text is
+    cut into chunks anywhere; nothing is declined."""
+
+    KEYS = ('reads', 'bases', 'median', 'reads25', 'reads75', 'n25', 'n50', 'n75')
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.reads = self.bases = 0
+        self.dense = int(_lib.lib().magot_fq_dense())
+        self._stats = None
+
+    @classmethod
+    def parse(cls, data, chunk_bytes=0, ctx=None):
+        """The FASTQ text in ``data`` (bytes, a buffer, an mmap, numpy), streamed
+        to the device in chunks of ``chunk_bytes`` (0: sized for transfer)."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(data)
+        h = ctypes.c_void_p()
+        check(_lib.lib().magot_fq_parse(self.ctx.handle, _text_ptr(view), len(view),
+                                        int(chunk_bytes or 0), ctypes.byref(h)), 'magot_fq_parse')
+        self.handle = h
+        out = np.zeros(8, np.uint64)
+        flags = ctypes.c_uint32()
+        check(_lib.lib().magot_fq_stats(self.handle, ptr(out), ctypes.byref(flags)),
+              'magot_fq_stats')
+        vals = [int(x) for x in out.tolist()]
+        for k in range(3):  # an N-value that was never set
+            if not flags.value >> k & 1:
+                vals[5 + k] = None
+        self._stats = dict(zip(self.KEYS, vals))
+        self.reads, self.bases = vals[0], vals[1]
+        return self
+
+    def stats(self):
+        """{'reads', 'bases', 'median', 'reads25', 'reads75', 'n25', 'n50',
+        'n75'}: the figures fqstats prints, in its order; an N-value that was
+        never set (no bases at all) is None.  With no reads the order
+        statistics mean nothing (the tool divides by zero before them)."""
+        return dict(self._stats)
+
+    def histogram(self):
+        """(lengths ascending, int64 counts): the lengths that occur."""
+        n = ctypes.c_uint64()
+        L = _lib.lib()
+        check(L.magot_fq_histogram(self.ctx.handle, self.handle, None, None, 0, ctypes.byref(n)),
+              'magot_fq_histogram')
+        lengths = np.zeros(max(n.value, 1), np.int64)
+        counts = np.zeros(max(n.value, 1), np.uint64)
+        check(L.magot_fq_histogram(self.ctx.handle, self.handle, ptr(lengths), ptr(counts),
+                                   n.value, ctypes.byref(n)), 'magot_fq_histogram')
+        return lengths[:n.value], counts[:n.value].astype(np.int64)
+
+    def time(self, iters):
+        """Mean device ms per pass: {'line_index', 'lengths', 'reduce', 'copy'},
+        the first two and the device copy over the last chunk ('chunk_bytes'
+        bytes of text), the reduction over the whole histogram (magot_fq_time)."""
+        ms = np.zeros(4, np.float64)
+        n = ctypes.c_uint64()
+        check(_lib.lib().magot_fq_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                       ctypes.byref(n)), 'magot_fq_time')
+        out = dict(zip(('line_index', 'lengths', 'reduce', 'copy'), ms.tolist()))
+        out['chunk_bytes'] = n.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_fq_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's
@@ -1507,4 +1589,4 @@ __all__ = ['DeviceGenome', 'ExtractionPlan', 'revcomp_batch', 'translate_batch',
            'OUT_PEP', 'MagotError', 'GffPlan', 'orf6_batch', 'Orf6Plan', 'fasta_read',
            'FastaGenome', 'PartitionedGenome', 'device_genome', 'extract_records', 'plan_parts',
            'copy_segments', 'orf6_sizes', 'OrfCalls', 'ORFCALL_TILE', 'ORF_TABLE_DTYPE',
-           'GenomeTrack', 'TrackWindows', 'interval_pieces']
+           'GenomeTrack', 'TrackWindows', 'interval_pieces', 'ReadLengths']

@@ -17,6 +17,7 @@
     python -m magot_amd.genome_tools at_content_from_fasta <fasta> [native=False]
     python -m magot_amd.genome_tools depth_from_gff <depth.txt> <gff> [features=['CDS','upstream']]
            [stream_length=1000] [order=py2|insertion] [native=False]
+    python -m magot_amd.genome_tools fqstats <reads.fastq> [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -1164,7 +1165,92 @@ def depth_from_gff(depth_file, gff, features="['CDS','intron','upstream','downst
 depth_from_gff.last_path = None
 
 
+def _fqstats_host(fastq_location):
+    """fqstats' figures from a line loop on the host, as ReadLengths.stats()
+    gives them."""
+    lengths = []
+    with open(fastq_location, 'rb') as fh:
+        for k, line in enumerate(fh):  # binary: a line ends at LF only
+            if k % 4 == 1:
+                lengths.append(len(line) - 1)
+    reads, bases = len(lengths), sum(lengths)
+    mean = bases // reads  # no reads: ZeroDivisionError, as there
+    lengths.sort(reverse=True)
+    marks = [None, None, None]
+    running = 0
+    for length in lengths:
+        running += length
+        for k, mark in enumerate((bases // 4, bases // 2, bases * 3 // 4)):
+            if marks[k] is None and running > mark:
+                marks[k] = length
+    return {'reads': reads, 'bases': bases, 'mean': mean, 'median': lengths[reads // 2],
+            'reads25': lengths[reads // 4], 'reads75': lengths[reads * 3 // 4],
+            'n25': marks[0], 'n50': marks[1], 'n75': marks[2]}
+
+
+def _fqstats_native(fastq_location, clock):
+    import mmap
+    with open(fastq_location, 'rb') as fh:
+        try:
+            size = os.fstat(fh.fileno()).st_size
+            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if size else b''
+        except (ValueError, OSError):  # not a file that maps: a pipe, a device
+            data = fh.read()
+    clock.lap('open')
+    lengths = engine.ReadLengths.parse(data)
+    try:
+        clock.lap('kernels')
+        return lengths.stats()
+    finally:
+        lengths.close()
+
+
+def fqstats(fastq_location, native='True'):
+    """genome_tools.py:85-124: read count, total bases, median and mean
+    length, the lengths a quarter and three quarters of the way down the
+    descending list, and N25 / N50 / N75 of a FASTQ file.  Every fourth line
+    from the second is a read, whatever it holds; lines end at LF only and a
+    read's length is its line without the LF (a CR counts; a last line without
+    LF counts one short, as there).  Python 2 integers: every division
+    floors.  An N-value never set (no bases at all) prints ``False``; a file
+    without reads raises ZeroDivisionError before anything is printed; a
+    missing file raises OSError.
+
+    On the device (engine.ReadLengths: the file streamed in chunks cut
+    anywhere, a line index from LF counts, the lengths as a histogram and the
+    figures reduced from it) for every file; ``native=False`` takes a line
+    loop on the host instead, for that switch and for timing.
+    ``fqstats.last_path`` names the path the last call took."""
+    clock = _Clock()
+    if native == 'True':
+        fqstats.last_path = ('fqstats', 'native', None)
+        s = _fqstats_native(fastq_location, clock)
+        if not s['reads']:
+            raise ZeroDivisionError('integer division or modulo by zero')
+        s['mean'] = s['bases'] // s['reads']
+    else:
+        fqstats.last_path = ('fqstats', 'host', "native != 'True'")
+        s = _fqstats_host(fastq_location)
+    n_value = lambda v: 'False' if v is None else str(v)  # noqa: E731
+    _write(''.join([
+        '%d reads\n' % s['reads'],
+        'total basepairs=%d\n' % s['bases'],
+        'median length=%d\n' % s['median'],
+        'mean length=%d\n' % s['mean'],
+        '25%% of reads >%d\n' % s['reads25'],
+        '75%% of reads >%d\n' % s['reads75'],
+        'n25=' + n_value(s['n25']) + '\n',
+        'n50=' + n_value(s['n50']) + '\n',
+        'n75=' + n_value(s['n75']) + '\n']))
+    clock.lap('write')
+    clock.emit()
+
+
+fqstats.last_path = None
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
+         'fqstats': fqstats,
          'extract_upstream_downstream': extract_upstream_downstream,
          'coords2fasta': coords2fasta,
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,

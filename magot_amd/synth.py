@@ -347,3 +347,57 @@ def write_depth_table(path, names, lengths, seed=SEED_BASE, rows=1 << 22):
                 lines += m
                 size += out.size
     return lines, size
+
+
+def fastq_read_lengths(shape, total_bytes, dense=1 << 20, seed=SEED_BASE):
+    """Read lengths (int64) of a synthetic FASTQ of about ``total_bytes``
+    (write_fastq's records: two bytes per base and seven per read).  'short':
+    every read 150 bases.  'long': log-normal lengths (median 8000, sigma 1),
+    three of them replaced by lengths above ``dense``."""
+    if shape == 'short':
+        return np.full(max(1, total_bytes // 307), 150, dtype=np.int64)
+    if shape != 'long':
+        raise ValueError(shape)
+    rng = np.random.default_rng(seed)
+    mean = 8000.0 * np.exp(0.5)  # of the log-normal
+    n = max(4, int(total_bytes / (2 * mean + 7)))
+    lengths = np.maximum(1, rng.lognormal(np.log(8000.0), 1.0, n)).astype(np.int64)
+    lengths = np.minimum(lengths, dense - 1)
+    lengths[rng.choice(n, 3, replace=False)] = [dense, dense + 12345, 3 * dense + 1]
+    return lengths
+
+
+def write_fastq(path, lengths, seed=SEED_BASE, batch_bytes=1 << 27):
+    """A FASTQ of four-line records (``@r``, the bases, ``+``, one 'I' per
+    base) with the given read lengths, written ``batch_bytes`` at a time
+    without a Python loop over reads; the bases repeat a seeded 1 MB pattern
+    (nothing reads them).  Returns (reads, bytes)."""
+    rng = np.random.default_rng(seed)
+    pattern = _ASCII[rng.integers(0, 4, 1 << 20)]
+    lengths = np.asarray(lengths, dtype=np.int64)
+    size = 2 * lengths + 7
+    ends = np.cumsum(size)
+    total = 0
+    with open(path, 'wb') as fh:
+        lo = 0
+        while lo < len(lengths):
+            base = int(ends[lo - 1]) if lo else 0
+            hi = max(lo + 1, int(np.searchsorted(ends, base + batch_bytes, side='right')))
+            n = int(ends[hi - 1]) - base
+            out = np.resize(pattern, n)
+            s = ends[lo:hi] - size[lo:hi] - base  # each record's first byte
+            ln = lengths[lo:hi]
+            out[s] = 64  # '@'
+            out[s + 1] = 114  # 'r'
+            out[s + 4 + ln] = 43  # '+'
+            for at in (s + 2, s + 3 + ln, s + 5 + ln, s + 6 + 2 * ln):
+                out[at] = 10
+            mark = np.zeros(n + 1, dtype=np.int8)  # +1 / -1 at a quality line's ends
+            np.add.at(mark, s + 6 + ln, 1)
+            np.add.at(mark, s + 6 + 2 * ln, -1)
+            quality = np.cumsum(mark[:n], dtype=np.int32) > 0
+            out[quality] = 73  # 'I'
+            fh.write(out.data)
+            total += n
+            lo = hi
+    return len(lengths), total
