@@ -1,0 +1,256 @@
+// What more than one unit of the C ABI (abi*.hip) needs, each defined once: the
+// handles whose insides another unit reads, and the host helpers the units
+// share.  Header only, as hostutil.h; included by the ABI units alone.
+#pragma once
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "common.h"
+
+struct magot_ctx {
+  int device = 0;
+  int n_cu = 0;
+  int blocks_per_cu = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t mark0 = nullptr, mark1 = nullptr;  // magot_ctx_mark
+  // pinned staging ring for genome uploads (allocated on first use); loads on
+  // one context from several host threads take turns on it
+  uint8_t* pin[2] = {nullptr, nullptr};
+  hipEvent_t pin_ev[2] = {nullptr, nullptr};
+  std::mutex pin_mu;
+};
+
+struct magot_genome {
+  magot_ctx* ctx = nullptr;
+  void* arena = nullptr;
+  uint64_t arena_bytes = 0;
+  bool owns_arena = true;  // false: caller memory (magot_genome_attach)
+  uint32_t* nib = nullptr;  // forward then reverse-strand nibble plane (ExtractArgs::span)
+  uint64_t span = 0;
+  magot::ExcRun* runs = nullptr;
+  uint32_t* dir = nullptr;
+  std::vector<uint64_t> contig_base, contig_len;
+  std::vector<std::string> names;  // contig names (magot_genome_load_fasta)
+  std::vector<magot::ExcRun> host_runs;   // host copies for per-interval exception flags
+  std::vector<uint32_t> host_dir;
+  uint64_t extent = 0, total_bases = 0, n_runs = 0;
+};
+
+struct magot_plan {
+  magot_ctx* ctx = nullptr;
+  const magot_genome* g = nullptr;
+  void* arena = nullptr;       // tables (intervals, records, tiles, layout)
+  uint64_t arena_bytes = 0;
+  void* out_arena = nullptr;   // output buffers (nucleotides, residues)
+  uint64_t out_bytes = 0;
+  magot::ExtractArgs args{};
+  std::vector<uint64_t> nuc_off, pep_off;  // host copies, n_tx+1 (record order)
+  // MAGOT_OUT_GENOME_ORDER: records laid out in genome order; each record's
+  // place in the output buffers (record order; device copies for reassembly)
+  bool genome_order = false;
+  std::vector<uint64_t> lay_nuc, lay_pep;
+  const uint64_t* d_lay_nuc = nullptr;  // T
+  const uint64_t* d_lay_pep = nullptr;  // T
+  const uint64_t* d_nuc_off = nullptr;  // T+1
+  const uint64_t* d_pep_off = nullptr;  // T+1
+  uint64_t n_exons = 0, n_tx = 0;
+  uint64_t n_ex_c = 0;  // compacted (non-empty) intervals
+  // the interval table of a record-order plan (n_ex_c starts with flag bits,
+  // n_ex_c + 1 output offsets), for magot_plan_orf6: the device holds only
+  // the packed tile blocks
+  std::unique_ptr<uint64_t[]> host_ex_g, host_ex_out;
+  bool executed = false;
+};
+
+// Six frames over an extraction plan: the records are gathered from the
+// genome plane through the plan's intervals inside the kernel (fused; the
+// plan's nucleotide output is not read).
+struct magot_orf6 {
+  magot_ctx* ctx = nullptr;
+  magot_plan* plan = nullptr;
+  void* arena = nullptr;
+  magot::Orf6Args args{};
+  uint8_t* out = nullptr;
+  uint64_t n_rec = 0, total = 0;
+  std::vector<uint64_t> host_soff;
+  bool executed = false;  // the streams are in HBM (magot_orfcall_create asks)
+  void launch(hipStream_t s) const { magot::launch_orf6(args, true, s); }
+};
+
+// internal to the library: what is not inlined stays out of its exported symbols
+#pragma GCC visibility push(hidden)
+
+namespace magot {
+
+// Sub-allocate 256-byte aligned slices of one device allocation.
+struct Carve {
+  uint64_t used = 0;
+  template <class T>
+  uint64_t take(uint64_t count) {
+    uint64_t at = used;
+    used += (count * sizeof(T) + 255) & ~255ull;
+    return at;
+  }
+};
+
+inline int bind(magot_ctx* ctx) {
+  if (!ctx) {
+    set_error("null context");
+    return MAGOT_ERR_ARG;
+  }
+  MAGOT_HIP_TRY(hipSetDevice(ctx->device));
+  return MAGOT_OK;
+}
+
+constexpr uint64_t kPinRing = 64ull << 20;  // each of the context's two pinned staging buffers
+
+inline int ensure_pin_ring(magot_ctx* ctx) {  // callers hold ctx->pin_mu
+  for (int k = 0; k < 2; ++k)
+    if (!ctx->pin[k]) {
+      MAGOT_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ctx->pin[k]), kPinRing,
+                                  hipHostMallocDefault));
+      MAGOT_HIP_TRY(hipEventCreateWithFlags(&ctx->pin_ev[k], hipEventDisableTiming));
+    }
+  return MAGOT_OK;
+}
+
+// RAII device scratch
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// A device allocation made on another thread while the caller goes on
+// (hipMalloc of C3's 0.8 GB of outputs takes ~10 ms).  It is joined, and
+// freed unless taken, when it goes out of scope.
+struct AsyncAlloc {
+  void* mem = nullptr;
+  hipError_t err = hipSuccess;
+  std::thread th;
+  AsyncAlloc(int device, uint64_t bytes)
+      : th([this, device, bytes]() {
+          err = hipSetDevice(device);
+          if (err == hipSuccess) err = hipMalloc(&mem, bytes);
+        }) {}
+  hipError_t take(void** out) {  // the caller owns *out now
+    th.join();
+    *out = mem;
+    mem = nullptr;
+    return err;
+  }
+  ~AsyncAlloc() {
+    if (th.joinable()) th.join();
+    if (mem) (void)hipFree(mem);
+  }
+};
+
+// The context bound and h a handle made on it; `noun` is what the message
+// calls the handle.
+template <class H>
+int handle_of(magot_ctx* ctx, const H* h, const char* who, const char* noun) {
+  if (int rc = bind(ctx)) return rc;
+  if (!h || h->ctx != ctx) {
+    set_error(std::string(who) + ": null " + noun + ", or a " + noun + " of another context");
+    return MAGOT_ERR_ARG;
+  }
+  return MAGOT_OK;
+}
+
+// launch() (it returns a hipError_t) timed on the context stream between the
+// context's event pair; its milliseconds are added to *total_ms.
+template <class F>
+int time_pass(magot_ctx* ctx, double* total_ms, F launch) {
+  MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  MAGOT_HIP_TRY(launch());
+  MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  MAGOT_HIP_TRY(hipEventSynchronize(ctx->ev1));
+  float ms = 0.f;
+  MAGOT_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *total_ms += ms;
+  return MAGOT_OK;
+}
+
+// Text parsed on the device in chunks (abi_text.hip): chunk k is staged in
+// pinned slot k & 1 and copied to device slot k & 1 on a stream of its own,
+// while the context stream still parses the chunk before it.  Where to cut
+// the text is the caller's.
+constexpr uint64_t kTextChunkDefault = 64ull << 20;
+constexpr uint64_t kTextChunkMin = 1024, kTextChunkMax = 1ull << 30;
+
+inline uint64_t text_chunk_bytes(uint64_t asked, uint64_t len) {
+  const uint64_t chunk = std::min(std::max(asked ? asked : kTextChunkDefault, kTextChunkMin),
+                                  kTextChunkMax);
+  return std::min(chunk, std::max<uint64_t>(len, 1));
+}
+
+struct TextStream {
+  uint8_t* dev[2] = {nullptr, nullptr};
+  uint8_t* pin[2] = {nullptr, nullptr};
+  hipEvent_t up_done[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
+  hipStream_t copy = nullptr;
+  // the last chunk, still in dev[last_slot] (the timed passes)
+  int last_slot = 0, last_in = 0;
+  uint64_t last_len = 0, last_off = 0;
+
+  int open(uint64_t chunk, int n_slots) {
+    MAGOT_HIP_TRY(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+    for (int s = 0; s < n_slots; ++s) {
+      MAGOT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev[s]), chunk + 256));
+      MAGOT_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pin[s]), chunk, hipHostMallocDefault));
+      MAGOT_HIP_TRY(hipEventCreateWithFlags(&up_done[s], hipEventDisableTiming));
+      MAGOT_HIP_TRY(hipEventCreateWithFlags(&done[s], hipEventDisableTiming));
+    }
+    return MAGOT_OK;
+  }
+  // Chunk k, the n bytes at src that start at byte `off` of the text, to its
+  // slot; the context stream waits for it.
+  int push(magot_ctx* ctx, const char* src, uint64_t n, uint64_t off, uint64_t k) {
+    const int s = (int)(k & 1);
+    if (k >= 2) MAGOT_HIP_TRY(hipEventSynchronize(up_done[s]));  // pin[s] was read
+    std::memcpy(pin[s], src, n);
+    if (k >= 2) MAGOT_HIP_TRY(hipStreamWaitEvent(copy, done[s], 0));  // dev[s] was parsed
+    MAGOT_HIP_TRY(hipMemcpyAsync(dev[s], pin[s], n, hipMemcpyHostToDevice, copy));
+    MAGOT_HIP_TRY(hipEventRecord(up_done[s], copy));
+    MAGOT_HIP_TRY(hipStreamWaitEvent(ctx->stream, up_done[s], 0));
+    last_slot = s;
+    last_in = (int)(k & 1);
+    last_len = n;
+    last_off = off;
+    return MAGOT_OK;
+  }
+  int passed(magot_ctx* ctx, int s) {  // the passes over slot s are on the context stream
+    MAGOT_HIP_TRY(hipEventRecord(done[s], ctx->stream));
+    return MAGOT_OK;
+  }
+  void release_pinned() {
+    for (int s = 0; s < 2; ++s) {
+      if (pin[s]) (void)hipHostFree(pin[s]);
+      pin[s] = nullptr;
+    }
+  }
+  void close() {  // the owner's device is current
+    for (int s = 0; s < 2; ++s) {
+      if (pin[s]) (void)hipHostFree(pin[s]);
+      if (dev[s]) (void)hipFree(dev[s]);
+      pin[s] = dev[s] = nullptr;
+    }
+    for (int s = 0; s < 2; ++s) {
+      if (up_done[s]) (void)hipEventDestroy(up_done[s]);
+      if (done[s]) (void)hipEventDestroy(done[s]);
+    }
+    if (copy) (void)hipStreamDestroy(copy);
+  }
+};
+
+}  // namespace magot
+
+#pragma GCC visibility pop

@@ -762,7 +762,7 @@ void set_error(const std::string& msg);
 
 }  // namespace magot
 
-// magot_mask_plan's result (maskplan.cpp), read by magot_mask_create (abi.hip)
+// magot_mask_plan's result (maskplan.cpp), read by magot_mask_create (abi_mask.hip)
 struct magot_maskplan {
   uint32_t flags = 0;
   std::vector<uint64_t> contig_lens;

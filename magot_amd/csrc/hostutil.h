@@ -1,6 +1,6 @@
 // Host-side helpers shared by the translation units that plan on the CPU
-// (abi.hip, tileplan.cpp): lap timing, the thread count, range-parallel loops
-// and uninitialised arrays.  No HIP here.
+// (the abi*.hip units, tileplan.cpp): lap timing, the thread count,
+// range-parallel loops and uninitialised arrays.  No HIP here.
 #pragma once
 
 #include <algorithm>

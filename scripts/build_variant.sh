@@ -9,12 +9,12 @@ D=magot_amd/_build/var_$NAME; mkdir -p $D
 objs=""
 for f in magot_amd/_build/*.o; do
   b=$(basename $f)
-  if [ $b = extract.hip.o ] || [ $b = seqops.hip.o ] || [ $b = abi.hip.o ]; then
+  case $b in extract.hip.o|seqops.hip.o|abi*.hip.o)
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -Wall -Wno-unused-function --offload-arch=gfx950 -Iinclude "$@" -x hip -c magot_amd/csrc/${b%.o} -o $D/$b
-    objs="$objs $D/$b"
-  else
-    objs="$objs $f"
-  fi
+    objs="$objs $D/$b" ;;
+  *)
+    objs="$objs $f" ;;
+  esac
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o scripts/lib_$NAME.so $objs -lpthread
 echo scripts/lib_$NAME.so

@@ -299,6 +299,12 @@ def test_sums_equal_numpy(world):
     assert set(ms) == {'line_index', 'parse', 'directory', 'sums', 'chunk_bytes'}
     assert ms['chunk_bytes'] == len(world.text) and ms['parse'] > 0
     assert (t.values(big) == world.arrays[big]).all()  # the timed passes change nothing
+    for chunk, slot in ((SMALL, 0), (2 * MIDDLE, 1)):  # the last of many chunks, in either slot
+        starts = cuts(world.text, chunk)
+        assert len(starts) > 2 and (len(starts) - 1) % 2 == slot
+        many = world.track(chunk)
+        assert many.time(1)['chunk_bytes'] == len(world.text) - starts[-1]
+        assert (many.values(big) == world.arrays[big]).all()
 
 
 # -- the tool ---------------------------------------------------------------

@@ -185,6 +185,13 @@ def test_chunk_sizes_agree_and_timing_changes_nothing(world):
     assert ms['chunk_bytes'] == len(world.text) and ms['lengths'] > 0 and ms['reduce'] > 0
     assert small.time(1)['chunk_bytes'] == (len(world.text) - 1) % SMALL + 1
     assert whole.stats() == before
+    # small's last chunk went through slot 0; one that went through slot 1
+    last = len(world.text) - 1
+    assert last // SMALL % 2 == 0 and last // (2 * MIDDLE) % 2 == 1
+    even = engine.ReadLengths.parse(world.text, chunk_bytes=2 * MIDDLE)
+    assert even.time(1)['chunk_bytes'] == (len(world.text) - 1) % (2 * MIDDLE) + 1
+    assert even.stats() == before
+    even.close()
     again = engine.ReadLengths.parse(world.text, chunk_bytes=MIDDLE)
     assert again.stats() == before
     again.close()
