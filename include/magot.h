@@ -865,6 +865,69 @@ int magot_fq_histogram(magot_ctx* ctx, magot_fq* t, int64_t* lengths, uint64_t* 
 int magot_fq_time(magot_ctx* ctx, magot_fq* t, int iters, double* ms4, uint64_t* chunk_len);
 void magot_fq_destroy(magot_fq* t);
 
+/* ---- interval joins: purge_overlaps, annotation_overlap ----
+ * (genome_tools.py:548-568, annotation_funcs.py:13-30).  An index over a set
+ * of intervals (dense seqid, p0, p1), the integers as parsed: nothing is
+ * sorted by the caller, ordered or clipped; reversed and negative coordinates
+ * are legal.  Each query (seqid, c0, c1) is answered from sorted tables by
+ * binary search; a seqid not below n_seq (MAGOT_OVERLAP_NO_SEQ) has no
+ * partner.
+ *   magot_overlap_coord_range  the coordinates an index holds, [-2^39, 2^39);
+ *       one outside is MAGOT_ERR_RANGE before any launch.
+ *   magot_overlap_lane_scan    overlap's range scan: a query with more
+ *       intervals starting inside it is scanned by a whole wave.
+ *   magot_overlap_create   uploads the intervals and builds the tables on the
+ *       context stream (n_seq below 2^24).
+ *   magot_overlap_purge    drop[i] = 1 when any interval p of query i's seqid
+ *       has p0 < c0 < p1, p0 < c1 < p1 or c0 < p0 < c1 (all strict).
+ *   magot_overlap_counts   counts[i] = the intervals p of query i's seqid with
+ *       p0 <= q0 <= p1 or p0 <= q1 <= p1 (closed).
+ *   magot_overlap_time     mean device ms over `iters` runs of: the key pass,
+ *       the five sorts, the segment bounds, the purge pass and the overlap
+ *       passes over the last query set given (0 when none was), and a device
+ *       copy of the sorted tables (*copy_bytes), in ms6[0..5].
+ * Host planner of purge_overlaps.  magot_overlap_plan scans both GFF texts
+ * (lines end after '\n' only) into one row per line: whether it has more than
+ * 6 tabs, and then the dense seqid of its first column in the first file's
+ * dictionary (MAGOT_OVERLAP_NO_SEQ: second file only, not there; its integers
+ * are then not read), int(x[3]), int(x[4]) as Python 2 reads them, the line's
+ * offset and its length with the LF.  MAGOT_ERR_UNSUPPORTED with *reason set
+ * where only the reference's sequential run is exact.
+ *   magot_ovplan_table     file `which` (0, 1): the columns in place (valid
+ *       until destroy); any pointer may be NULL.
+ *   magot_ovplan_render    the second file's lines with drop[line] == 0, each
+ *       without its last byte and with '\n' instead, in file order: *bytes
+ *       always; the text when out is not NULL (cap >= *bytes).
+ */
+#define MAGOT_OVERLAP_NO_SEQ 0xffffffffu
+enum {
+  MAGOT_OVERLAP_BAD_INT_FIRST = 1,  /* ValueError before anything is printed */
+  MAGOT_OVERLAP_BAD_INT_SECOND = 2, /* ValueError after part of the output */
+  MAGOT_OVERLAP_COORD_RANGE = 3,    /* a coordinate outside magot_overlap_coord_range */
+  MAGOT_OVERLAP_SEQIDS = 4          /* 2^24 - 1 seqids or more */
+};
+typedef struct magot_overlap magot_overlap;
+typedef struct magot_ovplan magot_ovplan;
+void magot_overlap_coord_range(int64_t* lo, int64_t* hi);
+uint32_t magot_overlap_lane_scan(void);
+int magot_overlap_create(magot_ctx* ctx, const uint32_t* seq, const int64_t* p0, const int64_t* p1,
+                         uint64_t n, uint32_t n_seq, magot_overlap** out);
+int magot_overlap_purge(magot_ctx* ctx, magot_overlap* h, const uint32_t* seq, const int64_t* c0,
+                        const int64_t* c1, uint64_t n, uint8_t* drop);
+int magot_overlap_counts(magot_ctx* ctx, magot_overlap* h, const uint32_t* seq, const int64_t* q0,
+                         const int64_t* q1, uint64_t n, int64_t* counts);
+int magot_overlap_time(magot_ctx* ctx, magot_overlap* h, int iters, double* ms6,
+                       uint64_t* copy_bytes);
+void magot_overlap_destroy(magot_overlap* h);
+int magot_overlap_plan(const char* gff1, uint64_t len1, const char* gff2, uint64_t len2,
+                       magot_ovplan** out, uint32_t* reason);
+int magot_ovplan_table(const magot_ovplan* p, int which, uint64_t* n_lines, uint32_t* n_seq,
+                       const uint8_t** flag, const uint32_t** seq, const int64_t** c0,
+                       const int64_t** c1, const uint64_t** off, const uint64_t** len);
+int magot_ovplan_render(const magot_ovplan* p, const char* gff2, uint64_t len2,
+                        const uint8_t* drop, uint8_t* out, uint64_t cap, uint64_t* bytes);
+void magot_ovplan_destroy(magot_ovplan* p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,9 @@ EXPORTS = (
     'magot_depth_sums', 'magot_depth_time', 'magot_depth_destroy',
     'magot_fq_dense', 'magot_fq_parse', 'magot_fq_stats', 'magot_fq_histogram', 'magot_fq_time',
     'magot_fq_destroy',
+    'magot_overlap_coord_range', 'magot_overlap_lane_scan', 'magot_overlap_create',
+    'magot_overlap_purge', 'magot_overlap_counts', 'magot_overlap_time', 'magot_overlap_destroy',
+    'magot_overlap_plan', 'magot_ovplan_table', 'magot_ovplan_render', 'magot_ovplan_destroy',
 )
 
 ERR_ARG = -1
@@ -90,6 +93,10 @@ DEPTH_REASONS = (None, 'empty line', 'leading blank', 'byte outside the grammar'
                  'not a number', 'number out of range', 'position out of sequence',
                  'repeated contig', 'line longer than a chunk', 'more than 2^31-1 lines',
                  'too many runs')
+OVERLAP_NO_SEQ = 0xffffffff
+# magot_overlap_plan's reasons (MAGOT_OVERLAP_*), by code
+OVERLAP_REASONS = (None, 'bad integer in the first file', 'bad integer in the second file',
+                   'coordinate beyond the key range', 'too many seqids')
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -281,6 +288,23 @@ def _declare(lib):
         'magot_fq_histogram': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _u64p]),
         'magot_fq_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p]),
         'magot_fq_destroy': (None, [_vp]),
+        'magot_overlap_coord_range': (None, [_i64p, _i64p]),
+        'magot_overlap_lane_scan': (ctypes.c_uint32, []),
+        'magot_overlap_create': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64,
+                                                ctypes.c_uint32, ctypes.POINTER(_vp)]),
+        'magot_overlap_purge': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
+        'magot_overlap_counts': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
+        'magot_overlap_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p]),
+        'magot_overlap_destroy': (None, [_vp]),
+        'magot_overlap_plan': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, ctypes.c_uint64,
+                                              ctypes.POINTER(_vp),
+                                              ctypes.POINTER(ctypes.c_uint32)]),
+        'magot_ovplan_table': (ctypes.c_int, [_vp, ctypes.c_int, _u64p,
+                                              ctypes.POINTER(ctypes.c_uint32)] +
+                               [ctypes.POINTER(_vp)] * 6),
+        'magot_ovplan_render': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp,
+                                               ctypes.c_uint64, _u64p]),
+        'magot_ovplan_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -18,9 +18,10 @@ LIB = os.path.join(HERE, 'libmagot.so')
 ARCH = os.environ.get('MAGOT_OFFLOAD_ARCH', 'gfx950')
 
 SOURCES = ['abi.hip', 'abi_genome.hip', 'abi_plan.hip', 'abi_seq.hip', 'abi_orf.hip', 'abi_mask.hip',
-           'abi_track.hip', 'abi_text.hip', 'extract.hip', 'seqops.hip', 'pack.cpp', 'gffplan.cpp',
-           'fasta.cpp', 'render.hip', 'devpack.hip', 'wire.hip', 'tileblocks.cpp', 'tileplan.cpp',
-           'orfcall.hip', 'maskplan.cpp', 'maskgen.hip', 'track.hip', 'depth.hip', 'fastq.hip']
+           'abi_track.hip', 'abi_text.hip', 'abi_overlap.hip', 'extract.hip', 'seqops.hip', 'pack.cpp',
+           'gffplan.cpp', 'fasta.cpp', 'render.hip', 'devpack.hip', 'wire.hip', 'tileblocks.cpp',
+           'tileplan.cpp', 'orfcall.hip', 'maskplan.cpp', 'maskgen.hip', 'track.hip', 'depth.hip',
+           'fastq.hip', 'overlap.hip', 'overlapplan.cpp']
 HEADERS = ['common.h', 'hostutil.h', 'wavecopy.h', 'abi_internal.h',
            os.path.join('..', '..', 'include', 'magot.h')]
 

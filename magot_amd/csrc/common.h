@@ -751,6 +751,64 @@ hipError_t launch_fq_sort(const int64_t* in, int64_t* out, uint64_t n, void* tmp
 hipError_t launch_fq_reduce(const FqReduceArgs& a, void* scan_tmp, size_t scan_bytes,
                             hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Interval joins: purge_overlaps, annotation_overlap (overlap.hip;
+// magot_overlap_*)
+// ---------------------------------------------------------------------------
+// Composite key of one interval end: dense seqid above the coordinate biased
+// to unsigned, so one sorted table holds every seqid's ends as one segment
+// each.  The all-ones key (seqid 2^24 - 1) marks an interval left out of a
+// table and sorts behind every segment.
+constexpr int kOvCoordBits = 40;
+constexpr int64_t kOvCoordMin = -(1ll << (kOvCoordBits - 1));
+constexpr int64_t kOvCoordMax = (1ll << (kOvCoordBits - 1)) - 1;
+constexpr uint32_t kOvMaxSeq = (1u << (64 - kOvCoordBits)) - 1;  // seqids 0 .. kOvMaxSeq - 1
+constexpr uint32_t kOvNoSeq = 0xffffffffu;  // a query on a seqid the index does not hold
+// overlap's range scan: a query with at most kOvLaneScan intervals starting
+// inside it is scanned by its own lane, a longer one by a whole wave
+constexpr uint32_t kOvLaneScan = 64;
+__host__ __device__ inline uint64_t ov_key(uint32_t seq, int64_t x) {
+  return ((uint64_t)seq << kOvCoordBits) | (uint64_t)(x - kOvCoordMin);
+}
+// The three tables of an index of n intervals, each of n keys with the left
+// out ones behind, and each table's segment bounds (n_seq + 1 entries):
+//   in    p0 < p1   starts and ends           purge's first two tests
+//   all   every     starts                    purge's third test
+//   cl    p0 <= p1  starts with their ends, and ends   overlap
+struct OvIndex {
+  uint64_t n;
+  uint32_t n_seq;
+  const uint64_t *in_s, *in_e, *all_s, *cl_s, *cl_e;
+  const int64_t* cl_v;  // the end of the interval whose start is cl_s[i]
+  const uint64_t *seg_in, *seg_all, *seg_cl;
+};
+struct OvBuildArgs {
+  uint64_t n;
+  uint32_t n_seq;
+  const uint32_t* seq;     // n, each < n_seq
+  const int64_t *p0, *p1;  // n, each in [kOvCoordMin, kOvCoordMax]
+  // unsorted keys (5 n) and ends (n), then the sorted tables of OvIndex
+  uint64_t* raw;
+  int64_t* raw_v;
+  uint64_t *in_s, *in_e, *all_s, *cl_s, *cl_e;
+  int64_t* cl_v;
+  uint64_t *seg_in, *seg_all, *seg_cl;
+};
+struct OvQuery {
+  uint64_t n;
+  const uint32_t* seq;     // n; kOvNoSeq or >= n_seq: no partner
+  const int64_t *c0, *c1;  // n, each in [kOvCoordMin, kOvCoordMax]
+};
+size_t ov_sort_bytes(uint64_t n);
+hipError_t launch_ov_keys(const OvBuildArgs& a, hipStream_t s);
+hipError_t launch_ov_sort(const OvBuildArgs& a, void* tmp, size_t bytes, hipStream_t s);
+hipError_t launch_ov_segments(const OvBuildArgs& a, hipStream_t s);
+hipError_t launch_ov_purge(const OvIndex& ix, const OvQuery& q, uint8_t* drop, hipStream_t s);
+// counts: n; long_list: n; n_long: one counter, zeroed here
+hipError_t launch_ov_overlap(const OvIndex& ix, const OvQuery& q, int64_t* counts,
+                             uint32_t* long_list, unsigned long long* n_long, int n_cu,
+                             hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);
@@ -767,6 +825,18 @@ struct magot_maskplan {
   uint32_t flags = 0;
   std::vector<uint64_t> contig_lens;
   std::vector<magot_mask_interval> rows;  // pieces of at most kMaskPiece bases, in GFF order
+};
+
+// magot_overlap_plan's result (overlapplan.cpp): one row per line of each file
+struct magot_ovtable {
+  std::vector<uint8_t> flag;   // 1: more than 6 tabs
+  std::vector<uint32_t> seq;   // dense seqid of the first file; kOvNoSeq: unknown, or no flag
+  std::vector<int64_t> c0, c1; // int(x[3]), int(x[4]); 0 where they were not read
+  std::vector<uint64_t> off, len;  // the line's place in its buffer, its LF included
+};
+struct magot_ovplan {
+  magot_ovtable t[2];
+  uint32_t n_seq = 0;
 };
 
 #define MAGOT_HIP_TRY(expr)                                                     \

@@ -1512,6 +1512,167 @@ class ReadLengths(object):
             pass
 
 
+def _query_columns(seq, c0, c1):
+    """(uint32 seqids, int64 c0, int64 c1) of equal length for the ABI; a
+    seqid below zero becomes OVERLAP_NO_SEQ (no partner)."""
+    seq = np.asarray(seq, dtype=np.int64).reshape(-1)
+    seq = np.where((seq < 0) | (seq >= _lib.OVERLAP_NO_SEQ), _lib.OVERLAP_NO_SEQ, seq)
+    seq = np.ascontiguousarray(seq.astype(np.uint32))
+    c0 = np.ascontiguousarray(np.asarray(c0, dtype=np.int64).reshape(-1))
+    c1 = np.ascontiguousarray(np.asarray(c1, dtype=np.int64).reshape(-1))
+    if not len(seq) == len(c0) == len(c1):
+        raise ValueError('seq, start and end must have one entry per interval')
+    return seq, c0, c1
+
+
+class IntervalIndex(object):
+    """One set of intervals (dense seqid, start, end) sorted on the device for
+    the reference's two interval joins (magot_overlap_*; genome_tools.py:548-568,
+    annotation_funcs.py:13-30).  The integers are taken as they are: reversed
+    and negative coordinates are legal, nothing is clipped; they must lie in
+    ``coord_range()``.  Queries name their seqid by the same dense numbers; one
+    the index does not hold (negative, or beyond the largest) has no partner."""
+
+    PASSES = ('keys', 'sort', 'segments', 'purge', 'overlap', 'copy')
+
+    def __init__(self, seq, start, end, n_seq=None, ctx=None):
+        self.ctx = ctx or _lib.default_context()
+        self.handle = None
+        seq = np.asarray(seq, dtype=np.int64).reshape(-1)
+        if len(seq) and (seq.min() < 0 or seq.max() >= _lib.OVERLAP_NO_SEQ):
+            raise ValueError('seqids of the index must be dense numbers from 0')
+        seq, p0, p1 = _query_columns(seq, start, end)
+        self.n = len(seq)
+        self.n_seq = int(n_seq) if n_seq is not None else (int(seq.max()) + 1 if self.n else 0)
+        h = ctypes.c_void_p()
+        check(_lib.lib().magot_overlap_create(self.ctx.handle, ptr(seq), ptr(p0), ptr(p1), self.n,
+                                              self.n_seq, ctypes.byref(h)), 'magot_overlap_create')
+        self.handle = h
+
+    @staticmethod
+    def coord_range():
+        """(lowest, highest) coordinate an index or a query may hold."""
+        lo, hi = ctypes.c_int64(), ctypes.c_int64()
+        _lib.lib().magot_overlap_coord_range(ctypes.byref(lo), ctypes.byref(hi))
+        return lo.value, hi.value
+
+    @staticmethod
+    def lane_scan():
+        """overlap_counts' range scan: a query with more intervals starting
+        inside it than this is scanned by a whole wave, not by its lane."""
+        return int(_lib.lib().magot_overlap_lane_scan())
+
+    def purge_flags(self, seq, c0, c1):
+        """purge_overlaps' test per query, a bool array: True where an interval
+        p of the query's seqid has p0 < c0 < p1, p0 < c1 < p1 or c0 < p0 < c1."""
+        seq, c0, c1 = _query_columns(seq, c0, c1)
+        out = np.zeros(max(len(seq), 1), np.uint8)
+        check(_lib.lib().magot_overlap_purge(self.ctx.handle, self.handle, ptr(seq), ptr(c0),
+                                             ptr(c1), len(seq), ptr(out)), 'magot_overlap_purge')
+        return out[:len(seq)].astype(bool)
+
+    def overlap_counts(self, seq, q0, q1):
+        """annotation_overlap's partners per query, int64: the intervals p of
+        the query's seqid with p0 <= q0 <= p1 or p0 <= q1 <= p1."""
+        seq, q0, q1 = _query_columns(seq, q0, q1)
+        out = np.zeros(max(len(seq), 1), np.int64)
+        check(_lib.lib().magot_overlap_counts(self.ctx.handle, self.handle, ptr(seq), ptr(q0),
+                                              ptr(q1), len(seq), ptr(out)), 'magot_overlap_counts')
+        return out[:len(seq)]
+
+    def time(self, iters):
+        """Mean device ms per pass: {'keys', 'sort', 'segments'} of the index
+        build, {'purge', 'overlap'} over the last query set given to either
+        method (0 when none was), and 'copy', a device copy of the sorted tables
+        ('copy_bytes' bytes) (magot_overlap_time)."""
+        ms = np.zeros(6, np.float64)
+        n = ctypes.c_uint64()
+        check(_lib.lib().magot_overlap_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                            ctypes.byref(n)), 'magot_overlap_time')
+        out = dict(zip(self.PASSES, ms.tolist()))
+        out['copy_bytes'] = n.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_overlap_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OverlapPlan(object):
+    """purge_overlaps' two GFF texts as tables (magot_overlap_plan,
+    genome_tools.py:548-568), a row per line: ``tables[k]`` for file k holds
+    'flag' (more than 6 tabs), 'seq' (dense seqid in the first file's
+    dictionary; OVERLAP_NO_SEQ where the second file's seqid is not there, or
+    no flag), 'c0', 'c1', 'off', 'len'.  ``OverlapPlan.build`` returns
+    (None, reason) where only the reference's sequential run is exact.  Host
+    only."""
+
+    COLUMNS = (('flag', np.uint8), ('seq', np.uint32), ('c0', np.int64), ('c1', np.int64),
+               ('off', np.uint64), ('len', np.uint64))
+
+    def __init__(self, handle, second):
+        self.handle = handle
+        self._second = second  # the text render() copies from
+        self.tables = []
+        L = _lib.lib()
+        for which in (0, 1):
+            n, n_seq = ctypes.c_uint64(), ctypes.c_uint32()
+            cols = [ctypes.c_void_p() for _ in self.COLUMNS]
+            check(L.magot_ovplan_table(handle, which, ctypes.byref(n), ctypes.byref(n_seq),
+                                       *[ctypes.byref(c) for c in cols]), 'magot_ovplan_table')
+            self.n_seq = n_seq.value
+            self.tables.append({name: _view(c.value, n.value, dt)
+                                for (name, dt), c in zip(self.COLUMNS, cols)})
+
+    @classmethod
+    def build(cls, gff1, gff2):
+        first, second = _text_view(gff1), _text_view(gff2)
+        h, reason = ctypes.c_void_p(), ctypes.c_uint32()
+        rc = _lib.lib().magot_overlap_plan(_text_ptr(first), len(first), _text_ptr(second),
+                                           len(second), ctypes.byref(h), ctypes.byref(reason))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None, _lib.OVERLAP_REASONS[reason.value]
+        check(rc, 'magot_overlap_plan')
+        return cls(h, second), None
+
+    def render(self, drop):
+        """The second file's lines with ``drop[line]`` false, each without its
+        last byte and with LF instead, in file order (a uint8 array)."""
+        drop = np.ascontiguousarray(np.asarray(drop, dtype=np.uint8))
+        if len(drop) != len(self.tables[1]['flag']):
+            raise ValueError('one flag per line of the second file')
+        L = _lib.lib()
+        n = ctypes.c_uint64()
+        text = self._second
+        check(L.magot_ovplan_render(self.handle, _text_ptr(text), len(text),
+                                    ptr(drop) if len(drop) else None, None, 0, ctypes.byref(n)),
+              'magot_ovplan_render')
+        out = np.empty(max(n.value, 1), np.uint8)
+        check(L.magot_ovplan_render(self.handle, _text_ptr(text), len(text),
+                                    ptr(drop) if len(drop) else None, ptr(out), n.value,
+                                    ctypes.byref(n)), 'magot_ovplan_render')
+        return out[:n.value]
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.tables = []
+            _lib.lib().magot_ovplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's

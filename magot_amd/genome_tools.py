@@ -18,6 +18,7 @@
     python -m magot_amd.genome_tools depth_from_gff <depth.txt> <gff> [features=['CDS','upstream']]
            [stream_length=1000] [order=py2|insertion] [native=False]
     python -m magot_amd.genome_tools fqstats <reads.fastq> [native=False]
+    python -m magot_amd.genome_tools purge_overlaps <first.gff> <gff_to_purge> [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -680,8 +681,12 @@ def _py2_int(field):
 
 def _file_lines(path):
     """``for line in open(path)`` of Python 2: lines end after '\\n' only."""
-    data = bytes(genome.read_buffer(path))
-    lines = data.split(b'\n')
+    return _lines_of(genome.read_buffer(path))
+
+
+def _lines_of(data):
+    """The same over a buffer."""
+    lines = bytes(data).split(b'\n')
     return [ln + b'\n' for ln in lines[:-1]] + ([lines[-1]] if lines[-1] else [])
 
 
@@ -1249,8 +1254,117 @@ def fqstats(fastq_location, native='True'):
 fqstats.last_path = None
 
 
+def _map_file(path):
+    """The bytes of the file at ``path`` (``open(path)`` of the reference: a
+    missing file raises), memory-mapped where it can be."""
+    import mmap
+    with open(path, 'rb') as fh:
+        try:
+            size = os.fstat(fh.fileno()).st_size
+            return mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if size else b''
+        except (ValueError, OSError):  # not a file that maps: a pipe, a device
+            return fh.read()
+
+
+def _purge_host(first, second, out):
+    """The reference's loops restated; kept lines are appended to ``out`` as
+    they would be printed, so what came before an exception is there."""
+    purge_dict = {}
+    for line in _lines_of(first):
+        if line.count(b'\t') > 6:
+            x = line.split(b'\t')
+            coords = [_py2_int(x[3]), _py2_int(x[4])]
+            purge_dict.setdefault(x[0], []).append(coords)
+    for line in _lines_of(second):
+        printline = True
+        if line.count(b'\t') > 6:
+            x = line.split(b'\t')
+            if x[0] in purge_dict:
+                c0, c1 = _py2_int(x[3]), _py2_int(x[4])
+                for p0, p1 in purge_dict[x[0]]:
+                    if p0 < c0 < p1 or p0 < c1 < p1 or c0 < p0 < c1:
+                        printline = False
+                        break  # the reference goes on; nothing can set it back
+            if printline:  # inside the test for tabs: other lines are never printed
+                out.append(line[:-1] + b'\n')
+
+
+def _purge_native(first, second, clock):
+    """(purge_overlaps' text as a uint8 array, None) from the device: both
+    texts lowered by magot_overlap_plan, the first file's intervals sorted into
+    an engine.IntervalIndex, one purge query per line of the second file that
+    has a known seqid, the kept lines copied on the host.  (None, reason) when
+    only the reference's sequential run is exact."""
+    plan, why = engine.OverlapPlan.build(first, second)
+    clock.lap('gff_scan')
+    if plan is None:
+        return None, why
+    index = None
+    try:
+        t0, t1 = plan.tables
+        rows = np.flatnonzero(t0['flag'])
+        index = engine.IntervalIndex(t0['seq'][rows], t0['c0'][rows], t0['c1'][rows],
+                                     n_seq=plan.n_seq)
+        clock.lap('index')
+        asked = np.flatnonzero(t1['seq'] != engine._lib.OVERLAP_NO_SEQ)
+        drop = (t1['flag'] == 0).astype(np.uint8)  # 6 tabs or fewer: never printed
+        drop[asked] = index.purge_flags(t1['seq'][asked], t1['c0'][asked], t1['c1'][asked])
+        clock.lap('kernels')
+        text = plan.render(drop)
+        clock.lap('render')
+        return text, None
+    finally:
+        if index is not None:
+            index.close()
+        plan.close()
+
+
+def purge_overlaps(gff1, gff_to_purge, native='True'):
+    """genome_tools.py:548-568: the lines of ``gff_to_purge`` that overlap no
+    line of ``gff1`` on the same seqid.  Only lines with more than 6 tabs are
+    read ('#' lines among them) and only they are printed; one whose seqid
+    ``gff1`` lacks is printed without its integers being read.  A line (c0, c1) is
+    dropped when an interval (p0, p1) of ``gff1`` has p0 < c0 < p1,
+    p0 < c1 < p1 or c0 < p0 < c1, all strict and on the integers as parsed:
+    touching, equal and reversed intervals do not count.  A printed line loses
+    its last byte (its LF; the last byte of a final line without one) and gets
+    an LF.
+
+    On the device (engine.IntervalIndex: the first file's intervals sorted,
+    a few binary searches per line) unless an integer does not parse, lies
+    beyond the index's coordinate range, or there are 2^24 seqids: then, and
+    with ``native=False``, the line loop below restates the reference, its
+    ValueError after the lines printed so far included.  Nothing is written
+    before the path is known.  ``purge_overlaps.last_path`` names the path the
+    last call took."""
+    clock = _Clock()
+    first, second = _map_file(gff1), _map_file(gff_to_purge)
+    clock.lap('open')
+    if native == 'True':
+        text, why = _purge_native(first, second, clock)
+        if text is not None:
+            purge_overlaps.last_path = ('purge_overlaps', 'native', None)
+            _write_bytes(text)
+            clock.lap('write')
+            clock.emit()
+            return
+    else:
+        why = "native != 'True'"
+    purge_overlaps.last_path = ('purge_overlaps', 'host', why)
+    out = []
+    try:
+        _purge_host(first, second, out)
+    finally:
+        _write_bytes(*out)
+    clock.lap('write')
+    clock.emit()
+
+
+purge_overlaps.last_path = None
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
-         'fqstats': fqstats,
+         'fqstats': fqstats, 'purge_overlaps': purge_overlaps,
          'extract_upstream_downstream': extract_upstream_downstream,
          'coords2fasta': coords2fasta,
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,
