@@ -374,6 +374,9 @@ int magot_revcomp_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq
  * '+'/'-'.  codons_out[i] = number of emitted residues (before trimX), or -1
  * when the reference returns None (len <= 2 + frame).  pep_off (n+1) must be
  * filled by magot_translate_sizes first; out holds pep_off[n] bytes.
+ * magot_translate_batch refuses (MAGOT_ERR_ARG, before it touches the device)
+ * a seq_off that is not non-decreasing, a negative frame, and a pep_off that
+ * is not magot_translate_sizes' table for seq_off and frames.
  * lut64 maps codon c0 + 4*c1 + 16*c2 (A=0,C=1,G=2,T=3) to a residue byte;
  * NULL = the standard code of genome.py:795-802.  The junk first codon of
  * frames 1/2 (genome.py:811-818) is emitted as 'X'.

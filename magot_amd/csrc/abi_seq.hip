@@ -77,16 +77,39 @@ int magot_translate_sizes(const uint64_t* seq_off, uint64_t n, const int32_t* fr
 int magot_translate_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n,
                           const int32_t* frames, const uint8_t* strands, const uint8_t* lut64,
                           const uint64_t* pep_off, uint8_t* out) {
-  if (int rc = bind(ctx)) return rc;
+  // the tables are checked on the host before the device is touched
   if (!seq_off || !pep_off || (n && (!frames || !strands))) {
     set_error("magot_translate_batch: null argument");
     return MAGOT_ERR_ARG;
   }
-  for (uint64_t i = 0; i < n; ++i)
+  for (uint64_t i = 0; i < n; ++i) {
+    if (seq_off[i + 1] < seq_off[i]) {
+      set_error("magot_translate_batch: seq_off must be non-decreasing");
+      return MAGOT_ERR_ARG;
+    }
+    if (frames[i] < 0) {
+      set_error("magot_translate_batch: negative frame");
+      return MAGOT_ERR_ARG;
+    }
     if (strands[i] != '+' && strands[i] != '-') {
       set_error("magot_translate_batch: strand must be '+' or '-'");
       return MAGOT_ERR_ARG;
     }
+  }
+  {
+    // the kernel finds a residue's record in pep_off and reads its codon at
+    // the place the record's length and frame give (magot_translate_sizes'
+    // counts); a different table would send its loads past the record and
+    // past the input, so it is refused
+    std::vector<uint64_t> want(n + 1);
+    if (int rc = magot_translate_sizes(seq_off, n, frames, want.data(), nullptr)) return rc;
+    if (std::memcmp(want.data(), pep_off, want.size() * 8) != 0) {
+      set_error(
+          "magot_translate_batch: pep_off is not magot_translate_sizes' table for seq_off, frames");
+      return MAGOT_ERR_ARG;
+    }
+  }
+  if (int rc = bind(ctx)) return rc;
   const uint64_t total = n ? seq_off[n] : 0, total_pep = n ? pep_off[n] : 0;
   if (total_pep == 0) return MAGOT_OK;
   if (!seqs || !out) {

@@ -50,6 +50,65 @@ def test_translate_sizes_host_function():
     assert poff.tolist() == [0, 0, 0, 1, 2, 5]
 
 
+MAGOT_ERR_ARG = _lib.ERR_ARG
+
+
+def _translate_batch_null_ctx(off, frames, strands, poff):
+    """magot_translate_batch with a null context and null buffers: the table
+    checks are host work and come first, so no device is needed (or reached)."""
+    L = _lib.lib()
+    off = np.asarray(off, dtype=np.uint64)
+    frames = np.asarray(frames, dtype=np.int32)
+    strands = np.frombuffer(strands.encode('ascii'), dtype=np.uint8).copy()
+    poff = np.asarray(poff, dtype=np.uint64)
+    rc = L.magot_translate_batch(None, None, _lib.ptr(off), len(frames), _lib.ptr(frames),
+                                 _lib.ptr(strands), None, _lib.ptr(poff), None)
+    return rc, L.magot_last_error().decode('utf-8', 'replace')
+
+
+def _sizes(off, frames):
+    off = np.asarray(off, dtype=np.uint64)
+    frames = np.asarray(frames, dtype=np.int32)
+    poff = np.empty(len(frames) + 1, dtype=np.uint64)
+    _lib.check(_lib.lib().magot_translate_sizes(_lib.ptr(off), len(frames), _lib.ptr(frames),
+                                                _lib.ptr(poff), None), 'sizes')
+    return poff
+
+
+def test_translate_batch_refuses_a_table_it_cannot_trust():
+    """The kernel places every load from seq_off, frames and pep_off; the entry
+    point refuses the tables that would send it past a record, before the
+    context is looked at."""
+    off, frames, strands = [0, 0, 2, 5, 9, 20], [0, 0, 0, 1, 2], '+-+-+'
+    good = _sizes(off, frames)
+    assert good.tolist() == [0, 0, 0, 1, 2, 5]
+    for bad in ([0, 0, 0, 1, 2, 6],         # one residue more than the last record has
+                [0, 0, 0, 1, 2, 4],
+                [0, 0, 1, 1, 2, 5],         # a residue for a record below one codon
+                [0, 0, 0, 2, 2, 5],
+                [1, 1, 1, 2, 3, 6],         # shifted
+                [0, 0, 0, 1, 2, 5 + (1 << 32)]):
+        rc, msg = _translate_batch_null_ctx(off, frames, strands, bad)
+        assert rc == MAGOT_ERR_ARG
+        assert 'pep_off' in msg and 'magot_translate_sizes' in msg
+    rc, msg = _translate_batch_null_ctx([0, 0, 5, 2, 9, 20], frames, strands, good)
+    assert rc == MAGOT_ERR_ARG and 'seq_off' in msg and 'non-decreasing' in msg
+    rc, msg = _translate_batch_null_ctx(off, [0, 0, 0, -1, 2], strands, good)
+    assert rc == MAGOT_ERR_ARG and 'negative frame' in msg
+    rc, msg = _translate_batch_null_ctx(off, frames, '+-+?+', good)
+    assert rc == MAGOT_ERR_ARG and 'strand' in msg
+
+
+def test_translate_batch_accepts_the_sizes_table():
+    """A correct table passes the checks: with a null context the refusal is
+    the null-context one."""
+    off, frames = [0, 0, 2, 5, 9, 20], [0, 0, 0, 1, 2]
+    rc, msg = _translate_batch_null_ctx(off, frames, '+-+-+', _sizes(off, frames))
+    assert rc == MAGOT_ERR_ARG and msg == 'null context'
+    rc, msg = _translate_batch_null_ctx([0], [], '', [0])
+    assert rc == MAGOT_ERR_ARG and msg == 'null context'
+
+
 def test_orf6_sizes_host_function():
     """Six-frame stream sizes (genome.py:809-818 frame quirk) and placement:
     16-byte-aligned, non-overlapping spans covering [0, total), each record's
