@@ -931,6 +931,76 @@ int magot_ovplan_render(const magot_ovplan* p, const char* gff2, uint64_t len2,
                         const uint8_t* drop, uint8_t* out, uint64_t cap, uint64_t* bytes);
 void magot_ovplan_destroy(magot_ovplan* p);
 
+/*
+ * besthits_from_psl (genome_tools.py:572-592) on the device: per query name of
+ * a BLAT PSL the line with the highest matches - misMatches, as a reduction
+ * keyed by a string: hash the key, sort, verify the grouping byte for byte,
+ * reduce by segment.
+ *
+ * A line ends at LF only; the last one may lack it.  A line whose first byte is
+ * one of 'p', LF, 'm', '-', TAB, space is a pass-through line.  Every other
+ * line is a data line: at least 9 tabs; field 0 and field 1 each 1..10 digits,
+ * value <= 2^31 - 1, no sign, no blanks; the key is the bytes between the 9th
+ * tab and the next tab or the end of the line, the LF (and a CR before it)
+ * included when field 9 is the last.  score = field 0 - field 1; of the lines
+ * of one key the highest score wins, the earliest line among equals.
+ *   magot_psl_parse   uploads the whole text into one device buffer through the
+ *       context's pinned ring and runs every pass.  Declined with
+ *       MAGOT_ERR_UNSUPPORTED, *out = NULL and *reason a MAGOT_PSL_* code: a
+ *       text longer than max_bytes (0: a quarter of the free device memory),
+ *       before anything of that size is allocated; more than 2^31 - 1 lines;
+ *       a data line outside the grammar (the first such line, 1-based, in
+ *       *line; on a line with several faults: few fields, then field 0, then
+ *       field 1, form before range); two different keys in one bucket of the
+ *       low hash_bits bits (1..64) of CPython 2.7's string hash.  *line is 0
+ *       for the whole-text reasons.  A null text with len > 0 and hash_bits
+ *       outside 1..64 are MAGOT_ERR_ARG before any launch.
+ *   magot_psl_sizes   lines, pass-through lines, data lines, keys.
+ *   magot_psl_upload_ms  what the upload took inside magot_psl_parse, in device
+ *       ms from its first copy's enqueue to its last byte's arrival: the host's
+ *       copies into the pinned ring lie in between.
+ *   magot_psl_pass_lines  the pass-through lines in file order: offset in the
+ *       text and length, the LF included.
+ *   magot_psl_groups  one row per key in first-seen order: the full 64-bit hash
+ *       of the key, its first line and its best line (0-based), the best score,
+ *       and the best line's offset and length (LF included).  Any pointer may
+ *       be NULL.
+ *   magot_psl_time    mean device ms over `iters` runs of: the line index, the
+ *       parse, the compaction, the sort, the verification, the reduction, the
+ *       first-seen order with its gather, and a device copy of the text
+ *       (*text_bytes), in ms8[0..7].  The handle's answers stand afterwards.
+ * Host side (no device):
+ *   magot_psl_order   perm[0..n): the order in which a CPython 2.7 dict iterates
+ *       n distinct keys inserted in the order given, from their hashes alone.
+ *   magot_psl_render  per row (off, len) of the text the bytes [off, off + len
+ *       - 1) and an LF (`print line[:-1]`); with whole != 0 all len bytes and
+ *       an LF (`print line`).  *bytes always; the text when out is not NULL
+ *       (cap >= *bytes).  A row outside the text, or an empty row without
+ *       `whole`, is MAGOT_ERR_RANGE.
+ */
+enum {
+  MAGOT_PSL_FEW_FIELDS = 1,     /* a data line with fewer than 10 fields */
+  MAGOT_PSL_INTEGER_FORM = 2,   /* field 0 or 1 is not 1 or more digits alone */
+  MAGOT_PSL_NUMBER_RANGE = 3,   /* more than 10 digits, or above 2^31 - 1 */
+  MAGOT_PSL_HASH_COLLISION = 4, /* two keys in one bucket of the masked hash */
+  MAGOT_PSL_TOO_LARGE = 5,      /* the text is longer than max_bytes */
+  MAGOT_PSL_TOO_MANY_LINES = 6  /* more than 2^31 - 1 lines */
+};
+typedef struct magot_psl magot_psl;
+int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t hash_bits,
+                    uint64_t max_bytes, magot_psl** out, uint32_t* reason, uint64_t* line);
+int magot_psl_sizes(const magot_psl* p, uint64_t* n_lines, uint64_t* n_pass, uint64_t* n_data,
+                    uint64_t* n_groups);
+double magot_psl_upload_ms(const magot_psl* p);
+int magot_psl_pass_lines(magot_ctx* ctx, magot_psl* p, uint64_t* off, uint64_t* len);
+int magot_psl_groups(magot_ctx* ctx, magot_psl* p, uint64_t* hash, uint32_t* first_line,
+                     uint32_t* best_line, int64_t* score, uint64_t* off, uint64_t* len);
+int magot_psl_time(magot_ctx* ctx, magot_psl* p, int iters, double* ms8, uint64_t* text_bytes);
+void magot_psl_destroy(magot_psl* p);
+int magot_psl_order(const uint64_t* hash, uint64_t n, uint64_t* perm);
+int magot_psl_render(const char* text, uint64_t len, const uint64_t* off, const uint64_t* row_len,
+                     uint64_t n, int whole, uint8_t* out, uint64_t cap, uint64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,6 +66,9 @@ EXPORTS = (
     'magot_overlap_coord_range', 'magot_overlap_lane_scan', 'magot_overlap_create',
     'magot_overlap_purge', 'magot_overlap_counts', 'magot_overlap_time', 'magot_overlap_destroy',
     'magot_overlap_plan', 'magot_ovplan_table', 'magot_ovplan_render', 'magot_ovplan_destroy',
+    'magot_psl_parse', 'magot_psl_sizes', 'magot_psl_upload_ms', 'magot_psl_pass_lines',
+    'magot_psl_groups', 'magot_psl_time', 'magot_psl_destroy', 'magot_psl_order',
+    'magot_psl_render',
 )
 
 ERR_ARG = -1
@@ -97,6 +100,9 @@ OVERLAP_NO_SEQ = 0xffffffff
 # magot_overlap_plan's reasons (MAGOT_OVERLAP_*), by code
 OVERLAP_REASONS = (None, 'bad integer in the first file', 'bad integer in the second file',
                    'coordinate beyond the key range', 'too many seqids')
+# magot_psl_parse's reasons (MAGOT_PSL_*), by code
+PSL_REASONS = (None, 'few_fields', 'integer_form', 'number_range', 'hash_collision', 'too_large',
+               'too_many_lines')
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -305,6 +311,18 @@ def _declare(lib):
         'magot_ovplan_render': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp,
                                                ctypes.c_uint64, _u64p]),
         'magot_ovplan_destroy': (None, [_vp]),
+        'magot_psl_parse': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
+                                           ctypes.c_uint64, ctypes.POINTER(_vp),
+                                           ctypes.POINTER(ctypes.c_uint32), _u64p]),
+        'magot_psl_sizes': (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+        'magot_psl_upload_ms': (ctypes.c_double, [_vp]),
+        'magot_psl_pass_lines': (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+        'magot_psl_groups': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        'magot_psl_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p]),
+        'magot_psl_destroy': (None, [_vp]),
+        'magot_psl_order': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
+        'magot_psl_render': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64,
+                                            ctypes.c_int, _vp, ctypes.c_uint64, _u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -1,0 +1,285 @@
+// C ABI: besthits_from_psl's keyed reduction on the device (psl.hip;
+// genome_tools.py:572-592).  The host-only entry points (the dict order, the
+// line renderer) are in pslhost.cpp.
+#include "abi_internal.h"
+
+using namespace magot;
+
+struct magot_psl {
+  magot_ctx* ctx = nullptr;
+  void* text_mem = nullptr;  // the text, the block counts and their scan's scratch
+  void* mem = nullptr;       // everything sized by the lines
+  void* copy_mem = nullptr;  // magot_psl_time's copy target
+  PslArgs a{};
+  void* tmp0 = nullptr;
+  void* tmp = nullptr;
+  size_t tmp0_bytes = 0, tmp_bytes = 0;
+  float upload_ms = 0.f;  // first enqueue to last byte on the device, the staging copies included
+};
+
+namespace {
+
+constexpr int kPslPasses = 8;
+
+// The text into its device buffer through the context's two pinned buffers.
+int psl_upload(magot_ctx* ctx, const char* text, uint64_t len, uint8_t* dev) {
+  std::lock_guard<std::mutex> lock(ctx->pin_mu);
+  if (int rc = ensure_pin_ring(ctx)) return rc;
+  int b = 0;
+  for (uint64_t q0 = 0; q0 < len; q0 += kPinRing, b ^= 1) {
+    const uint64_t n = std::min(kPinRing, len - q0);
+    MAGOT_HIP_TRY(hipEventSynchronize(ctx->pin_ev[b]));  // the buffer's previous copy has drained
+    std::memcpy(ctx->pin[b], text + q0, n);
+    MAGOT_HIP_TRY(hipMemcpyAsync(dev + q0, ctx->pin[b], n, hipMemcpyHostToDevice, ctx->stream));
+    MAGOT_HIP_TRY(hipEventRecord(ctx->pin_ev[b], ctx->stream));
+  }
+  return MAGOT_OK;
+}
+
+// pass k of magot_psl_time on the handle's own buffers
+hipError_t psl_pass(const magot_psl* p, int k, hipStream_t s) {
+  const PslArgs& a = p->a;
+  switch (k) {
+    case 0:
+      if (hipError_t e = launch_psl_count(a, p->tmp0, p->tmp0_bytes, s)) return e;
+      return launch_psl_fill(a, s);
+    case 1: return launch_psl_parse(a, s);
+    case 2:
+      if (hipError_t e = launch_psl_compact(a, p->tmp, p->tmp_bytes, s)) return e;
+      return launch_psl_scatter(a, s);
+    case 3: return launch_psl_sort(a, p->tmp, p->tmp_bytes, s);
+    case 4: return launch_psl_verify(a, s);
+    case 5: return launch_psl_reduce(a, p->tmp, p->tmp_bytes, s);
+    case 6: return launch_psl_order(a, p->tmp, p->tmp_bytes, s);
+    default:
+      if (!a.n) return hipSuccess;
+      return hipMemcpyAsync(p->copy_mem, a.text, a.n, hipMemcpyDeviceToDevice, s);
+  }
+}
+
+int psl_decline(uint32_t* reason, uint64_t* line, uint32_t why, uint64_t at) {
+  if (reason) *reason = why;
+  if (line) *line = at;
+  set_error("magot_psl_parse: input outside the device path; use the line loop");
+  return MAGOT_ERR_UNSUPPORTED;
+}
+
+template <class T>
+int psl_fetch(T* dst, const T* src, uint64_t n) {
+  if (dst && n) MAGOT_HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void magot_psl_destroy(magot_psl* p) {
+  if (!p) return;
+  if (p->ctx) (void)hipSetDevice(p->ctx->device);
+  if (p->copy_mem) (void)hipFree(p->copy_mem);
+  if (p->mem) (void)hipFree(p->mem);
+  if (p->text_mem) (void)hipFree(p->text_mem);
+  delete p;
+}
+
+int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t hash_bits,
+                    uint64_t max_bytes, magot_psl** out, uint32_t* reason, uint64_t* line) {
+  if (int rc = bind(ctx)) return rc;
+  if (!out || (len && !text)) {
+    set_error("magot_psl_parse: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  *out = nullptr;
+  if (reason) *reason = 0;
+  if (line) *line = 0;
+  if (hash_bits < 1 || hash_bits > 64) {
+    set_error("magot_psl_parse: hash_bits outside 1..64");
+    return MAGOT_ERR_ARG;
+  }
+  if (!max_bytes) {  // the line tables take about as much again as a PSL's text
+    size_t free_b = 0, total_b = 0;
+    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    max_bytes = free_b / 4;
+  }
+  if (len > max_bytes) return psl_decline(reason, line, MAGOT_PSL_TOO_LARGE, 0);
+
+  struct Guard {
+    magot_psl* p;
+    ~Guard() { magot_psl_destroy(p); }
+  } guard{new magot_psl()};
+  magot_psl* p = guard.p;
+  p->ctx = ctx;
+  PslArgs& a = p->a;
+  a.n = len;
+  a.n_blocks = depth_text_blocks(len);
+  a.hash_bits = hash_bits;
+  hipStream_t s = ctx->stream;
+  if (len) {
+    p->tmp0_bytes = psl_count_tmp_bytes(a.n_blocks);
+    Carve cv;
+    const uint64_t o_text = cv.take<uint8_t>(len + 16);  // a 16-byte load at the last byte
+    const uint64_t o_blk = cv.take<uint64_t>(a.n_blocks + 1);
+    const uint64_t o_pre = cv.take<uint64_t>(a.n_blocks + 1);
+    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp0_bytes);
+    const uint64_t o_status = cv.take<unsigned long long>(2);
+    MAGOT_HIP_TRY(hipMalloc(&p->text_mem, cv.used + 256));
+    char* base = static_cast<char*>(p->text_mem);
+    a.text = reinterpret_cast<const uint8_t*>(base + o_text);
+    a.blk = reinterpret_cast<uint64_t*>(base + o_blk);
+    a.pre = reinterpret_cast<uint64_t*>(base + o_pre);
+    p->tmp0 = base + o_tmp;
+    a.status = reinterpret_cast<unsigned long long*>(base + o_status);
+    a.n_uniq = a.status + 1;
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
+    if (int rc = psl_upload(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
+    MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
+    MAGOT_HIP_TRY(launch_psl_count(a, p->tmp0, p->tmp0_bytes, s));
+    uint64_t lfs = 0;
+    MAGOT_HIP_TRY(hipMemcpyAsync(&lfs, a.pre + a.n_blocks, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+    MAGOT_HIP_TRY(hipEventElapsedTime(&p->upload_ms, ctx->ev0, ctx->ev1));
+    a.n_lines = lfs + (text[len - 1] != '\n' ? 1 : 0);
+    if (a.n_lines > kPslLineMask) return psl_decline(reason, line, MAGOT_PSL_TOO_MANY_LINES, 0);
+  }
+  if (a.n_lines) {
+    const uint64_t L = a.n_lines;
+    p->tmp_bytes = psl_tmp_bytes(L);
+    Carve cv;
+    const uint64_t o_start = cv.take<uint64_t>(L + 1), o_hash = cv.take<uint64_t>(L);
+    const uint64_t o_koff = cv.take<uint64_t>(L), o_klen = cv.take<uint32_t>(L);
+    const uint64_t o_rank = cv.take<uint64_t>(L), o_kind = cv.take<uint32_t>(L + 1);
+    const uint64_t o_dpos = cv.take<uint32_t>(L + 1);
+    const uint64_t o_skey = cv.take<uint64_t>(L), o_sval = cv.take<uint64_t>(L);
+    const uint64_t o_skey2 = cv.take<uint64_t>(L), o_sval2 = cv.take<uint64_t>(L);
+    const uint64_t o_poff = cv.take<uint64_t>(L), o_plen = cv.take<uint64_t>(L);
+    const uint64_t o_uniq = cv.take<uint64_t>(L), o_agg = cv.take<PslAgg>(L);
+    const uint64_t o_seg = cv.take<uint32_t>(4 * L);
+    const uint64_t o_g64 = cv.take<uint64_t>(4 * L), o_g32 = cv.take<uint32_t>(2 * L);
+    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
+    MAGOT_HIP_TRY(hipMalloc(&p->mem, cv.used + 256));
+    char* base = static_cast<char*>(p->mem);
+    a.line_start = reinterpret_cast<uint64_t*>(base + o_start);
+    a.hash = reinterpret_cast<uint64_t*>(base + o_hash);
+    a.key_off = reinterpret_cast<uint64_t*>(base + o_koff);
+    a.key_len = reinterpret_cast<uint32_t*>(base + o_klen);
+    a.rank = reinterpret_cast<uint64_t*>(base + o_rank);
+    a.kind = reinterpret_cast<uint32_t*>(base + o_kind);
+    a.dpos = reinterpret_cast<uint32_t*>(base + o_dpos);
+    a.skey = reinterpret_cast<uint64_t*>(base + o_skey);
+    a.sval = reinterpret_cast<uint64_t*>(base + o_sval);
+    a.skey_sorted = reinterpret_cast<uint64_t*>(base + o_skey2);
+    a.sval_sorted = reinterpret_cast<uint64_t*>(base + o_sval2);
+    a.pass_off = reinterpret_cast<uint64_t*>(base + o_poff);
+    a.pass_len = reinterpret_cast<uint64_t*>(base + o_plen);
+    a.uniq = reinterpret_cast<uint64_t*>(base + o_uniq);
+    a.agg = reinterpret_cast<PslAgg*>(base + o_agg);
+    uint32_t* seg = reinterpret_cast<uint32_t*>(base + o_seg);
+    a.seg_first = seg;
+    a.seg_id = seg + L;
+    a.seg_first_sorted = seg + 2 * L;
+    a.seg_id_sorted = seg + 3 * L;
+    uint64_t* g64 = reinterpret_cast<uint64_t*>(base + o_g64);
+    a.g_hash = g64;
+    a.g_off = g64 + L;
+    a.g_len = g64 + 2 * L;
+    a.g_score = reinterpret_cast<int64_t*>(g64 + 3 * L);
+    uint32_t* g32 = reinterpret_cast<uint32_t*>(base + o_g32);
+    a.g_first = g32;
+    a.g_best = g32 + L;
+    p->tmp = base + o_tmp;
+
+    MAGOT_HIP_TRY(launch_psl_fill(a, s));
+    MAGOT_HIP_TRY(launch_psl_parse(a, s));
+    MAGOT_HIP_TRY(launch_psl_compact(a, p->tmp, p->tmp_bytes, s));
+    unsigned long long status = 0;
+    uint32_t n_data = 0;
+    MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipMemcpyAsync(&n_data, a.dpos + L, 4, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+    if (status != ~0ull)
+      return psl_decline(reason, line, (uint32_t)(status & 0xff), (status >> 8) + 1);
+    a.n_data = n_data;
+    MAGOT_HIP_TRY(launch_psl_scatter(a, s));
+    MAGOT_HIP_TRY(launch_psl_sort(a, p->tmp, p->tmp_bytes, s));
+    MAGOT_HIP_TRY(launch_psl_verify(a, s));
+    MAGOT_HIP_TRY(launch_psl_reduce(a, p->tmp, p->tmp_bytes, s));
+    unsigned long long n_uniq = 0;
+    MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipMemcpyAsync(&n_uniq, a.n_uniq, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+    if (status != ~0ull)
+      return psl_decline(reason, line, (uint32_t)(status & 0xff), (status >> 8) + 1);
+    if (n_uniq > a.n_data) {
+      set_error("magot_psl_parse: more keys than data lines");
+      return MAGOT_ERR_STATE;
+    }
+    a.n_groups = n_uniq;
+    MAGOT_HIP_TRY(launch_psl_order(a, p->tmp, p->tmp_bytes, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  }
+  guard.p = nullptr;
+  *out = p;
+  return MAGOT_OK;
+}
+
+int magot_psl_sizes(const magot_psl* p, uint64_t* n_lines, uint64_t* n_pass, uint64_t* n_data,
+                    uint64_t* n_groups) {
+  if (!p) {
+    set_error("magot_psl_sizes: null handle");
+    return MAGOT_ERR_ARG;
+  }
+  if (n_lines) *n_lines = p->a.n_lines;
+  if (n_pass) *n_pass = p->a.n_lines - p->a.n_data;
+  if (n_data) *n_data = p->a.n_data;
+  if (n_groups) *n_groups = p->a.n_groups;
+  return MAGOT_OK;
+}
+
+double magot_psl_upload_ms(const magot_psl* p) { return p ? (double)p->upload_ms : 0.0; }
+
+int magot_psl_pass_lines(magot_ctx* ctx, magot_psl* p, uint64_t* off, uint64_t* len) {
+  if (int rc = handle_of(ctx, p, "magot_psl_pass_lines", "handle")) return rc;
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const uint64_t n = p->a.n_lines - p->a.n_data;
+  if (int rc = psl_fetch(off, p->a.pass_off, n)) return rc;
+  return psl_fetch(len, p->a.pass_len, n);
+}
+
+int magot_psl_groups(magot_ctx* ctx, magot_psl* p, uint64_t* hash, uint32_t* first_line,
+                     uint32_t* best_line, int64_t* score, uint64_t* off, uint64_t* len) {
+  if (int rc = handle_of(ctx, p, "magot_psl_groups", "handle")) return rc;
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const PslArgs& a = p->a;
+  const uint64_t n = a.n_groups;
+  if (int rc = psl_fetch(hash, a.g_hash, n)) return rc;
+  if (int rc = psl_fetch(first_line, a.g_first, n)) return rc;
+  if (int rc = psl_fetch(best_line, a.g_best, n)) return rc;
+  if (int rc = psl_fetch(score, a.g_score, n)) return rc;
+  if (int rc = psl_fetch(off, a.g_off, n)) return rc;
+  return psl_fetch(len, a.g_len, n);
+}
+
+int magot_psl_time(magot_ctx* ctx, magot_psl* p, int iters, double* ms8, uint64_t* text_bytes) {
+  if (int rc = handle_of(ctx, p, "magot_psl_time", "handle")) return rc;
+  if (iters <= 0 || !ms8) {
+    set_error("magot_psl_time: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  if (text_bytes) *text_bytes = p->a.n;
+  for (int k = 0; k < kPslPasses; ++k) ms8[k] = 0;
+  if (!p->a.n_lines) return MAGOT_OK;  // an empty text: nothing was launched
+  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.n + 256));
+  // every pass writes what it wrote in magot_psl_parse: the answers stand
+  double total[kPslPasses] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < iters; ++i)
+    for (int k = 0; k < kPslPasses; ++k)
+      if (int rc = time_pass(ctx, &total[k],
+                             [&]() -> hipError_t { return psl_pass(p, k, ctx->stream); }))
+        return rc;
+  for (int k = 0; k < kPslPasses; ++k) ms8[k] = total[k] / iters;
+  return MAGOT_OK;
+}
+
+}  // extern "C"

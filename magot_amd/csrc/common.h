@@ -809,6 +809,72 @@ hipError_t launch_ov_overlap(const OvIndex& ix, const OvQuery& q, int64_t* count
                              uint32_t* long_list, unsigned long long* n_long, int n_cu,
                              hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// besthits_from_psl: a reduction keyed by a string (psl.hip; magot_psl_*)
+// ---------------------------------------------------------------------------
+// rank of a data line: its score biased to unsigned above the line counted
+// from the top, so the maximum over a key is the highest score and, among
+// equals, the earliest line; a stable sort of ranks in line order keeps each
+// key's lines in line order.
+constexpr uint64_t kPslLineMask = (1ull << 31) - 1;  // lines 0 .. 2^31 - 2
+__host__ __device__ inline uint64_t psl_rank(int64_t score, uint64_t line) {
+  return ((uint64_t)(score + (1ll << 31)) << 31) | (kPslLineMask - line);
+}
+__host__ __device__ inline uint64_t psl_rank_line(uint64_t rank) {
+  return kPslLineMask - (rank & kPslLineMask);
+}
+__host__ __device__ inline int64_t psl_rank_score(uint64_t rank) {
+  return (int64_t)(rank >> 31) - (1ll << 31);
+}
+struct PslAgg {  // per key: the best rank, and the rank's low bits of its first line
+  uint64_t best, first;
+};
+struct PslArgs {
+  const uint8_t* text;  // n bytes, 16-byte aligned, readable to the next multiple of 16
+  uint64_t n;
+  uint64_t n_blocks;    // depth_text_blocks(n)
+  uint64_t* blk;        // n_blocks + 1: LFs per text block, the last entry 0
+  uint64_t* pre;        // their exclusive scan; pre[n_blocks]: the LFs of the text
+  // per line, n_lines of each (line_start: n_lines + 1, the last entry n)
+  uint64_t n_lines;
+  uint64_t* line_start;
+  uint64_t* hash;       // CPython 2.7's hash of the key (data lines)
+  uint64_t* key_off;
+  uint32_t* key_len;
+  uint64_t* rank;
+  uint32_t* kind;       // 1: data line, 0: pass-through; then n_lines + 1 of
+  uint32_t* dpos;       // their exclusive scan: data lines before each line
+  unsigned long long* status;  // min of (line << 8 | MAGOT_PSL_* reason); ~0 when clean
+  // the data lines compacted (n_data), then sorted by the masked hash
+  uint64_t n_data;
+  uint32_t hash_bits;
+  uint64_t *skey, *sval, *skey_sorted, *sval_sorted;
+  uint64_t *pass_off, *pass_len;  // n_lines - n_data, in file order
+  // per key (n_groups, at most n_data)
+  uint64_t n_groups;
+  uint64_t* uniq;       // the masked hashes that occur
+  PslAgg* agg;
+  unsigned long long* n_uniq;
+  uint32_t *seg_first, *seg_id, *seg_first_sorted, *seg_id_sorted;
+  // the rows of magot_psl_groups, in first-seen order
+  uint64_t *g_hash, *g_off, *g_len;
+  int64_t* g_score;
+  uint32_t *g_first, *g_best;
+};
+// rocprim scratch: of the block scan, and of every later pass over a text of
+// n_lines lines (n_data and n_groups are at most n_lines)
+size_t psl_count_tmp_bytes(uint64_t n_blocks);
+size_t psl_tmp_bytes(uint64_t n_lines);
+hipError_t launch_psl_count(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_psl_fill(const PslArgs& a, hipStream_t s);
+hipError_t launch_psl_parse(const PslArgs& a, hipStream_t s);
+hipError_t launch_psl_compact(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_psl_scatter(const PslArgs& a, hipStream_t s);
+hipError_t launch_psl_sort(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_psl_verify(const PslArgs& a, hipStream_t s);
+hipError_t launch_psl_reduce(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_psl_order(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

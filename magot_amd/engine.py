@@ -1673,6 +1673,123 @@ class OverlapPlan(object):
             pass
 
 
+class BestHits(object):
+    """besthits_from_psl's keyed reduction on the device (magot_psl_*,
+    genome_tools.py:572-592): per query name of a PSL text -- the bytes between
+    a data line's 9th tab and the next tab or the line's end -- the line with
+    the highest field 0 - field 1, the earliest among equals.  Lines are
+    grouped by CPython 2.7's string hash of the key, sorted, and every group is
+    verified byte for byte; ``parse`` returns (None, reason) where only the
+    line loop is exact: 'few_fields', 'integer_form', 'number_range' (a data
+    line outside the native grammar), 'hash_collision', 'too_large',
+    'too_many_lines'."""
+
+    PASSES = ('line_index', 'parse', 'compact', 'sort', 'verify', 'reduce', 'order', 'copy')
+    GROUP_COLUMNS = (('hash', np.uint64), ('first_line', np.uint32), ('best_line', np.uint32),
+                     ('score', np.int64), ('off', np.uint64), ('len', np.uint64))
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.n_lines = self.n_pass = self.n_data = self.n_groups = 0
+        self.upload_ms = 0.0
+
+    @classmethod
+    def parse(cls, data, hash_bits=64, max_bytes=0, ctx=None):
+        """The PSL text in ``data`` (bytes, a buffer, an mmap, numpy) made
+        resident on the device and reduced.  ``hash_bits``: the low bits of the
+        hash the lines are grouped by (two keys in one bucket decline the text;
+        fewer than 64 bits only serve to test that).  ``max_bytes``: a longer
+        text is declined (0: a quarter of the free device memory)."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(data)
+        h, reason, line = ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_uint64()
+        rc = _lib.lib().magot_psl_parse(self.ctx.handle, _text_ptr(view), len(view),
+                                        int(hash_bits), int(max_bytes or 0), ctypes.byref(h),
+                                        ctypes.byref(reason), ctypes.byref(line))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None, _lib.PSL_REASONS[reason.value]
+        check(rc, 'magot_psl_parse')
+        self.handle = h
+        sizes = [ctypes.c_uint64() for _ in range(4)]
+        check(_lib.lib().magot_psl_sizes(h, *[ctypes.byref(x) for x in sizes]), 'magot_psl_sizes')
+        self.n_lines, self.n_pass, self.n_data, self.n_groups = [x.value for x in sizes]
+        # device ms of the upload, the staging copies on the host included
+        self.upload_ms = float(_lib.lib().magot_psl_upload_ms(h))
+        return self
+
+    def pass_lines(self):
+        """(off, len) of the pass-through lines in file order, uint64 each; a
+        length counts the line's LF."""
+        off = np.zeros(max(self.n_pass, 1), np.uint64)
+        length = np.zeros(max(self.n_pass, 1), np.uint64)
+        check(_lib.lib().magot_psl_pass_lines(self.ctx.handle, self.handle, ptr(off), ptr(length)),
+              'magot_psl_pass_lines')
+        return off[:self.n_pass], length[:self.n_pass]
+
+    def groups(self):
+        """One row per key in first-seen order, as a dict of arrays: 'hash'
+        (the key's full 64-bit hash), 'first_line', 'best_line' (0-based),
+        'score', and 'off', 'len' of the best line (its LF counted)."""
+        cols = [np.zeros(max(self.n_groups, 1), dt) for _, dt in self.GROUP_COLUMNS]
+        check(_lib.lib().magot_psl_groups(self.ctx.handle, self.handle, *[ptr(c) for c in cols]),
+              'magot_psl_groups')
+        return {name: c[:self.n_groups] for (name, _), c in zip(self.GROUP_COLUMNS, cols)}
+
+    def time(self, iters):
+        """Mean device ms per pass (PASSES; 'copy': a device copy of the text,
+        'text_bytes' bytes) (magot_psl_time)."""
+        ms = np.zeros(len(self.PASSES), np.float64)
+        n = ctypes.c_uint64()
+        check(_lib.lib().magot_psl_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                        ctypes.byref(n)), 'magot_psl_time')
+        out = dict(zip(self.PASSES, ms.tolist()))
+        out['text_bytes'] = n.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_psl_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def py2_order_of_hashes(hashes):
+    """The order (indices, uint64) in which a CPython 2.7 dict iterates distinct
+    keys inserted in the given order, from their string hashes alone
+    (magot_psl_order; py2order.dict_order on the host, natively)."""
+    hashes = np.ascontiguousarray(np.asarray(hashes, dtype=np.uint64).reshape(-1))
+    perm = np.zeros(max(len(hashes), 1), np.uint64)
+    check(_lib.lib().magot_psl_order(ptr(hashes) if len(hashes) else None, len(hashes), ptr(perm)),
+          'magot_psl_order')
+    return perm[:len(hashes)]
+
+
+def render_lines(data, off, length, whole=False):
+    """The rows (off, length) of the text in ``data``, each without its last
+    byte and with LF instead (``whole``: all of it and an LF), as one uint8
+    array (magot_psl_render)."""
+    view = _text_view(data)
+    off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64).reshape(-1))
+    length = np.ascontiguousarray(np.asarray(length, dtype=np.uint64).reshape(-1))
+    if len(off) != len(length):
+        raise ValueError('one length per offset')
+    n, need = len(off), ctypes.c_uint64()
+    L = _lib.lib()
+    args = (_text_ptr(view), len(view), ptr(off) if n else None, ptr(length) if n else None, n,
+            1 if whole else 0)
+    check(L.magot_psl_render(*args, None, 0, ctypes.byref(need)), 'magot_psl_render')
+    out = np.empty(max(need.value, 1), np.uint8)
+    check(L.magot_psl_render(*args, ptr(out), need.value, ctypes.byref(need)), 'magot_psl_render')
+    return out[:need.value]
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's
