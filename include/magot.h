@@ -1001,6 +1001,47 @@ int magot_psl_order(const uint64_t* hash, uint64_t n, uint64_t* perm);
 int magot_psl_render(const char* text, uint64_t len, const uint64_t* off, const uint64_t* row_len,
                      uint64_t n, int whole, uint8_t* out, uint64_t cap, uint64_t* bytes);
 
+/*
+ * composition_by_site (genome_tools.py:488-503) on the device: per site of an
+ * alignment, how many rows hold a, t, c, g there, either case; every other
+ * byte (N, '-', IUPAC, ...) is left out.  The rows are stretches of a resident
+ * genome's contigs, so one pass over its forward plane counts them.
+ *   magot_site_create  row r is the n_sites bases of contig contig[r] from
+ *       offset[r] (0-based); a caller may so count a block of rows or of sites.
+ *       n_sites = 0 or n_rows = 0, 2^32 rows or more, and a genome of another
+ *       context are MAGOT_ERR_ARG; a row that names no contig or runs past its
+ *       contig's end is MAGOT_ERR_RANGE; all before any launch.  The genome
+ *       must outlive the handle.
+ *   magot_site_execute  the counting pass, on the context stream.
+ *   magot_site_counts  n_sites x 4 counts, a, t, c, g per site, to the
+ *       caller's buffer (MAGOT_ERR_STATE before magot_site_execute).
+ *   magot_site_time    mean device ms over `iters` runs of the pass.
+ *   magot_site_params  the pass's shape, for tests that straddle it: sites per
+ *       lane and per workgroup tile, rows per strip (above which row strips are
+ *       combined with atomics), and the rows after which the 4-bit and the 8-bit
+ *       counters are widened.  Any pointer may be NULL.
+ * Host side (no device):
+ *   magot_site_render  the tool's text from n_sites x 4 counts:
+ *       "a\tt\tc\tg\n", then per site the four quotients count / (a + t + c + g)
+ *       as Python 2's str(float) prints them ('%.12g'; ".0" appended to a
+ *       result without '.' or 'e').  *text is allocated here (n_threads
+ *       threads; 0: up to 16) and released with magot_site_text_free.  A site
+ *       whose four counts are 0 is MAGOT_ERR_RANGE with the first such site in
+ *       *empty_site and no text; otherwise *empty_site = n_sites.
+ */
+typedef struct magot_site magot_site;
+int magot_site_create(magot_ctx* ctx, const magot_genome* g, const uint32_t* contig,
+                      const uint64_t* offset, uint64_t n_rows, uint64_t n_sites, magot_site** out);
+int magot_site_execute(magot_ctx* ctx, magot_site* p);
+int magot_site_counts(magot_ctx* ctx, magot_site* p, uint32_t* counts);
+int magot_site_time(magot_ctx* ctx, magot_site* p, int iters, double* ms);
+void magot_site_params(uint32_t* sites_per_lane, uint32_t* sites_per_tile, uint32_t* rows_per_strip,
+                       uint32_t* widen4_rows, uint32_t* widen8_rows);
+void magot_site_destroy(magot_site* p);
+int magot_site_render(const uint32_t* counts, uint64_t n_sites, uint32_t n_threads, uint8_t** text,
+                      uint64_t* bytes, uint64_t* empty_site);
+void magot_site_text_free(uint8_t* text);
+
 #ifdef __cplusplus
 }
 #endif

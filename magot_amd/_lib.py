@@ -69,6 +69,8 @@ EXPORTS = (
     'magot_psl_parse', 'magot_psl_sizes', 'magot_psl_upload_ms', 'magot_psl_pass_lines',
     'magot_psl_groups', 'magot_psl_time', 'magot_psl_destroy', 'magot_psl_order',
     'magot_psl_render',
+    'magot_site_create', 'magot_site_execute', 'magot_site_counts', 'magot_site_time',
+    'magot_site_params', 'magot_site_destroy', 'magot_site_render', 'magot_site_text_free',
 )
 
 ERR_ARG = -1
@@ -323,6 +325,16 @@ def _declare(lib):
         'magot_psl_order': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
         'magot_psl_render': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64,
                                             ctypes.c_int, _vp, ctypes.c_uint64, _u64p]),
+        'magot_site_create': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.POINTER(_vp)]),
+        'magot_site_execute': (ctypes.c_int, [_vp, _vp]),
+        'magot_site_counts': (ctypes.c_int, [_vp, _vp, _vp]),
+        'magot_site_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
+        'magot_site_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 5),
+        'magot_site_destroy': (None, [_vp]),
+        'magot_site_render': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint32,
+                                             ctypes.POINTER(_vp), _u64p, _u64p]),
+        'magot_site_text_free': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -21,7 +21,8 @@ SOURCES = ['abi.hip', 'abi_genome.hip', 'abi_plan.hip', 'abi_seq.hip', 'abi_orf.
            'abi_track.hip', 'abi_text.hip', 'abi_overlap.hip', 'extract.hip', 'seqops.hip', 'pack.cpp',
            'gffplan.cpp', 'fasta.cpp', 'render.hip', 'devpack.hip', 'wire.hip', 'tileblocks.cpp',
            'tileplan.cpp', 'orfcall.hip', 'maskplan.cpp', 'maskgen.hip', 'track.hip', 'depth.hip',
-           'fastq.hip', 'overlap.hip', 'overlapplan.cpp', 'abi_psl.hip', 'psl.hip', 'pslhost.cpp']
+           'fastq.hip', 'overlap.hip', 'overlapplan.cpp', 'abi_psl.hip', 'psl.hip', 'pslhost.cpp',
+           'abi_site.hip', 'sitecount.hip', 'sitehost.cpp']
 HEADERS = ['common.h', 'hostutil.h', 'wavecopy.h', 'abi_internal.h',
            os.path.join('..', '..', 'include', 'magot.h')]
 

@@ -875,6 +875,34 @@ hipError_t launch_psl_verify(const PslArgs& a, hipStream_t s);
 hipError_t launch_psl_reduce(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_psl_order(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// composition_by_site (sitecount.hip; genome_tools.py:488-503)
+// ---------------------------------------------------------------------------
+// Per site of an alignment whose rows lie in the forward nibble plane, the
+// rows that hold a, t, c, g there (either case).  A lane owns kSiteLane
+// consecutive sites, one word of every row after a funnel shift by the row's
+// start; a workgroup owns a tile of sites and a strip of rows.  Per code a
+// 0/1-per-nibble mask is added into 4-bit counters, which are widened into
+// bytes every kSiteWiden4 rows (15 is the most a nibble holds) and the bytes
+// into 32-bit registers every kSiteWiden8 rows (17 * 15 = 255, the most a byte
+// holds).  One strip: the counts are stored; several: added with integer
+// atomics into zeroed memory, exact in any order.
+constexpr uint32_t kSiteLane = 8;
+constexpr uint32_t kSiteBlock = 256;
+constexpr uint32_t kSiteTile = kSiteLane * kSiteBlock;
+constexpr uint32_t kSiteWiden4 = 15;
+constexpr uint32_t kSiteWiden8 = 17 * kSiteWiden4;
+constexpr uint32_t kSiteStrip = 4 * kSiteWiden8;
+struct SiteArgs {
+  const uint32_t* nib;        // the forward plane
+  const uint64_t* row_start;  // n_rows global base coordinates
+  uint64_t n_rows, n_sites;
+  uint32_t* counts;           // n_sites x 4: a, t, c, g
+  uint32_t n_tiles, n_strips;
+};
+// zeroes the counts first when there are several strips
+hipError_t launch_site_count(const SiteArgs& a, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

@@ -1790,6 +1790,113 @@ def render_lines(data, off, length, whole=False):
     return out[:need.value]
 
 
+class SiteCounts(object):
+    """composition_by_site's counting pass over a resident genome
+    (magot_site_*, genome_tools.py:488-503): the alignment's rows are contigs of
+    ``genome`` (``rows``: contig indices; default all of them, in order), each
+    read from ``offsets`` (default 0) for ``n_sites`` sites (default: the
+    first row's length from its offset).  Per site the rows holding a, t, c, g
+    there in either case are counted; every other byte is left out.  A row
+    shorter than its offset + n_sites is refused (MagotError)."""
+
+    def __init__(self, genome, rows=None, offsets=None, n_sites=None):
+        self.ctx = genome.ctx
+        self.handle = None
+        self._genome = genome  # the plane must outlive the handle
+        rows = np.arange(len(genome.lengths)) if rows is None else np.asarray(rows).reshape(-1)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if offsets is None:
+            offsets = np.zeros(len(rows), np.uint64)
+        offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+        if len(offsets) != len(rows):
+            raise ValueError('one offset per row')
+        if n_sites is None and len(rows):
+            n_sites = int(genome.lengths[int(rows[0])]) - int(offsets[0])
+        self.n_rows, self.n_sites = len(rows), int(n_sites or 0)
+        h = ctypes.c_void_p()
+        check(_lib.lib().magot_site_create(self.ctx.handle, genome.handle, ptr(rows), ptr(offsets),
+                                           self.n_rows, self.n_sites, ctypes.byref(h)),
+              'magot_site_create')
+        self.handle = h
+
+    @staticmethod
+    def _params():
+        p = [ctypes.c_uint32() for _ in range(5)]
+        _lib.lib().magot_site_params(*[ctypes.byref(x) for x in p])
+        return [x.value for x in p]
+
+    @staticmethod
+    def sites_per_lane():
+        """Consecutive sites one lane counts: one plane word of every row."""
+        return SiteCounts._params()[0]
+
+    @staticmethod
+    def sites_per_tile():
+        """Sites of one workgroup."""
+        return SiteCounts._params()[1]
+
+    @staticmethod
+    def rows_per_strip():
+        """Rows one workgroup goes down; an alignment with more is counted in
+        strips whose counts are added with atomics."""
+        return SiteCounts._params()[2]
+
+    @staticmethod
+    def widening_periods():
+        """(rows after which the 4-bit counters are widened to bytes, rows after
+        which the bytes are widened to 32 bits)."""
+        return tuple(SiteCounts._params()[3:5])
+
+    def counts(self):
+        """n_sites x 4 uint32: the rows with a, t, c, g at each site."""
+        check(_lib.lib().magot_site_execute(self.ctx.handle, self.handle), 'magot_site_execute')
+        out = np.empty((self.n_sites, 4), np.uint32)
+        check(_lib.lib().magot_site_counts(self.ctx.handle, self.handle, ptr(out)),
+              'magot_site_counts')
+        return out
+
+    def time(self, iters):
+        """Mean device ms of the counting pass (magot_site_time)."""
+        ms = ctypes.c_double()
+        check(_lib.lib().magot_site_time(self.ctx.handle, self.handle, int(iters), ctypes.byref(ms)),
+              'magot_site_time')
+        return ms.value
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_site_destroy(self.handle)
+            self.handle = None
+        self._genome = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def render_composition(counts, threads=0):
+    """composition_by_site's text (a uint8 array) from n x 4 counts of a, t, c,
+    g: the header line, then per site the four shares of their sum as Python
+    2 prints a float (magot_site_render).  ZeroDivisionError, as the tool's, when
+    a site has no counted base.  Host only."""
+    counts = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32))
+    if counts.ndim != 2 or counts.shape[1] != 4:
+        raise ValueError('counts must be n x 4')
+    L = _lib.lib()
+    text, n, empty = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
+    rc = L.magot_site_render(ptr(counts) if len(counts) else None, len(counts), int(threads),
+                             ctypes.byref(text), ctypes.byref(n), ctypes.byref(empty))
+    if rc == _lib.ERR_RANGE:
+        raise ZeroDivisionError('float division by zero (site %d)' % empty.value)
+    check(rc, 'magot_site_render')
+    try:
+        return np.ctypeslib.as_array(ctypes.cast(text, ctypes.POINTER(ctypes.c_uint8)),
+                                     shape=(n.value,)).copy()
+    finally:
+        L.magot_site_text_free(text)
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's

@@ -21,6 +21,8 @@
     python -m magot_amd.genome_tools purge_overlaps <first.gff> <gff_to_purge> [native=False]
     python -m magot_amd.genome_tools besthits_from_psl <hits.psl> [order=py2|insertion]
            [native=False]
+    python -m magot_amd.genome_tools composition_by_site <alignment.fasta> [order=py2|insertion]
+           [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -111,11 +113,8 @@ def _literal(text):
 
 
 def _write(text):
-    out = getattr(sys.stdout, 'buffer', None)
-    if out is not None:
-        sys.stdout.flush()
-        out.write(text.encode('latin-1'))
-        out.flush()
+    if getattr(sys.stdout, 'buffer', None) is not None:
+        _write_bytes(text.encode('latin-1'))
     else:
         sys.stdout.write(text)
 
@@ -125,7 +124,12 @@ def _write_bytes(*parts):
     if out is not None:
         sys.stdout.flush()
         for p in parts:
-            out.write(p)
+            # an unbuffered stream (PYTHONUNBUFFERED) writes what one write(2)
+            # takes, at most 2 GiB, and says how much
+            view = memoryview(p).cast('B')
+            while len(view):
+                n = out.write(view)
+                view = view[len(view) if n is None else n:]
         out.flush()
     else:
         sys.stdout.write(''.join(bytes(p).decode('latin-1') for p in parts))
@@ -1470,6 +1474,139 @@ def besthits_from_psl(psl, order='py2', native='True'):
 
 besthits_from_psl.last_path = None
 
+def _py2_float_str(value):
+    """str(float) of Python 2: twelve significant digits, and '.0' on a result
+    that has neither '.' nor 'e'."""
+    text = '%.12g' % value
+    return text if ('.' in text or 'e' in text or 'n' in text) else text + '.0'
+
+
+def _composition_host(fasta_alignment, order):
+    """The reference's loops restated over genome.GenomeSequence; the text it
+    prints once they are through."""
+    seq_dict = genome.GenomeSequence(fasta_alignment)
+    names = list(seq_dict)
+    if order == 'py2':
+        from . import py2order
+        names = py2order.dict_order(names)
+    position_list = [['a', 't', 'c', 'g']]
+    for site in range(len(seq_dict[names[0]])):  # no record: IndexError
+        count_dict = {'a': 0, 't': 0, 'c': 0, 'g': 0}
+        allcounts = 0
+        for name in names:
+            cell = seq_dict[name][site].lower()  # a shorter record: IndexError
+            if cell in count_dict:
+                count_dict[cell] += 1
+                allcounts += 1
+        position_list.append([_py2_float_str(count_dict[n] * 1.0 / allcounts)  # ZeroDivisionError
+                              for n in position_list[0]])
+    return ''.join('\t'.join(position) + '\n' for position in position_list)
+
+
+def _composition_native(fasta_alignment, order, clock):
+    """(composition_by_site's text as a uint8 array, None) from the device: the
+    FASTA packed natively, engine.SiteCounts over its records as rows,
+    engine.render_composition on the host.  (None, reason) where the records
+    the native reader sees are not the reference's dict.  Raises the
+    reference's IndexError and ZeroDivisionError."""
+    fa = genome.read_buffer(fasta_alignment)
+    if len(fa) == 0:
+        return None, 'no records'
+    if bytes(fa[:1]) != b'>':
+        return None, 'text before the first header'
+    found = engine.fasta_contigs(fa)
+    clock.lap('fasta_index')
+    if found is None:
+        return None, 'the native reader refuses the file'
+    names, lengths = found
+    if not names:
+        return None, 'no records'
+    if sum(lengths) > engine.PART_BASES:
+        return None, 'more bases than one plane'
+    first = names[0]
+    if order == 'py2':
+        from . import py2order
+        first = py2order.dict_order(names)[0]
+    n_sites = lengths[names.index(first)]
+    # The reference divides at every site before it reaches the next one, so
+    # with a record shorter than the first it raises at that record's end --
+    # unless a site before it has no counted base.  The sites up to there are
+    # counted to tell the two apart.
+    shortest = min(lengths)
+    clock.lap('order')
+    dev = sites = None
+    try:
+        dev = engine.FastaGenome.load(fa, truncate_names=False)
+        clock.lap('fasta_read')
+        if dev is None:
+            return None, 'the native reader refuses the file'
+        sites = engine.SiteCounts(dev, n_sites=min(n_sites, shortest))
+        counts = sites.counts()
+        clock.lap('kernels')
+        _composition_native.calls += 1
+        if shortest < n_sites:
+            if not counts.any(axis=1).all():
+                raise ZeroDivisionError('float division by zero')
+            raise IndexError('string index out of range')
+        text = engine.render_composition(counts)
+        clock.lap('render')
+        return text, None
+    finally:
+        for obj in (sites, dev):
+            if obj is not None:
+                obj.close()
+
+
+_composition_native.calls = 0  # device passes so far
+
+
+def composition_by_site(fasta_alignment, order='py2', native='True'):
+    """genome_tools.py:488-503: for every column of a FASTA alignment the
+    share of a, t, c and g among the records that hold one of the four there,
+    in either case; N, '-', IUPAC and every other byte count neither as a base
+    nor in the denominator.  The header line ``a\\tt\\tc\\tg``, then one
+    line per site of the four shares as Python 2 prints a float.  The number of
+    sites is the length of the dict's first record: the first in the order a
+    Python 2 dict of the names iterates (``order='py2'``) or the first in the
+    file (``order='insertion'``).  Longer records are read up to there; a
+    shorter one is an IndexError, a site without a counted base a
+    ZeroDivisionError, no record an IndexError, and nothing is printed then:
+    the reference prints after its loops.
+
+    On the device (engine.SiteCounts: one pass across the records of the
+    packed genome; engine.render_composition for the text) for a regular
+    file that starts with a header, whose records the native reader takes,
+    with at most one device plane of bases; the native reader folds a repeated
+    name as the dict does (first position, last sequence).  Otherwise,
+    and with ``native=False``, the loops on the host restate the reference
+    over genome.GenomeSequence, a string that names no file read as the text
+    itself included.  With a record shorter than the first, the device counts
+    the sites before that record's end, to raise ZeroDivisionError where the
+    reference meets an empty site first, IndexError otherwise.
+    ``composition_by_site.last_path`` names the path the last call took."""
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'py2' or 'insertion'")
+    clock = _Clock()
+    if native != 'True':
+        why = "native != 'True'"
+    elif not (isinstance(fasta_alignment, str) and os.path.isfile(fasta_alignment)):
+        why = 'not a regular file'
+    else:
+        composition_by_site.last_path = ('composition_by_site', 'native', None)
+        text, why = _composition_native(fasta_alignment, order, clock)
+        if text is not None:
+            _write_bytes(text)
+            clock.lap('write')
+            clock.emit()
+            return
+    composition_by_site.last_path = ('composition_by_site', 'host', why)
+    _write(_composition_host(fasta_alignment, order))
+    clock.lap('write')
+    clock.emit()
+
+
+composition_by_site.last_path = None
+
 
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
          'fqstats': fqstats, 'purge_overlaps': purge_overlaps, 'besthits_from_psl': besthits_from_psl,
@@ -1477,7 +1614,8 @@ TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at
          'coords2fasta': coords2fasta,
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,
          'get_seq_from_fasta': get_seq_from_fasta, 'dna2orfs': dna2orfs,
-         'mask_from_gff': mask_from_gff, 'depth_from_gff': depth_from_gff}
+         'mask_from_gff': mask_from_gff, 'depth_from_gff': depth_from_gff,
+         'composition_by_site': composition_by_site}
 
 
 def parse_argv(argv):
