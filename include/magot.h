@@ -1042,6 +1042,97 @@ int magot_site_render(const uint32_t* counts, uint64_t n_sites, uint32_t n_threa
                       uint64_t* bytes, uint64_t* empty_site);
 void magot_site_text_free(uint8_t* text);
 
+/*
+ * heterozygosity_from_vcf (magot_variants.py:16-139) on the device: per locus
+ * and sample the variants inside whose GT's first and last byte differ.  The
+ * text is resident, as a PSL's; spans are (offset, length) into it and leave
+ * the line's LF out.
+ *   magot_vcf_parse   uploads and indexes the text, places its data lines and
+ *       "##" lines, reads S from the '#' line and parses every data line.
+ *       Outside the native grammar: MAGOT_ERR_UNSUPPORTED, *out = NULL, *reason
+ *       a MAGOT_VCF_* code and *line the 1-based line (0: none).  max_bytes as
+ *       magot_psl_parse's; max_samples and max_runs 0 for the limits below, or
+ *       less, for tests.
+ *   magot_vcf_sizes   lines, data lines, "##" lines, samples, words per bit row,
+ *       CHROM runs, and the span of the '#' line.
+ *   magot_vcf_header_lines  the spans of the "##" lines in file order.
+ *   magot_vcf_runs    the CHROM span of each run's first line: consecutive data
+ *       lines with one CHROM are a run.
+ *   magot_vcf_resolve contig[r] of each run (the caller's numbering): keys
+ *       (contig << 32 | POS), a stable sort, and per data line whether it is the
+ *       last (kept) and the first of its key.
+ *   magot_vcf_tables  per data line, in file order: its 0-based line, POS, the
+ *       CPython 2.7 hash of CHROM<:>POS, kept, first (both after
+ *       magot_vcf_resolve, else 0), and the bit rows (data lines x words).
+ *       Any pointer may be NULL.
+ *   magot_vcf_last_of the 0-based line and span of the kept line whose key is
+ *       that of data line d.
+ *   magot_vcf_count   per locus (contig, lo, hi: positions lo..hi, none when
+ *       lo > hi) and sample the kept lines inside with their bit set, to
+ *       counts[n_loci x samples]; *foreign = 1 when a counted line has a bit
+ *       outside allowed[words].  MAGOT_ERR_UNSUPPORTED with
+ *       MAGOT_VCF_TOO_MANY_COUNTS in *reason above 2^29 counters.
+ *   magot_vcf_time    mean device ms over `iters` runs of: the line index, the
+ *       classification, the parse, the runs, the sort, the flags, the counting
+ *       pass of the last magot_vcf_count (0 before one), and a device copy of
+ *       the text.
+ *   magot_vcf_params  rows per piece of the counting pass (longer loci are
+ *       counted in pieces combined with atomics), and the limits on samples,
+ *       runs and counters.
+ * Host side (no device):
+ *   magot_vcf_render  the rows "locus,rate,..." joined by LF: per locus with
+ *       seqlen >= 1 its text (loci + loci_off[l] .. loci_off[l + 1]) and per
+ *       column c of cols str(100.0 * counts[l * n_samples + c] / seqlen) as
+ *       Python 2 prints a float.  *text is released with magot_site_text_free.
+ */
+enum {
+  MAGOT_VCF_NO_HEADER = 1,       /* no '#' line that is not "##" */
+  MAGOT_VCF_MANY_HEADERS = 2,    /* more than one */
+  MAGOT_VCF_HEADER_AFTER_DATA = 3,
+  MAGOT_VCF_NO_SAMPLES = 4,      /* the '#' line has fewer than 10 fields */
+  MAGOT_VCF_TOO_MANY_SAMPLES = 5,/* more than 1024: the parse kernel's LDS */
+  MAGOT_VCF_NO_DATA = 6,
+  MAGOT_VCF_FIELD_COUNT = 7,     /* a data line without exactly 9 + S fields */
+  MAGOT_VCF_CHROM_FORM = 8,      /* CHROM holds "<:>" */
+  MAGOT_VCF_POS_FORM = 9,        /* POS is not digits alone without a leading zero */
+  MAGOT_VCF_POS_RANGE = 10,      /* more than 10 digits, or above 2^31 - 1 */
+  MAGOT_VCF_NO_GT = 11,          /* FORMAT without GT */
+  MAGOT_VCF_EMPTY_GT = 12,       /* a sample column without a GT subfield, or an empty one */
+  MAGOT_VCF_EQUALS_FIXED = 13,   /* a sample column equal to one of fields 0-8 */
+  MAGOT_VCF_TOO_LARGE = 14,      /* the text is longer than max_bytes */
+  MAGOT_VCF_TOO_MANY_LINES = 15, /* more than 2^31 - 1 lines: 32-bit line numbers */
+  MAGOT_VCF_TOO_MANY_RUNS = 16,  /* more than 2^20 CHROM runs: the host names each */
+  MAGOT_VCF_LINE_TOO_LONG = 17,  /* 2^31 bytes or more: 32-bit field starts */
+  MAGOT_VCF_TOO_MANY_COUNTS = 18,/* loci x samples above 2^29: 2 GiB of counters */
+  MAGOT_VCF_CARRIAGE_RETURN = 19 /* a CR anywhere: read_vcf drops every CR before it splits */
+};
+typedef struct magot_vcf magot_vcf;
+int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max_bytes,
+                    uint32_t max_samples, uint32_t max_runs, magot_vcf** out, uint32_t* reason,
+                    uint64_t* line);
+int magot_vcf_sizes(const magot_vcf* p, uint64_t* n_lines, uint64_t* n_data, uint64_t* n_hdr,
+                    uint32_t* n_samples, uint32_t* words, uint64_t* n_runs, uint64_t* head_off,
+                    uint64_t* head_len);
+double magot_vcf_upload_ms(const magot_vcf* p);
+int magot_vcf_header_lines(magot_ctx* ctx, magot_vcf* p, uint64_t* off, uint64_t* len);
+int magot_vcf_runs(magot_ctx* ctx, magot_vcf* p, uint64_t* off, uint64_t* len);
+int magot_vcf_resolve(magot_ctx* ctx, magot_vcf* p, const uint32_t* contig, uint64_t n_runs);
+int magot_vcf_tables(magot_ctx* ctx, magot_vcf* p, uint32_t* line, int32_t* pos, uint64_t* hash,
+                     uint8_t* kept, uint8_t* first, uint32_t* bits);
+int magot_vcf_last_of(magot_ctx* ctx, magot_vcf* p, uint64_t d, uint64_t* line, uint64_t* off,
+                      uint64_t* len);
+int magot_vcf_count(magot_ctx* ctx, magot_vcf* p, const uint32_t* contig, const uint32_t* lo,
+                    const uint32_t* hi, uint64_t n_loci, const uint32_t* allowed, uint32_t* counts,
+                    uint32_t* foreign, uint32_t* reason);
+int magot_vcf_time(magot_ctx* ctx, magot_vcf* p, int iters, double* ms8, uint64_t* text_bytes);
+void magot_vcf_params(uint32_t* split_rows, uint32_t* max_samples, uint32_t* max_runs,
+                      uint64_t* max_counts);
+void magot_vcf_destroy(magot_vcf* p);
+int magot_vcf_render(const char* loci, const uint64_t* loci_off, const int64_t* seqlen,
+                     const uint32_t* counts, uint64_t n_loci, uint32_t n_samples,
+                     const uint32_t* cols, uint32_t n_cols, uint32_t n_threads, uint8_t** text,
+                     uint64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

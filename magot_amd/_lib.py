@@ -71,6 +71,10 @@ EXPORTS = (
     'magot_psl_render',
     'magot_site_create', 'magot_site_execute', 'magot_site_counts', 'magot_site_time',
     'magot_site_params', 'magot_site_destroy', 'magot_site_render', 'magot_site_text_free',
+    'magot_vcf_parse', 'magot_vcf_sizes', 'magot_vcf_upload_ms', 'magot_vcf_header_lines',
+    'magot_vcf_runs', 'magot_vcf_resolve', 'magot_vcf_tables', 'magot_vcf_last_of',
+    'magot_vcf_count', 'magot_vcf_time', 'magot_vcf_params', 'magot_vcf_destroy',
+    'magot_vcf_render',
 )
 
 ERR_ARG = -1
@@ -105,6 +109,11 @@ OVERLAP_REASONS = (None, 'bad integer in the first file', 'bad integer in the se
 # magot_psl_parse's reasons (MAGOT_PSL_*), by code
 PSL_REASONS = (None, 'few_fields', 'integer_form', 'number_range', 'hash_collision', 'too_large',
                'too_many_lines')
+# magot_vcf_parse's and magot_vcf_count's reasons (MAGOT_VCF_*), by code
+VCF_REASONS = (None, 'no_header', 'many_headers', 'header_after_data', 'no_samples',
+               'too_many_samples', 'no_data', 'field_count', 'chrom_form', 'pos_form', 'pos_range',
+               'no_gt', 'empty_gt', 'equals_fixed', 'too_large', 'too_many_lines', 'too_many_runs',
+               'line_too_long', 'too_many_counts', 'carriage_return')
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -335,6 +344,27 @@ def _declare(lib):
         'magot_site_render': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint32,
                                              ctypes.POINTER(_vp), _u64p, _u64p]),
         'magot_site_text_free': (None, [_vp]),
+        'magot_vcf_parse': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp),
+                                           ctypes.POINTER(ctypes.c_uint32), _u64p]),
+        'magot_vcf_sizes': (ctypes.c_int, [_vp, _u64p, _u64p, _u64p,
+                                           ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32), _u64p, _u64p, _u64p]),
+        'magot_vcf_upload_ms': (ctypes.c_double, [_vp]),
+        'magot_vcf_header_lines': (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+        'magot_vcf_runs': (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+        'magot_vcf_resolve': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_vcf_tables': (ctypes.c_int, [_vp] * 8),
+        'magot_vcf_last_of': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _u64p, _u64p, _u64p]),
+        'magot_vcf_count': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp,
+                                           ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32)]),
+        'magot_vcf_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p]),
+        'magot_vcf_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3 + [_u64p]),
+        'magot_vcf_destroy': (None, [_vp]),
+        'magot_vcf_render': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
+                                            _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.POINTER(_vp), _u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

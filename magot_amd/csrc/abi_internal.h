@@ -121,6 +121,22 @@ inline int ensure_pin_ring(magot_ctx* ctx) {  // callers hold ctx->pin_mu
   return MAGOT_OK;
 }
 
+// A text into its device buffer through the context's two pinned buffers
+// (magot_psl_parse, magot_vcf_parse).
+inline int upload_text(magot_ctx* ctx, const char* text, uint64_t len, uint8_t* dev) {
+  std::lock_guard<std::mutex> lock(ctx->pin_mu);
+  if (int rc = ensure_pin_ring(ctx)) return rc;
+  int b = 0;
+  for (uint64_t q0 = 0; q0 < len; q0 += kPinRing, b ^= 1) {
+    const uint64_t n = std::min(kPinRing, len - q0);
+    MAGOT_HIP_TRY(hipEventSynchronize(ctx->pin_ev[b]));  // the buffer's previous copy has drained
+    std::memcpy(ctx->pin[b], text + q0, n);
+    MAGOT_HIP_TRY(hipMemcpyAsync(dev + q0, ctx->pin[b], n, hipMemcpyHostToDevice, ctx->stream));
+    MAGOT_HIP_TRY(hipEventRecord(ctx->pin_ev[b], ctx->stream));
+  }
+  return MAGOT_OK;
+}
+
 // RAII device scratch
 struct DevBuf {
   void* p = nullptr;

@@ -21,21 +21,6 @@ namespace {
 
 constexpr int kPslPasses = 8;
 
-// The text into its device buffer through the context's two pinned buffers.
-int psl_upload(magot_ctx* ctx, const char* text, uint64_t len, uint8_t* dev) {
-  std::lock_guard<std::mutex> lock(ctx->pin_mu);
-  if (int rc = ensure_pin_ring(ctx)) return rc;
-  int b = 0;
-  for (uint64_t q0 = 0; q0 < len; q0 += kPinRing, b ^= 1) {
-    const uint64_t n = std::min(kPinRing, len - q0);
-    MAGOT_HIP_TRY(hipEventSynchronize(ctx->pin_ev[b]));  // the buffer's previous copy has drained
-    std::memcpy(ctx->pin[b], text + q0, n);
-    MAGOT_HIP_TRY(hipMemcpyAsync(dev + q0, ctx->pin[b], n, hipMemcpyHostToDevice, ctx->stream));
-    MAGOT_HIP_TRY(hipEventRecord(ctx->pin_ev[b], ctx->stream));
-  }
-  return MAGOT_OK;
-}
-
 // pass k of magot_psl_time on the handle's own buffers
 hipError_t psl_pass(const magot_psl* p, int k, hipStream_t s) {
   const PslArgs& a = p->a;
@@ -132,7 +117,7 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     a.status = reinterpret_cast<unsigned long long*>(base + o_status);
     a.n_uniq = a.status + 1;
     MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
-    if (int rc = psl_upload(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
+    if (int rc = upload_text(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
     MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
     MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
     MAGOT_HIP_TRY(launch_psl_count(a, p->tmp0, p->tmp0_bytes, s));

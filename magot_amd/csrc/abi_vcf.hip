@@ -1,0 +1,436 @@
+// C ABI: heterozygosity_from_vcf's parse, sort and counting on the device
+// (vcf.hip; magot_variants.py:16-139).  The text is made resident and indexed
+// as a PSL's (upload_text, psl.hip's line index).  The renderer is in
+// vcfhost.cpp.
+#include "abi_internal.h"
+
+using namespace magot;
+
+struct magot_vcf {
+  magot_ctx* ctx = nullptr;
+  void* text_mem = nullptr;  // the text, the block counts and their scan's scratch
+  void* mem = nullptr;       // everything sized by the lines
+  void* data_mem = nullptr;  // everything sized by the data lines
+  void* loci_mem = nullptr;  // the last magot_vcf_count's tables
+  void* copy_mem = nullptr;  // magot_vcf_time's copy target
+  PslArgs ix{};              // the line index
+  VcfArgs a{};
+  VcfCountArgs c{};
+  void *tmp0 = nullptr, *tmp = nullptr, *ctmp = nullptr;
+  size_t tmp0_bytes = 0, tmp_bytes = 0, ctmp_bytes = 0;
+  uint32_t* last_line = nullptr;
+  uint64_t head_off = 0, head_len = 0;
+  bool resolved = false;
+  float upload_ms = 0.f;
+};
+
+namespace {
+
+constexpr int kVcfPasses = 8;
+
+int vcf_decline(uint32_t* reason, uint64_t* line, uint32_t why, uint64_t at) {
+  if (reason) *reason = why;
+  if (line) *line = at;
+  set_error("magot_vcf_parse: input outside the device path; use the host functions");
+  return MAGOT_ERR_UNSUPPORTED;
+}
+
+template <class T>
+int vcf_fetch(T* dst, const T* src, uint64_t n) {
+  if (dst && n) MAGOT_HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+// the span of 0-based line k without its LF
+int vcf_line_span(const magot_vcf* p, const char* host_text, uint64_t k, uint64_t* off,
+                  uint64_t* len) {
+  uint64_t se[2] = {0, 0};
+  MAGOT_HIP_TRY(hipMemcpy(se, p->ix.line_start + k, sizeof se, hipMemcpyDeviceToHost));
+  uint8_t last = 0;
+  if (host_text) last = (uint8_t)host_text[se[1] - 1];
+  else MAGOT_HIP_TRY(hipMemcpy(&last, p->a.text + se[1] - 1, 1, hipMemcpyDeviceToHost));
+  *off = se[0];
+  *len = se[1] - se[0] - (last == '\n' ? 1 : 0);
+  return MAGOT_OK;
+}
+
+hipError_t vcf_pass(const magot_vcf* p, int k, hipStream_t s) {
+  const VcfArgs& a = p->a;
+  switch (k) {
+    case 0:
+      if (hipError_t e = launch_psl_count(p->ix, p->tmp0, p->tmp0_bytes, s)) return e;
+      return launch_psl_fill(p->ix, s);
+    case 1:
+      if (hipError_t e = launch_vcf_classify(a, p->tmp, p->tmp_bytes, s)) return e;
+      return launch_vcf_compact(a, s);
+    case 2: return launch_vcf_parse(a, s);
+    case 3:
+      if (hipError_t e = launch_vcf_runs_scan(a, p->tmp, p->tmp_bytes, s)) return e;
+      return launch_vcf_runs(a, s);
+    case 4: return p->resolved ? launch_vcf_sort(a, p->tmp, p->tmp_bytes, s) : hipSuccess;
+    case 5: return p->resolved ? launch_vcf_flags(a, s) : hipSuccess;
+    case 6:
+      if (!p->loci_mem) return hipSuccess;
+      if (hipError_t e = launch_vcf_ranges(a, p->c, p->ctmp, p->ctmp_bytes, s)) return e;
+      return launch_vcf_count(a, p->c, s);
+    default: return hipMemcpyAsync(p->copy_mem, a.text, a.n, hipMemcpyDeviceToDevice, s);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+void magot_vcf_destroy(magot_vcf* p) {
+  if (!p) return;
+  if (p->ctx) (void)hipSetDevice(p->ctx->device);
+  for (void* m : {p->copy_mem, p->loci_mem, p->data_mem, p->mem, p->text_mem})
+    if (m) (void)hipFree(m);
+  delete p;
+}
+
+void magot_vcf_params(uint32_t* split_rows, uint32_t* max_samples, uint32_t* max_runs,
+                      uint64_t* max_counts) {
+  if (split_rows) *split_rows = kVcfSplit;
+  if (max_samples) *max_samples = kVcfMaxSamples;
+  if (max_runs) *max_runs = kVcfMaxRuns;
+  if (max_counts) *max_counts = kVcfMaxCounts;
+}
+
+int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max_bytes,
+                    uint32_t max_samples, uint32_t max_runs, magot_vcf** out, uint32_t* reason,
+                    uint64_t* line) {
+  if (int rc = bind(ctx)) return rc;
+  if (!out || (len && !text)) {
+    set_error("magot_vcf_parse: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  *out = nullptr;
+  if (reason) *reason = 0;
+  if (line) *line = 0;
+  if (!max_samples || max_samples > kVcfMaxSamples) max_samples = kVcfMaxSamples;
+  if (!max_runs || max_runs > kVcfMaxRuns) max_runs = kVcfMaxRuns;
+  if (!max_bytes) {  // the bit rows and the line tables beside the text
+    size_t free_b = 0, total_b = 0;
+    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    max_bytes = free_b / 4;
+  }
+  if (len > max_bytes) return vcf_decline(reason, line, MAGOT_VCF_TOO_LARGE, 0);
+  if (!len) return vcf_decline(reason, line, MAGOT_VCF_NO_HEADER, 0);
+
+  struct Guard {
+    magot_vcf* p;
+    ~Guard() { magot_vcf_destroy(p); }
+  } guard{new magot_vcf()};
+  magot_vcf* p = guard.p;
+  p->ctx = ctx;
+  PslArgs& ix = p->ix;
+  VcfArgs& a = p->a;
+  hipStream_t s = ctx->stream;
+  ix.n = a.n = len;
+  ix.n_blocks = depth_text_blocks(len);
+  ix.hash_bits = 64;
+  {
+    p->tmp0_bytes = psl_count_tmp_bytes(ix.n_blocks);
+    Carve cv;
+    const uint64_t o_text = cv.take<uint8_t>(len + 32);  // a 16-byte load at the last byte
+    const uint64_t o_blk = cv.take<uint64_t>(ix.n_blocks + 1);
+    const uint64_t o_pre = cv.take<uint64_t>(ix.n_blocks + 1);
+    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp0_bytes);
+    const uint64_t o_status = cv.take<unsigned long long>(8);
+    const uint64_t o_last = cv.take<uint32_t>(1);
+    MAGOT_HIP_TRY(hipMalloc(&p->text_mem, cv.used + 256));
+    char* base = static_cast<char*>(p->text_mem);
+    ix.text = a.text = reinterpret_cast<const uint8_t*>(base + o_text);
+    ix.blk = reinterpret_cast<uint64_t*>(base + o_blk);
+    ix.pre = reinterpret_cast<uint64_t*>(base + o_pre);
+    p->tmp0 = base + o_tmp;
+    a.status = reinterpret_cast<unsigned long long*>(base + o_status);
+    p->last_line = reinterpret_cast<uint32_t*>(base + o_last);
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
+    if (int rc = upload_text(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
+    MAGOT_HIP_TRY(launch_psl_count(ix, p->tmp0, p->tmp0_bytes, s));
+    uint64_t lfs = 0;
+    MAGOT_HIP_TRY(hipMemcpyAsync(&lfs, ix.pre + ix.n_blocks, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+    MAGOT_HIP_TRY(hipEventElapsedTime(&p->upload_ms, ctx->ev0, ctx->ev1));
+    ix.n_lines = lfs + (text[len - 1] != '\n' ? 1 : 0);
+    if (ix.n_lines > kPslLineMask) return vcf_decline(reason, line, MAGOT_VCF_TOO_MANY_LINES, 0);
+  }
+  const uint64_t L = a.n_lines = ix.n_lines;  // at least 1
+  a.final_lf = text[len - 1] == '\n' ? 1 : 0;
+  {
+    p->tmp_bytes = vcf_tmp_bytes(L);
+    Carve cv;
+    const uint64_t o_start = cv.take<uint64_t>(L + 1);
+    const uint64_t o_kind = cv.take<uint64_t>(L + 1), o_kpos = cv.take<uint64_t>(L + 1);
+    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
+    MAGOT_HIP_TRY(hipMalloc(&p->mem, cv.used + 256));
+    char* base = static_cast<char*>(p->mem);
+    ix.line_start = reinterpret_cast<uint64_t*>(base + o_start);
+    a.line_start = ix.line_start;
+    a.kind = reinterpret_cast<uint64_t*>(base + o_kind);
+    a.kpos = reinterpret_cast<uint64_t*>(base + o_kpos);
+    p->tmp = base + o_tmp;
+  }
+  MAGOT_HIP_TRY(launch_psl_fill(ix, s));
+  MAGOT_HIP_TRY(launch_vcf_classify(a, p->tmp, p->tmp_bytes, s));
+  unsigned long long st[5] = {0, 0, 0, 0, 0};
+  uint64_t totals = 0;
+  MAGOT_HIP_TRY(hipMemcpyAsync(st, a.status, sizeof st, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(&totals, a.kpos + L, 8, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  a.n_data = totals & 0xffffffffull;
+  a.n_hdr = totals >> 32;
+  if (st[4]) return vcf_decline(reason, line, MAGOT_VCF_CARRIAGE_RETURN, 0);
+  if (st[1] == 0) return vcf_decline(reason, line, MAGOT_VCF_NO_HEADER, 0);
+  if (st[1] > 1) return vcf_decline(reason, line, MAGOT_VCF_MANY_HEADERS, 0);
+  if (!a.n_data) return vcf_decline(reason, line, MAGOT_VCF_NO_DATA, 0);
+  if (st[3] < st[2]) return vcf_decline(reason, line, MAGOT_VCF_HEADER_AFTER_DATA, st[3] + 1);
+  // S from the '#' line: the fields of the text behind '#', less nine
+  if (int rc = vcf_line_span(p, text, st[2], &p->head_off, &p->head_len)) return rc;
+  uint64_t fields = 1;
+  for (uint64_t i = 1; i < p->head_len; ++i) fields += text[p->head_off + i] == '\t';
+  if (fields < 10) return vcf_decline(reason, line, MAGOT_VCF_NO_SAMPLES, st[2] + 1);
+  if (fields - 9 > max_samples) return vcf_decline(reason, line, MAGOT_VCF_TOO_MANY_SAMPLES, st[2] + 1);
+  a.n_samples = (uint32_t)(fields - 9);
+  a.words = (a.n_samples + 31) / 32;
+  {
+    const uint64_t D = a.n_data;
+    Carve cv;
+    const uint64_t o_dl = cv.take<uint32_t>(D), o_ho = cv.take<uint64_t>(a.n_hdr + 1);
+    const uint64_t o_hn = cv.take<uint64_t>(a.n_hdr + 1);
+    const uint64_t o_pos = cv.take<int32_t>(D), o_hash = cv.take<uint64_t>(D);
+    const uint64_t o_cl = cv.take<uint32_t>(D);
+    const uint64_t o_head = cv.take<uint32_t>(D + 1), o_run = cv.take<uint32_t>(D + 1);
+    const uint64_t o_bits = cv.take<uint32_t>(D * a.words);
+    const uint64_t o_roff = cv.take<uint64_t>(max_runs), o_rlen = cv.take<uint64_t>(max_runs);
+    const uint64_t o_cor = cv.take<uint32_t>(max_runs);
+    const uint64_t o_key = cv.take<uint64_t>(D), o_key2 = cv.take<uint64_t>(D);
+    const uint64_t o_val = cv.take<uint32_t>(D), o_val2 = cv.take<uint32_t>(D);
+    const uint64_t o_ks = cv.take<uint8_t>(D), o_kept = cv.take<uint8_t>(D);
+    const uint64_t o_first = cv.take<uint8_t>(D);
+    MAGOT_HIP_TRY(hipMalloc(&p->data_mem, cv.used + 256));
+    char* base = static_cast<char*>(p->data_mem);
+    a.data_line = reinterpret_cast<uint32_t*>(base + o_dl);
+    a.hdr_off = reinterpret_cast<uint64_t*>(base + o_ho);
+    a.hdr_len = reinterpret_cast<uint64_t*>(base + o_hn);
+    a.pos = reinterpret_cast<int32_t*>(base + o_pos);
+    a.hash = reinterpret_cast<uint64_t*>(base + o_hash);
+    a.chrom_len = reinterpret_cast<uint32_t*>(base + o_cl);
+    a.head = reinterpret_cast<uint32_t*>(base + o_head);
+    a.run = reinterpret_cast<uint32_t*>(base + o_run);
+    a.bits = reinterpret_cast<uint32_t*>(base + o_bits);
+    a.run_off = reinterpret_cast<uint64_t*>(base + o_roff);
+    a.run_len = reinterpret_cast<uint64_t*>(base + o_rlen);
+    a.contig_of_run = reinterpret_cast<const uint32_t*>(base + o_cor);
+    a.key = reinterpret_cast<uint64_t*>(base + o_key);
+    a.key_sorted = reinterpret_cast<uint64_t*>(base + o_key2);
+    a.val = reinterpret_cast<uint32_t*>(base + o_val);
+    a.val_sorted = reinterpret_cast<uint32_t*>(base + o_val2);
+    a.kept_sorted = reinterpret_cast<uint8_t*>(base + o_ks);
+    a.kept = reinterpret_cast<uint8_t*>(base + o_kept);
+    a.first = reinterpret_cast<uint8_t*>(base + o_first);
+    MAGOT_HIP_TRY(hipMemsetAsync(a.kept, 0, D, s));
+    MAGOT_HIP_TRY(hipMemsetAsync(a.first, 0, D, s));
+  }
+  MAGOT_HIP_TRY(launch_vcf_compact(a, s));
+  MAGOT_HIP_TRY(launch_vcf_parse(a, s));
+  MAGOT_HIP_TRY(launch_vcf_runs_scan(a, p->tmp, p->tmp_bytes, s));
+  uint32_t n_runs = 0;
+  MAGOT_HIP_TRY(hipMemcpyAsync(st, a.status, 8, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(&n_runs, a.run + a.n_data, 4, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  if (st[0] != ~0ull)
+    return vcf_decline(reason, line, (uint32_t)(st[0] & 0xff), (st[0] >> 8) + 1);
+  if (n_runs > max_runs) return vcf_decline(reason, line, MAGOT_VCF_TOO_MANY_RUNS, 0);
+  a.n_runs = n_runs;  // the run tables hold max_runs
+  MAGOT_HIP_TRY(launch_vcf_runs(a, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  guard.p = nullptr;
+  *out = p;
+  return MAGOT_OK;
+}
+
+int magot_vcf_sizes(const magot_vcf* p, uint64_t* n_lines, uint64_t* n_data, uint64_t* n_hdr,
+                    uint32_t* n_samples, uint32_t* words, uint64_t* n_runs, uint64_t* head_off,
+                    uint64_t* head_len) {
+  if (!p) {
+    set_error("magot_vcf_sizes: null handle");
+    return MAGOT_ERR_ARG;
+  }
+  if (n_lines) *n_lines = p->a.n_lines;
+  if (n_data) *n_data = p->a.n_data;
+  if (n_hdr) *n_hdr = p->a.n_hdr;
+  if (n_samples) *n_samples = p->a.n_samples;
+  if (words) *words = p->a.words;
+  if (n_runs) *n_runs = p->a.n_runs;
+  if (head_off) *head_off = p->head_off;
+  if (head_len) *head_len = p->head_len;
+  return MAGOT_OK;
+}
+
+double magot_vcf_upload_ms(const magot_vcf* p) { return p ? (double)p->upload_ms : 0.0; }
+
+int magot_vcf_header_lines(magot_ctx* ctx, magot_vcf* p, uint64_t* off, uint64_t* len) {
+  if (int rc = handle_of(ctx, p, "magot_vcf_header_lines", "handle")) return rc;
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (int rc = vcf_fetch(off, p->a.hdr_off, p->a.n_hdr)) return rc;
+  return vcf_fetch(len, p->a.hdr_len, p->a.n_hdr);
+}
+
+int magot_vcf_runs(magot_ctx* ctx, magot_vcf* p, uint64_t* off, uint64_t* len) {
+  if (int rc = handle_of(ctx, p, "magot_vcf_runs", "handle")) return rc;
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (int rc = vcf_fetch(off, p->a.run_off, p->a.n_runs)) return rc;
+  return vcf_fetch(len, p->a.run_len, p->a.n_runs);
+}
+
+int magot_vcf_resolve(magot_ctx* ctx, magot_vcf* p, const uint32_t* contig, uint64_t n_runs) {
+  if (int rc = handle_of(ctx, p, "magot_vcf_resolve", "handle")) return rc;
+  VcfArgs& a = p->a;
+  if (!contig || n_runs != a.n_runs) {
+    set_error("magot_vcf_resolve: one contig per run");
+    return MAGOT_ERR_ARG;
+  }
+  uint32_t top = 0;
+  for (uint64_t r = 0; r < n_runs; ++r) top = std::max(top, contig[r]);
+  a.key_bits = 32;
+  while (a.key_bits < 64 && (top >> (a.key_bits - 32))) ++a.key_bits;
+  hipStream_t s = ctx->stream;
+  MAGOT_HIP_TRY(hipMemcpyAsync(const_cast<uint32_t*>(a.contig_of_run), contig,
+                               n_runs * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));  // the caller's array is read
+  p->resolved = true;
+  MAGOT_HIP_TRY(launch_vcf_sort(a, p->tmp, p->tmp_bytes, s));
+  MAGOT_HIP_TRY(launch_vcf_flags(a, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  return MAGOT_OK;
+}
+
+int magot_vcf_tables(magot_ctx* ctx, magot_vcf* p, uint32_t* line, int32_t* pos, uint64_t* hash,
+                     uint8_t* kept, uint8_t* first, uint32_t* bits) {
+  if (int rc = handle_of(ctx, p, "magot_vcf_tables", "handle")) return rc;
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const VcfArgs& a = p->a;
+  const uint64_t n = a.n_data;
+  if (int rc = vcf_fetch(line, a.data_line, n)) return rc;
+  if (int rc = vcf_fetch(pos, a.pos, n)) return rc;
+  if (int rc = vcf_fetch(hash, a.hash, n)) return rc;
+  if (int rc = vcf_fetch(kept, a.kept, n)) return rc;
+  if (int rc = vcf_fetch(first, a.first, n)) return rc;
+  return vcf_fetch(bits, a.bits, n * a.words);
+}
+
+int magot_vcf_last_of(magot_ctx* ctx, magot_vcf* p, uint64_t d, uint64_t* line, uint64_t* off,
+                      uint64_t* len) {
+  if (int rc = handle_of(ctx, p, "magot_vcf_last_of", "handle")) return rc;
+  if (!p->resolved || d >= p->a.n_data || !line || !off || !len) {
+    set_error("magot_vcf_last_of: before magot_vcf_resolve, no such data line, or null argument");
+    return p->resolved ? MAGOT_ERR_ARG : MAGOT_ERR_STATE;
+  }
+  hipStream_t s = ctx->stream;
+  MAGOT_HIP_TRY(launch_vcf_last_of(p->a, d, p->last_line, s));
+  uint32_t ln = 0;
+  MAGOT_HIP_TRY(hipMemcpyAsync(&ln, p->last_line, 4, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  *line = ln;
+  return vcf_line_span(p, nullptr, ln, off, len);
+}
+
+int magot_vcf_count(magot_ctx* ctx, magot_vcf* p, const uint32_t* contig, const uint32_t* lo,
+                    const uint32_t* hi, uint64_t n_loci, const uint32_t* allowed, uint32_t* counts,
+                    uint32_t* foreign, uint32_t* reason) {
+  if (int rc = handle_of(ctx, p, "magot_vcf_count", "handle")) return rc;
+  if (reason) *reason = 0;
+  if (!p->resolved) {
+    set_error("magot_vcf_count: before magot_vcf_resolve");
+    return MAGOT_ERR_STATE;
+  }
+  const VcfArgs& a = p->a;
+  if (n_loci > kVcfMaxCounts || n_loci * a.n_samples > kVcfMaxCounts) {  // before any table is read
+    if (reason) *reason = MAGOT_VCF_TOO_MANY_COUNTS;
+    set_error("magot_vcf_count: more counters than the device path takes");
+    return MAGOT_ERR_UNSUPPORTED;
+  }
+  if (!allowed || !foreign || (n_loci && (!contig || !lo || !hi || !counts))) {
+    set_error("magot_vcf_count: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  *foreign = 0;
+  if (!n_loci) return MAGOT_OK;
+  if (p->loci_mem) {
+    MAGOT_HIP_TRY(hipFree(p->loci_mem));
+    p->loci_mem = nullptr;
+  }
+  VcfCountArgs& c = p->c;
+  c = VcfCountArgs{};
+  c.n_loci = n_loci;
+  p->ctmp_bytes = vcf_count_tmp_bytes(n_loci);
+  Carve cv;
+  const uint64_t o_c = cv.take<uint32_t>(n_loci), o_lo = cv.take<uint32_t>(n_loci);
+  const uint64_t o_hi = cv.take<uint32_t>(n_loci);
+  const uint64_t o_b = cv.take<uint64_t>(n_loci), o_e = cv.take<uint64_t>(n_loci);
+  const uint64_t o_pc = cv.take<uint64_t>(n_loci + 1), o_po = cv.take<uint64_t>(n_loci + 1);
+  const uint64_t o_al = cv.take<uint32_t>(a.words), o_fg = cv.take<uint32_t>(1);
+  const uint64_t o_cnt = cv.take<uint32_t>(n_loci * a.n_samples);
+  const uint64_t o_tmp = cv.take<uint8_t>(p->ctmp_bytes);
+  MAGOT_HIP_TRY(hipMalloc(&p->loci_mem, cv.used + 256));
+  char* base = static_cast<char*>(p->loci_mem);
+  uint32_t* d_c = reinterpret_cast<uint32_t*>(base + o_c);
+  uint32_t* d_lo = reinterpret_cast<uint32_t*>(base + o_lo);
+  uint32_t* d_hi = reinterpret_cast<uint32_t*>(base + o_hi);
+  uint32_t* d_al = reinterpret_cast<uint32_t*>(base + o_al);
+  c.contig = d_c;
+  c.lo = d_lo;
+  c.hi = d_hi;
+  c.allowed = d_al;
+  c.rng_b = reinterpret_cast<uint64_t*>(base + o_b);
+  c.rng_e = reinterpret_cast<uint64_t*>(base + o_e);
+  c.pieces = reinterpret_cast<uint64_t*>(base + o_pc);
+  c.piece_off = reinterpret_cast<uint64_t*>(base + o_po);
+  c.foreign = reinterpret_cast<uint32_t*>(base + o_fg);
+  c.counts = reinterpret_cast<uint32_t*>(base + o_cnt);
+  p->ctmp = base + o_tmp;
+  hipStream_t s = ctx->stream;
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_c, contig, n_loci * 4, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_lo, lo, n_loci * 4, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_hi, hi, n_loci * 4, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_al, allowed, a.words * 4, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(launch_vcf_ranges(a, c, p->ctmp, p->ctmp_bytes, s));
+  uint64_t n_pieces = 0;
+  MAGOT_HIP_TRY(hipMemcpyAsync(&n_pieces, c.piece_off + n_loci, 8, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  if (n_pieces > 0x7fffffffull) {
+    set_error("magot_vcf_count: more pieces than one launch holds");
+    return MAGOT_ERR_RANGE;
+  }
+  c.n_pieces = n_pieces;
+  MAGOT_HIP_TRY(launch_vcf_count(a, c, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(counts, c.counts, n_loci * a.n_samples * 4, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(foreign, c.foreign, 4, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  return MAGOT_OK;
+}
+
+int magot_vcf_time(magot_ctx* ctx, magot_vcf* p, int iters, double* ms8, uint64_t* text_bytes) {
+  if (int rc = handle_of(ctx, p, "magot_vcf_time", "handle")) return rc;
+  if (iters <= 0 || !ms8) {
+    set_error("magot_vcf_time: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  if (text_bytes) *text_bytes = p->a.n;
+  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.n + 256));
+  // every pass writes what it wrote before: the answers stand
+  double total[kVcfPasses] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < iters; ++i)
+    for (int k = 0; k < kVcfPasses; ++k)
+      if (int rc = time_pass(ctx, &total[k],
+                             [&]() -> hipError_t { return vcf_pass(p, k, ctx->stream); }))
+        return rc;
+  for (int k = 0; k < kVcfPasses; ++k) ms8[k] = total[k] / iters;
+  return MAGOT_OK;
+}
+
+}  // extern "C"

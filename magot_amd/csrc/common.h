@@ -903,6 +903,78 @@ struct SiteArgs {
 // zeroes the counts first when there are several strips
 hipError_t launch_site_count(const SiteArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// heterozygosity_from_vcf (vcf.hip; magot_variants.py:16-139; magot_vcf_*)
+// ---------------------------------------------------------------------------
+// The text is resident and indexed by psl.hip's line index.  Data lines are
+// compacted, parsed a wave each into (POS, key hash, CHROM run head, one het bit
+// per sample column), keyed (contig << 32 | POS) once the host has named the
+// runs' contigs, and sorted; a locus is a range of the sorted keys.
+constexpr uint32_t kVcfMaxSamples = 1024;  // the parse kernel's LDS: column starts and the field table
+constexpr uint32_t kVcfTable = 4096;       // its slots: the power of two above 2 * (9 + kVcfMaxSamples)
+constexpr uint32_t kVcfSplit = 4096;       // sorted rows one workgroup of the counting pass goes down
+constexpr uint32_t kVcfMaxRuns = 1u << 20; // CHROM runs the host names one by one
+constexpr uint64_t kVcfMaxCounts = 1ull << 29;  // loci x samples (2 GiB of counters)
+struct VcfArgs {
+  const uint8_t* text;  // n bytes, 16-byte aligned, readable to the next multiple of 16 and 16 more
+  uint64_t n;
+  uint64_t n_lines;
+  uint32_t final_lf;             // 1: the text's last byte is LF (every line has one)
+  const uint64_t* line_start;  // n_lines + 1 (PslArgs::line_start)
+  // per line: 1 for a data line, 1 << 32 for a "##" line; n_lines + 1, the last 0
+  uint64_t* kind;
+  uint64_t* kpos;  // their exclusive scan: both counts before each line, the totals last
+  // [0] min of (line << 8 | MAGOT_VCF_* reason), ~0 when clean; [1] the '#' lines
+  // that are not "##"; [2] the first of them; [3] the first data line; [4] 1 when
+  // the text holds a CR
+  unsigned long long* status;
+  uint64_t n_data, n_hdr;
+  uint32_t n_samples, words;  // words = ceil(n_samples / 32)
+  uint32_t* data_line;  // n_data: the line of each data line
+  uint64_t *hdr_off, *hdr_len;  // n_hdr: the "##" lines without their LFs, in file order
+  // per data line
+  int32_t* pos;
+  uint64_t* hash;       // CPython 2.7's string hash of CHROM + "<:>" + POS
+  uint32_t* chrom_len;
+  uint32_t* head;       // n_data + 1: 1 where CHROM differs from the data line before; the last 0
+  uint32_t* run;        // their exclusive scan; run[n_data]: the runs
+  uint32_t* bits;       // n_data x words: bit s: column s is the line's first field with its
+                        // bytes and its GT's first and last byte differ
+  uint64_t n_runs;
+  uint64_t *run_off, *run_len;  // n_runs: the CHROM span of each run's first line
+  // after the host has named the runs
+  const uint32_t* contig_of_run;  // n_runs
+  uint32_t key_bits;
+  uint64_t *key, *key_sorted;     // n_data
+  uint32_t *val, *val_sorted;     // the data line of each key; sorted stably
+  uint8_t* kept_sorted;           // 1: the last line of its key
+  uint8_t *kept, *first;          // per data line: the last, the first line of its key
+};
+struct VcfCountArgs {
+  uint64_t n_loci;
+  const uint32_t *contig, *lo, *hi;  // n_loci; lo > hi: no position
+  uint64_t *rng_b, *rng_e;           // the locus as rows [b, e) of the sorted keys
+  uint64_t *pieces, *piece_off;      // n_loci + 1: pieces of kVcfSplit rows, and their scan
+  uint64_t n_pieces;
+  const uint32_t* allowed;           // words: the columns the first variant names
+  uint32_t* counts;                  // n_loci x n_samples
+  uint32_t* foreign;                 // set when a counted row holds a het bit outside `allowed`
+};
+size_t vcf_tmp_bytes(uint64_t n_lines);
+size_t vcf_count_tmp_bytes(uint64_t n_loci);
+hipError_t launch_vcf_classify(const VcfArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_vcf_compact(const VcfArgs& a, hipStream_t s);
+hipError_t launch_vcf_parse(const VcfArgs& a, hipStream_t s);
+hipError_t launch_vcf_runs_scan(const VcfArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_vcf_runs(const VcfArgs& a, hipStream_t s);
+hipError_t launch_vcf_sort(const VcfArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_vcf_flags(const VcfArgs& a, hipStream_t s);
+// out[0]: the line of the kept row whose key is key[d]
+hipError_t launch_vcf_last_of(const VcfArgs& a, uint64_t d, uint32_t* out, hipStream_t s);
+hipError_t launch_vcf_ranges(const VcfArgs& a, const VcfCountArgs& c, void* tmp, size_t tmp_bytes,
+                             hipStream_t s);
+hipError_t launch_vcf_count(const VcfArgs& a, const VcfCountArgs& c, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -55,6 +56,20 @@ void parallel_ranges(uint64_t n, unsigned parts, F fn) {
     pool.emplace_back([&fn, n, parts, k]() { fn(n * k / parts, n * (k + 1) / parts, k); });
   fn(0, n / parts, 0u);
   for (std::thread& th : pool) th.join();
+}
+
+// str(float) of Python 2 into out[kPy2FloatMax]; the bytes written.  '%.12g',
+// and ".0" appended when the result has neither '.' nor 'e' (nor is inf or
+// nan, which the callers' ratios never are).  glibc's printf rounds the exact
+// binary value correctly, as Python's own conversion does.
+constexpr int kPy2FloatMax = 24;  // "3.33333333333e-05" is 17 bytes
+inline int py2_float_str(double v, char* out) {
+  int n = snprintf(out, kPy2FloatMax, "%.12g", v);
+  if (!memchr(out, '.', n) && !memchr(out, 'e', n)) {
+    out[n++] = '.';
+    out[n++] = '0';
+  }
+  return n;
 }
 
 // A host array left uninitialised (POD rows the planner writes itself, in

@@ -28,7 +28,7 @@ namespace magot {
 namespace {
 
 constexpr uint32_t kSmallTotal = 64;
-constexpr int kMaxField = 24;  // "3.33333333333e-05" is 17 bytes
+constexpr int kMaxField = kPy2FloatMax;
 
 struct Field {
   uint8_t len = 0;
@@ -36,13 +36,7 @@ struct Field {
 };
 
 int site_ratio(uint32_t count, uint64_t total, char* out) {
-  const double v = count * 1.0 / (double)total;
-  int n = snprintf(out, kMaxField, "%.12g", v);
-  if (!memchr(out, '.', n) && !memchr(out, 'e', n)) {
-    out[n++] = '.';
-    out[n++] = '0';
-  }
-  return n;
+  return py2_float_str(count * 1.0 / (double)total, out);
 }
 
 // sites [s0, s1) into `out`

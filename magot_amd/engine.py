@@ -1897,6 +1897,196 @@ def render_composition(counts, threads=0):
         L.magot_site_text_free(text)
 
 
+class VariantHets(object):
+    """heterozygosity_from_vcf's tables on the device (magot_vcf_*,
+    magot_variants.py:16-139).  ``parse`` makes the VCF's text resident, indexes
+    its lines and parses every data line, a wave each: POS, CPython 2.7's hash
+    of ``CHROM<:>POS``, CHROM run heads, and per sample column one bit -- the
+    column is the line's first field with its bytes (read_vcf's
+    ``fields.index``) and its GT's first and last byte differ.  ``resolve``
+    takes the contig of every CHROM run, keys the lines (contig, POS) and sorts
+    them: a key's last line is kept.  ``count`` counts the kept lines' bits per
+    locus, a range of the sorted keys.  ``parse`` returns (None, reason) outside
+    the native grammar (_lib.VCF_REASONS).  Spans are (offset, length) into the
+    text without the line's LF."""
+
+    PASSES = ('line_index', 'classify', 'parse', 'runs', 'sort', 'flags', 'count', 'copy')
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.n_lines = self.n_data = self.n_header = self.n_samples = self.words = self.n_runs = 0
+        self.header = (0, 0)
+        self.upload_ms = 0.0
+        self.declined_line = 0
+
+    @classmethod
+    def parse(cls, data, max_bytes=0, max_samples=0, max_runs=0, ctx=None):
+        """``max_bytes``: a longer text is declined (0: a quarter of the free
+        device memory); ``max_samples``, ``max_runs``: lower limits than the
+        device path's own, for tests."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(data)
+        h, reason, line = ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_uint64()
+        rc = _lib.lib().magot_vcf_parse(self.ctx.handle, _text_ptr(view), len(view),
+                                        int(max_bytes or 0), int(max_samples or 0),
+                                        int(max_runs or 0), ctypes.byref(h), ctypes.byref(reason),
+                                        ctypes.byref(line))
+        if rc == _lib.ERR_UNSUPPORTED:
+            VariantHets.last_declined_line = line.value
+            return None, _lib.VCF_REASONS[reason.value]
+        check(rc, 'magot_vcf_parse')
+        self.handle = h
+        n = [ctypes.c_uint64() for _ in range(3)]
+        s, w = ctypes.c_uint32(), ctypes.c_uint32()
+        r, ho, hl = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(_lib.lib().magot_vcf_sizes(h, *[ctypes.byref(x) for x in n + [s, w, r, ho, hl]]),
+              'magot_vcf_sizes')
+        self.n_lines, self.n_data, self.n_header = [x.value for x in n]
+        self.n_samples, self.words, self.n_runs = s.value, w.value, r.value
+        self.header = (ho.value, hl.value)
+        self.upload_ms = float(_lib.lib().magot_vcf_upload_ms(h))
+        return self
+
+    last_declined_line = 0  # 1-based line of the last decline (0: none named)
+
+    @staticmethod
+    def params():
+        """(rows per piece of the counting pass, most samples, most CHROM runs,
+        most counters)."""
+        p = [ctypes.c_uint32() for _ in range(3)] + [ctypes.c_uint64()]
+        _lib.lib().magot_vcf_params(*[ctypes.byref(x) for x in p])
+        return tuple(x.value for x in p)
+
+    def _spans(self, fn, name, n):
+        off, length = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+        check(fn(self.ctx.handle, self.handle, ptr(off), ptr(length)), name)
+        return off[:n], length[:n]
+
+    def header_lines(self):
+        """The spans of the ``##`` lines in file order."""
+        return self._spans(_lib.lib().magot_vcf_header_lines, 'magot_vcf_header_lines',
+                           self.n_header)
+
+    def runs(self):
+        """The CHROM span of the first line of every run of data lines with one
+        CHROM."""
+        return self._spans(_lib.lib().magot_vcf_runs, 'magot_vcf_runs', self.n_runs)
+
+    def resolve(self, contig_of_run):
+        contig = np.ascontiguousarray(np.asarray(contig_of_run, dtype=np.uint32).reshape(-1))
+        check(_lib.lib().magot_vcf_resolve(self.ctx.handle, self.handle, ptr(contig), len(contig)),
+              'magot_vcf_resolve')
+
+    def tables(self):
+        """Per data line in file order, as a dict of arrays: 'line' (0-based),
+        'pos', 'hash', 'kept', 'first' (the last and the first line of its key;
+        zeros before ``resolve``) and 'bits' (n_data x words, uint32)."""
+        n = max(self.n_data, 1)
+        t = {'line': np.zeros(n, np.uint32), 'pos': np.zeros(n, np.int32),
+             'hash': np.zeros(n, np.uint64), 'kept': np.zeros(n, np.uint8),
+             'first': np.zeros(n, np.uint8), 'bits': np.zeros((n, max(self.words, 1)), np.uint32)}
+        check(_lib.lib().magot_vcf_tables(self.ctx.handle, self.handle,
+                                          *[ptr(t[k]) for k in ('line', 'pos', 'hash', 'kept',
+                                                                'first', 'bits')]),
+              'magot_vcf_tables')
+        return {k: v[:self.n_data] for k, v in t.items()}
+
+    def first_variant_line(self, order):
+        """(line, off, len) of the line that holds ``list(variant_set)[0]``:
+        the kept line of the first key as a Python 2 dict of the keys iterates
+        (``order='py2'``, from the hashes) or of the first data line's key."""
+        d = 0
+        if order == 'py2':
+            n = max(self.n_data, 1)
+            hashes, first = np.zeros(n, np.uint64), np.zeros(n, np.uint8)
+            check(_lib.lib().magot_vcf_tables(self.ctx.handle, self.handle, None, None,
+                                              ptr(hashes), None, ptr(first), None),
+                  'magot_vcf_tables')
+            firsts = np.flatnonzero(first[:self.n_data])
+            d = int(firsts[int(py2_order_of_hashes(hashes[firsts])[0])])
+        line, off, length = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(_lib.lib().magot_vcf_last_of(self.ctx.handle, self.handle, d, ctypes.byref(line),
+                                           ctypes.byref(off), ctypes.byref(length)),
+              'magot_vcf_last_of')
+        return line.value, off.value, length.value
+
+    def count(self, contig, lo, hi, allowed):
+        """(counts, foreign): per locus -- the positions lo..hi of a contig,
+        none when lo > hi -- and sample the kept lines inside with the sample's
+        bit set (n_loci x n_samples, uint32); ``foreign``: one of those lines has
+        a bit outside ``allowed`` (words x uint32).  (None, reason) above the
+        most counters."""
+        contig = np.ascontiguousarray(np.asarray(contig, dtype=np.uint32).reshape(-1))
+        lo = np.ascontiguousarray(np.asarray(lo, dtype=np.uint32).reshape(-1))
+        hi = np.ascontiguousarray(np.asarray(hi, dtype=np.uint32).reshape(-1))
+        allowed = np.ascontiguousarray(np.asarray(allowed, dtype=np.uint32).reshape(-1))
+        if not (len(contig) == len(lo) == len(hi)) or len(allowed) != self.words:
+            raise ValueError('one contig, lo and hi per locus; one word per 32 samples')
+        n = len(contig)
+        counts = np.zeros((max(n, 1), self.n_samples), np.uint32)
+        foreign, reason = ctypes.c_uint32(), ctypes.c_uint32()
+        rc = _lib.lib().magot_vcf_count(self.ctx.handle, self.handle, ptr(contig), ptr(lo), ptr(hi),
+                                        n, ptr(allowed), ptr(counts), ctypes.byref(foreign),
+                                        ctypes.byref(reason))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None, _lib.VCF_REASONS[reason.value]
+        check(rc, 'magot_vcf_count')
+        return counts[:n], bool(foreign.value)
+
+    def time(self, iters):
+        """Mean device ms per pass (PASSES; 'count': the last ``count``'s loci,
+        0 before one; 'copy': a device copy of the text, 'text_bytes' bytes)
+        (magot_vcf_time)."""
+        ms = np.zeros(len(self.PASSES), np.float64)
+        n = ctypes.c_uint64()
+        check(_lib.lib().magot_vcf_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                        ctypes.byref(n)), 'magot_vcf_time')
+        out = dict(zip(self.PASSES, ms.tolist()))
+        out['text_bytes'] = n.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_vcf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def render_hets(loci, seqlen, counts, cols, threads=0):
+    """calculate_heterozygosity's string from the het counts: per locus (a
+    str) with seqlen >= 1 the locus and, for every column of ``cols``, 100.0 *
+    count / seqlen as Python 2 prints a float; rows joined by LF
+    (magot_vcf_render).  Host only."""
+    counts = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32))
+    seqlen = np.ascontiguousarray(np.asarray(seqlen, dtype=np.int64).reshape(-1))
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.uint32).reshape(-1))
+    n = len(loci)
+    if counts.ndim != 2 or len(counts) != n or len(seqlen) != n:
+        raise ValueError('one row of counts and one length per locus')
+    parts = [s.encode('latin-1') for s in loci]
+    off = np.zeros(n + 1, np.uint64)
+    if n:
+        off[1:] = np.cumsum(np.fromiter((len(b) for b in parts), np.uint64, n))
+    blob = b''.join(parts)
+    L = _lib.lib()
+    text, size = ctypes.c_void_p(), ctypes.c_uint64()
+    check(L.magot_vcf_render(blob, ptr(off), ptr(seqlen) if n else None,
+                             ptr(counts) if counts.size else None, n, counts.shape[1],
+                             ptr(cols) if len(cols) else None, len(cols), int(threads),
+                             ctypes.byref(text), ctypes.byref(size)), 'magot_vcf_render')
+    try:
+        return ctypes.string_at(text, size.value).decode('latin-1')
+    finally:
+        L.magot_site_text_free(text)
+
+
 def copy_segments(src_dev_ptr, src_bytes, dst_dev_ptr, src_off, dst_off, ctx=None):
     """dst[dst_off[i]:dst_off[i+1]] = src[src_off[i]:...] on the device
     (magot_copy_segments; addresses of device memory, src_bytes the source's

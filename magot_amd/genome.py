@@ -1162,6 +1162,38 @@ def read_blast_csv(blast_csv, annotation_set_to_modify=None, hierarchy=['match',
 
 
 # ---------------------------------------------------------------------------
+# Variants (genome.py:502-522; filled by magot_variants.read_vcf)
+# ---------------------------------------------------------------------------
+
+class Genotype(object):
+    """genome.py:502-505: one sample's call at a variant; read_vcf sets an
+    attribute per FORMAT key."""
+
+    def name(self):
+        pass
+
+
+class Variant(object):
+    """genome.py:508-514 (``vcf_header_index`` is accepted and not kept, as
+    there)."""
+
+    def __init__(self, ref_allele, alt_alleles, genotypes=None, variant_set=None,
+                 vcf_header_index=None):
+        self.variant_set = variant_set
+        self.ref_allele = ref_allele
+        self.alt_alleles = alt_alleles
+        self.genotypes = genotypes
+
+
+class VariantSet(dict):
+    """genome.py:517-521: ``CHROM<:>POS`` -> Variant."""
+
+    def __init__(self, genome=None, vcf_headers=None):
+        self.genome = genome
+        self.vcf_headers = vcf_headers
+
+
+# ---------------------------------------------------------------------------
 # Genome facade (genome.py:880-978)
 # ---------------------------------------------------------------------------
 

@@ -23,6 +23,8 @@
            [native=False]
     python -m magot_amd.genome_tools composition_by_site <alignment.fasta> [order=py2|insertion]
            [native=False]
+    python -m magot_amd.genome_tools heterozygosity_from_vcf <calls.vcf> [window=10000]
+           [loci=<file, one locus per line>] [order=py2|insertion] [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -1608,6 +1610,27 @@ def composition_by_site(fasta_alignment, order='py2', native='True'):
 composition_by_site.last_path = None
 
 
+def heterozygosity_from_vcf(vcf, window='10000', loci=None, order='py2', native='True'):
+    """magot_variants.heterozygosity_from_vcf from the command line: the
+    windowed het rates of a VCF (magot_variants.py:16-139).  ``loci`` names a
+    file with one locus per line (``seqid,start,stop`` or ``seqid,length``;
+    empty lines are left out); without it the loci are the windows of the
+    header's contig lines.  The function's three prints, then the string it
+    returns, as Python 2's ``print`` writes it."""
+    from . import magot_variants
+    locus_list = None
+    if loci is not None:
+        text = genome.read_bytes(loci).decode('latin-1')
+        locus_list = [ln for ln in text.replace('\r', '').split('\n') if ln]
+    result = magot_variants.heterozygosity_from_vcf(vcf, locus_list, _literal(window), order=order,
+                                                    native=native)
+    heterozygosity_from_vcf.last_path = magot_variants.heterozygosity_from_vcf.last_path
+    _write(str(result) + '\n')
+
+
+heterozygosity_from_vcf.last_path = None
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
          'fqstats': fqstats, 'purge_overlaps': purge_overlaps, 'besthits_from_psl': besthits_from_psl,
          'extract_upstream_downstream': extract_upstream_downstream,
@@ -1615,7 +1638,8 @@ TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at
          'blast_csv2fasta': blast_csv2fasta, 'exonerate2fasta': exonerate2fasta,
          'get_seq_from_fasta': get_seq_from_fasta, 'dna2orfs': dna2orfs,
          'mask_from_gff': mask_from_gff, 'depth_from_gff': depth_from_gff,
-         'composition_by_site': composition_by_site}
+         'composition_by_site': composition_by_site,
+         'heterozygosity_from_vcf': heterozygosity_from_vcf}
 
 
 def parse_argv(argv):
