@@ -1133,6 +1133,94 @@ int magot_vcf_render(const char* loci, const uint64_t* loci_off, const int64_t* 
                      const uint32_t* cols, uint32_t n_cols, uint32_t n_threads, uint8_t** text,
                      uint64_t* bytes);
 
+/*
+ * exclude_from_fasta (genome_tools.py:377-391) and fasta2tab
+ * (magot_smallfuncs.py:21-29) on the device: the records of a FASTA text, the
+ * dict genome.py:854-877 makes of them, an anti-join of its keys against a list
+ * of names, and the text reflowed into one line per record.  The text is
+ * resident, as a PSL's.
+ *
+ * A line ends at LF only; the last one may lack it.  A line whose first byte is
+ * '>' is a header and opens a record; its name is the rest of the line less the
+ * LF and a CR before it.  Every other line adds its bytes, less the LF and a CR
+ * before it, to the record's sequence.  A line's cost does not depend on its
+ * length.  A name's first word is what Python 2's str.split gives first
+ * (blanks: space, TAB, LF, VT, FF, CR).  Only records with a sequence enter the
+ * dict: a key's place is that of its first such record, its sequence that of
+ * its last.
+ *   magot_fastarec_parse  uploads and indexes the text, tables its lines and
+ *       records and groups the records by name.  Declined with
+ *       MAGOT_ERR_UNSUPPORTED, *out = NULL, *reason a MAGOT_FASTAREC_* code and
+ *       *line the 1-based line (0 for the whole-text reasons), in this order: a
+ *       text longer than max_bytes (0: a quarter of the free device memory),
+ *       before anything of that size is allocated or read; a first byte that is
+ *       not '>' (line 1); more than 2^31 - 1 lines; the first line with a CR
+ *       that is neither before an LF nor the text's last byte, or with a name
+ *       longer than max_name bytes (on one line: the CR); two different keys in
+ *       one bucket of the low hash_bits bits (1..64) of CPython 2.7's string
+ *       hash (the lowest line that differs from its predecessor in the sorted
+ *       order).  A null text with len > 0 and hash_bits outside 1..64 are
+ *       MAGOT_ERR_ARG before any launch.
+ *   magot_fastarec_sizes  lines, records, records with a sequence, keys.
+ *   magot_fastarec_upload_ms  as magot_psl_upload_ms.
+ *   magot_fastarec_records  per record in file order: its header's 0-based
+ *       line, the name's offset and length, the sequence length, the name's
+ *       hash; the first word's offset, length and hash, and 1 where the name
+ *       has no word (then the word is empty, at the name's start).  Any pointer
+ *       may be NULL.
+ *   magot_fastarec_keys  per key in first-seen order: the hash, the first and
+ *       the last record with a sequence, and the first record's no-word flag.
+ *   magot_fastarec_exclude  keep[k] = 0 where key k -- its first word with
+ *       first_word != 0; the empty word where it has none -- equals one of the m
+ *       names blob[off[j] .. off[j + 1]); else 1.  Offsets that decrease or leave
+ *       the blob (blob_len bytes) are MAGOT_ERR_RANGE before any launch.
+ *   magot_fastarec_render  the records rec[0..n) (each below the record count,
+ *       else MAGOT_ERR_RANGE before any launch) in that order, into a device
+ *       buffer of the handle: style 0 '>' name LF sequence LF; style 1 name TAB
+ *       sequence LF, and a lone LF for n = 0.  *bytes: the text's length.
+ *   magot_fastarec_render_fetch  that text to the host (cap >= its length).
+ *   magot_fastarec_time  mean device ms over `iters` runs of: the line index,
+ *       the line table, the names, the sort, the keys, the reflow of every
+ *       record in file order in style 1 (*reflow_bytes), and a device copy of
+ *       the text (*text_bytes), in ms7[0..6].  The handle's answers stand
+ *       afterwards; a rendered text does not.
+ *   magot_fastarec_params  the longest name in bytes, the piece of a sequence
+ *       line one lane slot of the reflow copies, and the bytes of a text block
+ *       of the line index.
+ */
+enum {
+  MAGOT_FASTAREC_LEADING_TEXT = 1,   /* the first byte is not '>' */
+  MAGOT_FASTAREC_STRAY_CR = 2,       /* a CR not before an LF and not the last byte */
+  MAGOT_FASTAREC_LONG_NAME = 3,      /* a name longer than one lane hashes */
+  MAGOT_FASTAREC_HASH_COLLISION = 4, /* two keys in one bucket of the masked hash */
+  MAGOT_FASTAREC_TOO_LARGE = 5,      /* the text is longer than max_bytes */
+  MAGOT_FASTAREC_TOO_MANY_LINES = 6  /* more than 2^31 - 1 lines */
+};
+enum { MAGOT_FASTAREC_STYLE_FASTA = 0, MAGOT_FASTAREC_STYLE_TAB = 1 };
+typedef struct magot_fastarec magot_fastarec;
+int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t hash_bits,
+                         uint64_t max_bytes, magot_fastarec** out, uint32_t* reason,
+                         uint64_t* line);
+int magot_fastarec_sizes(const magot_fastarec* p, uint64_t* n_lines, uint64_t* n_records,
+                         uint64_t* n_with_sequence, uint64_t* n_keys);
+double magot_fastarec_upload_ms(const magot_fastarec* p);
+int magot_fastarec_records(magot_ctx* ctx, magot_fastarec* p, uint32_t* line, uint64_t* name_off,
+                           uint32_t* name_len, uint64_t* seq_len, uint64_t* hash,
+                           uint64_t* word_off, uint32_t* word_len, uint64_t* word_hash,
+                           uint32_t* no_word);
+int magot_fastarec_keys(magot_ctx* ctx, magot_fastarec* p, uint64_t* hash, uint32_t* first_record,
+                        uint32_t* last_record, uint32_t* no_word);
+int magot_fastarec_exclude(magot_ctx* ctx, magot_fastarec* p, const uint8_t* blob,
+                           uint64_t blob_len, const uint64_t* off, uint64_t m, int first_word,
+                           uint8_t* keep);
+int magot_fastarec_render(magot_ctx* ctx, magot_fastarec* p, const uint32_t* rec, uint64_t n,
+                          uint32_t style, uint64_t* bytes);
+int magot_fastarec_render_fetch(magot_ctx* ctx, magot_fastarec* p, uint8_t* out, uint64_t cap);
+int magot_fastarec_time(magot_ctx* ctx, magot_fastarec* p, int iters, double* ms7,
+                        uint64_t* text_bytes, uint64_t* reflow_bytes);
+void magot_fastarec_params(uint32_t* max_name, uint32_t* piece, uint32_t* text_block);
+void magot_fastarec_destroy(magot_fastarec* p);
+
 #ifdef __cplusplus
 }
 #endif

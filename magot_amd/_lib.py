@@ -75,6 +75,10 @@ EXPORTS = (
     'magot_vcf_runs', 'magot_vcf_resolve', 'magot_vcf_tables', 'magot_vcf_last_of',
     'magot_vcf_count', 'magot_vcf_time', 'magot_vcf_params', 'magot_vcf_destroy',
     'magot_vcf_render',
+    'magot_fastarec_parse', 'magot_fastarec_sizes', 'magot_fastarec_upload_ms',
+    'magot_fastarec_records', 'magot_fastarec_keys', 'magot_fastarec_exclude',
+    'magot_fastarec_render', 'magot_fastarec_render_fetch', 'magot_fastarec_time',
+    'magot_fastarec_params', 'magot_fastarec_destroy',
 )
 
 ERR_ARG = -1
@@ -114,6 +118,10 @@ VCF_REASONS = (None, 'no_header', 'many_headers', 'header_after_data', 'no_sampl
                'too_many_samples', 'no_data', 'field_count', 'chrom_form', 'pos_form', 'pos_range',
                'no_gt', 'empty_gt', 'equals_fixed', 'too_large', 'too_many_lines', 'too_many_runs',
                'line_too_long', 'too_many_counts', 'carriage_return')
+# magot_fastarec_parse's reasons (MAGOT_FASTAREC_*), by code
+FASTAREC_REASONS = (None, 'leading_text', 'stray_cr', 'long_name', 'hash_collision', 'too_large',
+                    'too_many_lines')
+FASTAREC_STYLES = {'fasta': 0, 'tab': 1}
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -365,6 +373,21 @@ def _declare(lib):
         'magot_vcf_render': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
                                             _vp, ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.POINTER(_vp), _u64p]),
+        'magot_fastarec_parse': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.c_uint64, ctypes.POINTER(_vp),
+                                                ctypes.POINTER(ctypes.c_uint32), _u64p]),
+        'magot_fastarec_sizes': (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+        'magot_fastarec_upload_ms': (ctypes.c_double, [_vp]),
+        'magot_fastarec_records': (ctypes.c_int, [_vp] * 11),
+        'magot_fastarec_keys': (ctypes.c_int, [_vp] * 6),
+        'magot_fastarec_exclude': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp,
+                                                  ctypes.c_uint64, ctypes.c_int, _vp]),
+        'magot_fastarec_render': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
+                                                 _u64p]),
+        'magot_fastarec_render_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_fastarec_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p, _u64p]),
+        'magot_fastarec_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3),
+        'magot_fastarec_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -975,6 +975,86 @@ hipError_t launch_vcf_ranges(const VcfArgs& a, const VcfCountArgs& c, void* tmp,
                              hipStream_t s);
 hipError_t launch_vcf_count(const VcfArgs& a, const VcfCountArgs& c, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// exclude_from_fasta, fasta2tab: FASTA records of a resident text
+// (fastarec.hip; genome_tools.py:377-391, magot_smallfuncs.py:21-29;
+// magot_fastarec_*)
+// ---------------------------------------------------------------------------
+// A line whose first byte is '>' is a header and opens a record; every other
+// line adds its bytes, less the LF and a CR before it, to the open record.  No
+// pass walks a sequence line: a line's payload is known from its two ends.
+constexpr uint32_t kFaMaxName = 1024;  // bytes of a name one lane hashes; a longer name declines
+constexpr uint32_t kFaPiece = 4096;    // bytes of a sequence line one lane slot of the reflow copies
+constexpr uint64_t kFaMaxLines = (1ull << 31) - 1;
+constexpr int kFaGroup = 16;           // pieces per wave of the reflow's copy
+static_assert((kFaPiece & (kFaPiece - 1)) == 0, "a power of two");
+struct FaArgs {
+  const uint8_t* text;  // n bytes, 16-byte aligned, readable to the next multiple of 16 and 16 more
+  uint64_t n;
+  uint64_t n_blocks;    // depth_text_blocks(n)
+  uint64_t* blk;        // n_blocks + 1: LFs per text block, the last entry 0
+  uint64_t* pre;        // their exclusive scan; pre[n_blocks]: the LFs of the text
+  unsigned long long* status;  // min of (line << 8 | MAGOT_FASTAREC_* reason); ~0 when clean
+  // per line, n_lines + 1 of each (the last entry of the first four 0, of the scans the total)
+  uint64_t n_lines;
+  uint64_t* line_start;  // the last entry n
+  uint64_t *hdr, *pay, *pcs;              // 1 for a header; payload bytes; pieces of kFaPiece
+  uint64_t *rec_of, *pay_pre, *pcs_pre;   // their exclusive scans
+  // per record (header line), n_rec of each where nothing else is said
+  uint64_t n_rec;
+  uint32_t* hdr_line;    // n_rec + 1, the last entry n_lines
+  uint64_t *name_off, *word_off, *hash, *word_hash, *seq_len;
+  uint32_t *name_len, *word_len, *no_word;
+  uint64_t *ne, *ne_pos;  // n_rec + 1: 1 where the sequence is not empty, and the scan
+  // the records with a sequence, compacted in file order, then sorted by the masked hash
+  uint32_t hash_bits;
+  uint64_t n_ne;
+  uint64_t *skey, *skey_sorted;
+  uint32_t *sval, *sval_sorted;
+  uint64_t *head, *head_pos;  // a run head's own position, else 0; their running maximum
+  uint64_t *is_first, *kpos;  // n_rec + 1: 1 on a key's first record, and the scan
+  uint32_t* last_of;          // on a key's first record: its last record
+  // per key in first-seen order
+  uint64_t n_keys;
+  uint64_t* k_hash;
+  uint32_t *k_first, *k_last, *k_no_word;
+};
+struct FaMemberArgs {  // the exclusion names: one blob, m + 1 offsets
+  uint64_t m;
+  const uint8_t* blob;
+  const uint64_t* off;
+  uint64_t *lkey, *lkey_sorted;  // m: the masked hashes
+  uint32_t *lidx, *lidx_sorted;
+  uint32_t first_word;           // compare each key's first word, not its name
+  uint8_t* keep;                 // n_keys: 0 where the compared name is in the list
+};
+enum { kFaStyleFasta = 0, kFaStyleTab = 1 };
+struct FaRenderArgs {
+  uint64_t n_out;        // records to print
+  const uint32_t* recs;  // n_out, each below n_rec, in output order
+  uint32_t style;
+  uint64_t *olen, *obase;  // n_out + 1: bytes of each printed record, the last 0; the scan
+  uint64_t *pcnt, *pbase;  // n_out + 1: 1 + its sequence pieces, the last 0; the scan
+  uint64_t n_pieces;
+  uint64_t *p_src, *p_dst;  // n_pieces: in the text, in `out`
+  uint32_t* p_len;
+  uint8_t* out;  // obase[n_out] bytes, 16-byte aligned
+};
+size_t fa_count_tmp_bytes(uint64_t n_blocks);
+size_t fa_tmp_bytes(uint64_t n);  // of every pass over at most n lines, records, names or pieces
+hipError_t launch_fa_count(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_fa_fill(const FaArgs& a, hipStream_t s);
+hipError_t launch_fa_lines(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_fa_names(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_fa_sort(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_fa_keys(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_fa_rows(const FaArgs& a, hipStream_t s);
+hipError_t launch_fa_member(const FaArgs& a, const FaMemberArgs& m, void* tmp, size_t tmp_bytes,
+                            hipStream_t s);
+hipError_t launch_fa_render_sizes(const FaArgs& a, const FaRenderArgs& r, void* tmp,
+                                  size_t tmp_bytes, hipStream_t s);
+hipError_t launch_fa_render(const FaArgs& a, const FaRenderArgs& r, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

@@ -1790,6 +1790,142 @@ def render_lines(data, off, length, whole=False):
     return out[:need.value]
 
 
+class FastaRecords(object):
+    """The records of a FASTA text on the device (magot_fastarec_*;
+    genome.py:854-877, genome_tools.py:377-391, magot_smallfuncs.py:21-29): a
+    line index, a line table that reads two bytes of every line however long
+    it is, one lane per header for the name and its CPython 2.7 hash, the
+    records with a sequence grouped by name as a dict keeps them (a sort by
+    hash, every group verified byte for byte), an anti-join of the keys against
+    a list of names, and the text reflowed into one line per record.  ``parse``
+    returns (None, reason) where only the host loop is exact: 'leading_text',
+    'stray_cr', 'long_name', 'hash_collision', 'too_large', 'too_many_lines';
+    ``declined_line`` then holds the 1-based line (0: the whole text)."""
+
+    PASSES = ('line_index', 'line_table', 'names', 'sort', 'keys', 'reflow', 'copy')
+    RECORD_COLUMNS = (('line', np.uint32), ('name_off', np.uint64), ('name_len', np.uint32),
+                      ('seq_len', np.uint64), ('hash', np.uint64), ('word_off', np.uint64),
+                      ('word_len', np.uint32), ('word_hash', np.uint64), ('no_word', np.uint32))
+    KEY_COLUMNS = (('hash', np.uint64), ('first_record', np.uint32), ('last_record', np.uint32),
+                   ('no_word', np.uint32))
+    declined_line = 0  # of the last declined parse
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.n_lines = self.n_records = self.n_with_sequence = self.n_keys = 0
+        self.upload_ms = 0.0
+
+    @classmethod
+    def parse(cls, data, hash_bits=64, max_bytes=0, ctx=None):
+        """The FASTA text in ``data`` (bytes, a buffer, an mmap, numpy) made
+        resident on the device, indexed and grouped.  ``hash_bits``: the low
+        bits of the hash the records are grouped by and the names of a list are
+        looked up by (two keys in one bucket decline the text; fewer than 64
+        bits only serve to test that).  ``max_bytes``: a longer text is
+        declined (0: a quarter of the free device memory)."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(data)
+        h, reason, line = ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_uint64()
+        rc = _lib.lib().magot_fastarec_parse(self.ctx.handle, _text_ptr(view), len(view),
+                                             int(hash_bits), int(max_bytes or 0), ctypes.byref(h),
+                                             ctypes.byref(reason), ctypes.byref(line))
+        if rc == _lib.ERR_UNSUPPORTED:
+            cls.declined_line = line.value
+            return None, _lib.FASTAREC_REASONS[reason.value]
+        check(rc, 'magot_fastarec_parse')
+        self.handle = h
+        sizes = [ctypes.c_uint64() for _ in range(4)]
+        check(_lib.lib().magot_fastarec_sizes(h, *[ctypes.byref(x) for x in sizes]),
+              'magot_fastarec_sizes')
+        self.n_lines, self.n_records, self.n_with_sequence, self.n_keys = [x.value for x in sizes]
+        self.upload_ms = float(_lib.lib().magot_fastarec_upload_ms(h))
+        return self
+
+    @staticmethod
+    def params():
+        """{'max_name': the longest name in bytes, 'piece': the bytes of a
+        sequence line one lane slot of the reflow copies, 'text_block': the
+        bytes per workgroup of the line index}"""
+        vals = [ctypes.c_uint32() for _ in range(3)]
+        _lib.lib().magot_fastarec_params(*[ctypes.byref(v) for v in vals])
+        return dict(zip(('max_name', 'piece', 'text_block'), [v.value for v in vals]))
+
+    def records(self):
+        """One row per header line in file order, as a dict of arrays: 'line'
+        (0-based), 'name_off', 'name_len', 'seq_len', 'hash' (of the name), and
+        the first word's 'word_off', 'word_len', 'word_hash' with 'no_word'."""
+        cols = [np.zeros(max(self.n_records, 1), dt) for _, dt in self.RECORD_COLUMNS]
+        check(_lib.lib().magot_fastarec_records(self.ctx.handle, self.handle,
+                                                *[ptr(c) for c in cols]), 'magot_fastarec_records')
+        return {name: c[:self.n_records] for (name, _), c in zip(self.RECORD_COLUMNS, cols)}
+
+    def keys(self):
+        """One row per dict key in first-seen order: 'hash', 'first_record' (its
+        place), 'last_record' (its sequence), 'no_word'."""
+        cols = [np.zeros(max(self.n_keys, 1), dt) for _, dt in self.KEY_COLUMNS]
+        check(_lib.lib().magot_fastarec_keys(self.ctx.handle, self.handle, *[ptr(c) for c in cols]),
+              'magot_fastarec_keys')
+        return {name: c[:self.n_keys] for (name, _), c in zip(self.KEY_COLUMNS, cols)}
+
+    def exclude(self, names, first_word=False):
+        """A bool array over the keys: False where the key (its first word with
+        ``first_word``; the empty word where it has none) is one of ``names``
+        (byte strings)."""
+        names = [n.encode('latin-1') if isinstance(n, str) else bytes(n) for n in names]
+        blob = np.frombuffer(b''.join(names), np.uint8)
+        off = np.zeros(len(names) + 1, np.uint64)
+        if names:
+            off[1:] = np.cumsum([len(n) for n in names], dtype=np.uint64)
+        keep = np.ones(max(self.n_keys, 1), np.uint8)
+        check(_lib.lib().magot_fastarec_exclude(self.ctx.handle, self.handle,
+                                                ptr(blob) if len(blob) else None, len(blob),
+                                                ptr(off), len(names), 1 if first_word else 0,
+                                                ptr(keep)), 'magot_fastarec_exclude')
+        return keep[:self.n_keys].astype(bool)
+
+    def render(self, records, style):
+        """The records (indices into ``records()``) in the order given as one
+        uint8 array: ``style`` 'fasta' ('>' name LF sequence LF) or 'tab' (name
+        TAB sequence, an LF between records and one at the end)."""
+        recs = np.ascontiguousarray(np.asarray(records, dtype=np.uint32).reshape(-1))
+        need = ctypes.c_uint64()
+        check(_lib.lib().magot_fastarec_render(self.ctx.handle, self.handle,
+                                               ptr(recs) if len(recs) else None, len(recs),
+                                               _lib.FASTAREC_STYLES[style], ctypes.byref(need)),
+              'magot_fastarec_render')
+        out = np.empty(max(need.value, 1), np.uint8)
+        check(_lib.lib().magot_fastarec_render_fetch(self.ctx.handle, self.handle, ptr(out),
+                                                     need.value), 'magot_fastarec_render_fetch')
+        return out[:need.value]
+
+    def time(self, iters):
+        """Mean device ms per pass (PASSES; 'reflow': every record in file
+        order in the 'tab' style, 'reflow_bytes' of output; 'copy': a device copy
+        of the text, 'text_bytes' bytes) (magot_fastarec_time)."""
+        ms = np.zeros(len(self.PASSES), np.float64)
+        n, m = ctypes.c_uint64(), ctypes.c_uint64()
+        check(_lib.lib().magot_fastarec_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                             ctypes.byref(n), ctypes.byref(m)),
+              'magot_fastarec_time')
+        out = dict(zip(self.PASSES, ms.tolist()))
+        out['text_bytes'] = n.value
+        out['reflow_bytes'] = m.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_fastarec_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SiteCounts(object):
     """composition_by_site's counting pass over a resident genome
     (magot_site_*, genome_tools.py:488-503): the alignment's rows are contigs of

@@ -130,6 +130,20 @@ def ensure_file(potential_file):
     return _Lines(_read_source(potential_file))
 
 
+def fasta2tab(fasta_file):
+    """magot_smallfuncs.py:21-29: every record of a FASTA as ``name TAB
+    sequence``, joined by LF, in file order; a line that is not a header
+    before the first header is an IndexError."""
+    rows = []
+    for line in ensure_file(fasta_file):
+        body = line.replace('\n', '').replace('\r', '')
+        if line[0] == '>':
+            rows.append([body[1:], '\t'])
+        else:
+            rows[-1].append(body)
+    return '\n'.join(''.join(row) for row in rows)
+
+
 # ---------------------------------------------------------------------------
 # Sequence (genome.py:781-851)
 # ---------------------------------------------------------------------------

@@ -25,6 +25,9 @@
            [native=False]
     python -m magot_amd.genome_tools heterozygosity_from_vcf <calls.vcf> [window=10000]
            [loci=<file, one locus per line>] [order=py2|insertion] [native=False]
+    python -m magot_amd.genome_tools exclude_from_fasta <fasta> <names.txt | name,name,...>
+           [just_firstword=True] [order=py2|insertion] [native=False]
+    python -m magot_amd.genome_tools fasta2tab <fasta> [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -1631,6 +1634,170 @@ def heterozygosity_from_vcf(vcf, window='10000', loci=None, order='py2', native=
 heterozygosity_from_vcf.last_path = None
 
 
+def _exclusion_names(exclude_list):
+    """genome_tools.py:381-384 as bytes: the lines of the file ``exclude_list``
+    names, every CR dropped (a file that ends in LF gives b'' too); when that
+    raises anything at all, the text itself split at its commas."""
+    try:
+        with open(exclude_list, 'rb') as fh:
+            return fh.read().replace(b'\r', b'').split(b'\n')
+    except Exception:  # noqa: BLE001  (the reference's bare except)
+        return exclude_list.encode('latin-1').split(b',')
+
+
+def _exclude_host(fasta, names, first_word, order, out):
+    """The reference's loop restated over genome.GenomeSequence; what it prints
+    is appended to ``out`` as it goes, so the records before a key without a
+    word are there when the IndexError leaves."""
+    seqs = genome.GenomeSequence(fasta)
+    keys = list(seqs)
+    if order == 'py2':
+        from . import py2order
+        keys = py2order.dict_order(keys)
+    listed = set(names)
+    for key in keys:
+        name = key.encode('latin-1')
+        compared = name.split()[0] if first_word else name  # bytes.split: Python 2's blanks
+        if compared not in listed:
+            out.append(b'>' + name + b'\n' + seqs[key].encode('latin-1') + b'\n')
+
+
+def _exclude_native(fasta, names, first_word, order, clock):
+    """(exclude_from_fasta's text as a uint8 array, None) from the device:
+    engine.FastaRecords' keys less the listed ones, in first-seen order or in
+    the order a Python 2 dict of them iterates (from the hashes the device
+    computed), each with its last sequence on one line.  (None, reason) when
+    only the host loop is exact."""
+    data = genome.read_buffer(fasta)
+    clock.lap('open')
+    recs = engine.FastaRecords.parse(data)
+    clock.lap('kernels')
+    if isinstance(recs, tuple):
+        return recs
+    try:
+        keys = recs.keys()
+        if first_word and keys['no_word'].any():
+            return None, 'a key without a word'
+        keep = recs.exclude(names, first_word=first_word)
+        clock.lap('membership')
+        last = keys['last_record']
+        if order == 'py2':
+            perm = engine.py2_order_of_hashes(keys['hash'])
+            last, keep = last[perm], keep[perm]
+        clock.lap('order')
+        text = recs.render(last[keep], 'fasta')
+        clock.lap('render')
+        return text, None
+    finally:
+        recs.close()
+
+
+def exclude_from_fasta(fasta, exclude_list, just_firstword='False', order='py2', native='True'):
+    """genome_tools.py:377-391: a FASTA file without the records named in
+    ``exclude_list`` -- a file of names, one per line, or, when no such file
+    opens, the names themselves between commas.  The file is read as
+    genome.GenomeSequence reads it: a record needs a sequence, a repeated name
+    keeps its first place and its last sequence, text before the first header
+    goes under the name ''.  With ``just_firstword='True'`` a record's first
+    word is compared, not its name; a name without a word is an IndexError
+    after the records before it.  Every record left is printed as ``>name``
+    and its sequence on one line, in the order a Python 2 dict of the names
+    iterates (``order='py2'``) or first seen (``order='insertion'``).
+
+    On the device (engine.FastaRecords: the records indexed at a cost that
+    does not depend on a line's length, grouped by name with a sort and
+    verified, the list looked up by hash and compared byte for byte, the text
+    reflowed by a grouped copy) for a regular file the device does not decline
+    -- text before the first header, a CR in mid-line, a name above the lane's
+    bound, two names in one hash bucket, a text too large -- and, with
+    ``just_firstword='True'``, no key without a word.  Otherwise, and with
+    ``native=False``, the loop on the host restates the reference, a string
+    that names no file read as the text itself included.  Nothing is written
+    before the path is known.  ``exclude_from_fasta.last_path`` names the path
+    the last call took."""
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'py2' or 'insertion'")
+    clock = _Clock()
+    first_word = just_firstword == 'True'
+    names = _exclusion_names(exclude_list)
+    clock.lap('list')
+    if native != 'True':
+        why = "native != 'True'"
+    elif not (isinstance(fasta, str) and os.path.isfile(fasta)):
+        why = 'not a regular file'
+    else:
+        text, why = _exclude_native(fasta, names, first_word, order, clock)
+        if text is not None:
+            exclude_from_fasta.last_path = ('exclude_from_fasta', 'native', None)
+            _write_bytes(text)
+            clock.lap('write')
+            clock.emit()
+            return
+    exclude_from_fasta.last_path = ('exclude_from_fasta', 'host', why)
+    out = []
+    try:
+        _exclude_host(fasta, names, first_word, order, out)
+    finally:
+        _write_bytes(*out)
+    clock.lap('write')
+    clock.emit()
+
+
+exclude_from_fasta.last_path = None
+
+
+def _fasta2tab_native(fasta_file, clock):
+    """(fasta2tab's text as a uint8 array, None) from the device: every header
+    of engine.FastaRecords in file order in the 'tab' style.  (None, reason)
+    when only the host loop is exact.  Raises the reference's IndexError."""
+    data = genome.read_buffer(fasta_file)
+    clock.lap('open')
+    if len(data) and bytes(data[:1]) != b'>':
+        raise IndexError('list index out of range')  # newlines[-1] of an empty list
+    recs = engine.FastaRecords.parse(data)
+    clock.lap('kernels')
+    if isinstance(recs, tuple):
+        return recs
+    try:
+        text = recs.render(np.arange(recs.n_records, dtype=np.uint32), 'tab')
+        clock.lap('render')
+        return text, None
+    finally:
+        recs.close()
+
+
+def fasta2tab(fasta_file, native='True'):
+    """genome_tools.py:349-350 over magot_smallfuncs.py:21-29: every record of
+    a FASTA file as ``name TAB sequence`` on one line, in file order; records
+    without a sequence and repeated names all stay.  A line that is not a
+    header before the first header is an IndexError, and nothing is printed.
+
+    On the device (engine.FastaRecords and its reflow) for a regular file the
+    device does not decline; otherwise, and with ``native=False``,
+    genome.fasta2tab on the host.  ``fasta2tab.last_path`` names the path the
+    last call took."""
+    clock = _Clock()
+    if native != 'True':
+        why = "native != 'True'"
+    elif not (isinstance(fasta_file, str) and os.path.isfile(fasta_file)):
+        why = 'not a regular file'
+    else:
+        fasta2tab.last_path = ('fasta2tab', 'native', None)
+        text, why = _fasta2tab_native(fasta_file, clock)
+        if text is not None:
+            _write_bytes(text)
+            clock.lap('write')
+            clock.emit()
+            return
+    fasta2tab.last_path = ('fasta2tab', 'host', why)
+    _write(genome.fasta2tab(fasta_file) + '\n')
+    clock.lap('write')
+    clock.emit()
+
+
+fasta2tab.last_path = None
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
          'fqstats': fqstats, 'purge_overlaps': purge_overlaps, 'besthits_from_psl': besthits_from_psl,
          'extract_upstream_downstream': extract_upstream_downstream,
@@ -1639,7 +1806,8 @@ TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at
          'get_seq_from_fasta': get_seq_from_fasta, 'dna2orfs': dna2orfs,
          'mask_from_gff': mask_from_gff, 'depth_from_gff': depth_from_gff,
          'composition_by_site': composition_by_site,
-         'heterozygosity_from_vcf': heterozygosity_from_vcf}
+         'heterozygosity_from_vcf': heterozygosity_from_vcf,
+         'exclude_from_fasta': exclude_from_fasta, 'fasta2tab': fasta2tab}
 
 
 def parse_argv(argv):
