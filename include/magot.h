@@ -1221,6 +1221,73 @@ int magot_fastarec_time(magot_ctx* ctx, magot_fastarec* p, int iters, double* ms
 void magot_fastarec_params(uint32_t* max_name, uint32_t* piece, uint32_t* text_block);
 void magot_fastarec_destroy(magot_fastarec* p);
 
+/*
+ * replace_names (genome_tools.py:431-446) on the device: every occurrence of a
+ * key -- a name of the table and the one-byte delimiter d behind it -- in a
+ * text replaced by the key's value and d.  The text is resident, as a PSL's.
+ *
+ * A field is what lies between two ds of a line (lines end at LF).  The device
+ * rewrites a field at most once: the suffix of it that is the name of lowest
+ * rank among the names that are suffixes of it becomes that name's value.  That
+ * is what the reference's loop over all keys prints when no name and no value
+ * holds d and no key's value feeds a later key (genome_tools.replace_names
+ * checks both; this interface does not).  The table's n_keys names are distinct,
+ * each of 1..max_name bytes, name k = names[name_off[k] .. name_off[k + 1]), its
+ * value values[val_off[k] .. val_off[k + 1]), rank[k] < n_keys its place in the
+ * order the keys are tried.  The output is the rewritten text with its last
+ * byte replaced by LF (`print line[:-1]`); an empty text gives an empty one.
+ *   magot_rename_parse  uploads text and table, builds the lookup structure
+ *       (an open-addressing table keyed by the low hash_bits bits, 1..64, of a
+ *       hash of the name from its last byte to its first), finds the field
+ *       ends, matches them and lays the output out.  Declined with
+ *       MAGOT_ERR_UNSUPPORTED, *out = NULL and *reason a MAGOT_RENAME_* code: a
+ *       table of 2^30 names or 4 GiB of names or of values; a text longer than
+ *       max_bytes (0: a quarter of the free device memory), before anything of
+ *       that size is allocated or read, or one whose field tables exceed half
+ *       the free device memory; two names in one bucket of the masked hash
+ *       (equal names included).  MAGOT_ERR_ARG before any launch: a null
+ *       argument, hash_bits outside 1..64, d above 255 or LF.  MAGOT_ERR_RANGE
+ *       before any launch: offsets that do not begin at 0, decrease or leave
+ *       their blob (their last entry is the blob's length), a name that is empty
+ *       or longer than max_name, a rank of n_keys or more.
+ *   magot_rename_sizes  the text's lines, its field ends, the hits, the output's
+ *       bytes.
+ *   magot_rename_upload_ms  as magot_psl_upload_ms.
+ *   magot_rename_hits  per hit in text order: the offset of its d, the key.
+ *       Either pointer may be NULL.
+ *   magot_rename_render  the output into a device buffer of the handle; *bytes:
+ *       its length.
+ *   magot_rename_render_fetch  that text to the host (cap >= its length).
+ *   magot_rename_time  mean device ms over `iters` runs of: the table build, the
+ *       field ends, the match, the layout, the copy into the output
+ *       (*out_bytes), and a device copy of the text (*text_bytes), in
+ *       ms6[0..5].  The handle's answers stand afterwards; a rendered text does
+ *       not.
+ *   magot_rename_params  the longest name in bytes, the bytes of a text block
+ *       of the field index, and the piece of an unchanged run one lane slot of
+ *       the copy takes.
+ */
+enum {
+  MAGOT_RENAME_TOO_LARGE = 1,       /* the text or its field tables */
+  MAGOT_RENAME_HASH_COLLISION = 2,  /* two names in one bucket of the masked hash */
+  MAGOT_RENAME_TABLE_TOO_LARGE = 3  /* 2^30 names, or 4 GiB of names or values */
+};
+typedef struct magot_rename magot_rename;
+int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uint8_t* names,
+                       const uint64_t* name_off, const uint8_t* values, const uint64_t* val_off,
+                       const uint32_t* rank, uint64_t n_keys, uint32_t delim, uint32_t hash_bits,
+                       uint64_t max_bytes, magot_rename** out, uint32_t* reason);
+int magot_rename_sizes(const magot_rename* p, uint64_t* n_lines, uint64_t* n_fields,
+                       uint64_t* n_hits, uint64_t* out_bytes);
+double magot_rename_upload_ms(const magot_rename* p);
+int magot_rename_hits(magot_ctx* ctx, magot_rename* p, uint64_t* end, uint32_t* key);
+int magot_rename_render(magot_ctx* ctx, magot_rename* p, uint64_t* bytes);
+int magot_rename_render_fetch(magot_ctx* ctx, magot_rename* p, uint8_t* out, uint64_t cap);
+int magot_rename_time(magot_ctx* ctx, magot_rename* p, int iters, double* ms6,
+                      uint64_t* text_bytes, uint64_t* out_bytes);
+void magot_rename_params(uint32_t* max_name, uint32_t* text_block, uint32_t* piece);
+void magot_rename_destroy(magot_rename* p);
+
 #ifdef __cplusplus
 }
 #endif

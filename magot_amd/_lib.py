@@ -79,6 +79,9 @@ EXPORTS = (
     'magot_fastarec_records', 'magot_fastarec_keys', 'magot_fastarec_exclude',
     'magot_fastarec_render', 'magot_fastarec_render_fetch', 'magot_fastarec_time',
     'magot_fastarec_params', 'magot_fastarec_destroy',
+    'magot_rename_parse', 'magot_rename_sizes', 'magot_rename_upload_ms', 'magot_rename_hits',
+    'magot_rename_render', 'magot_rename_render_fetch', 'magot_rename_time',
+    'magot_rename_params', 'magot_rename_destroy',
 )
 
 ERR_ARG = -1
@@ -122,6 +125,8 @@ VCF_REASONS = (None, 'no_header', 'many_headers', 'header_after_data', 'no_sampl
 FASTAREC_REASONS = (None, 'leading_text', 'stray_cr', 'long_name', 'hash_collision', 'too_large',
                     'too_many_lines')
 FASTAREC_STYLES = {'fasta': 0, 'tab': 1}
+# magot_rename_parse's reasons (MAGOT_RENAME_*), by code
+RENAME_REASONS = (None, 'too_large', 'hash_collision', 'table_too_large')
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -388,6 +393,18 @@ def _declare(lib):
         'magot_fastarec_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p, _u64p]),
         'magot_fastarec_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3),
         'magot_fastarec_destroy': (None, [_vp]),
+        'magot_rename_parse': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp,
+                                              ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_uint64, ctypes.POINTER(_vp),
+                                              ctypes.POINTER(ctypes.c_uint32)]),
+        'magot_rename_sizes': (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+        'magot_rename_upload_ms': (ctypes.c_double, [_vp]),
+        'magot_rename_hits': (ctypes.c_int, [_vp] * 4),
+        'magot_rename_render': (ctypes.c_int, [_vp, _vp, _u64p]),
+        'magot_rename_render_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_rename_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p, _u64p]),
+        'magot_rename_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3),
+        'magot_rename_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

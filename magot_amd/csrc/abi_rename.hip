@@ -1,0 +1,379 @@
+// C ABI: replace_names over a resident text (rename.hip; genome_tools.py:431-446):
+// the text and the table made resident, the table's lookup structure, the field
+// ends and their matches, the layout and the renamed text.
+#include "abi_internal.h"
+
+using namespace magot;
+
+struct magot_rename {
+  magot_ctx* ctx = nullptr;
+  void* text_mem = nullptr;   // the text, the values behind it, the table and the block counts
+  void* field_mem = nullptr;  // everything sized by the fields
+  void* hit_mem = nullptr;    // everything sized by the hits
+  void* out_mem = nullptr;    // the rendered text and its pieces
+  void* copy_mem = nullptr;   // magot_rename_time's copy target
+  RnArgs a{};
+  RnRenderArgs r{};
+  uint64_t n_lines = 0;
+  bool rendered = false;
+  void* tmp0 = nullptr;  // the block scan's scratch
+  void* tmp = nullptr;   // the field and hit scans' scratch
+  size_t tmp0_bytes = 0, tmp_bytes = 0;
+  float upload_ms = 0.f;
+};
+
+namespace {
+
+constexpr int kRnPasses = 6;
+
+int rn_decline(uint32_t* reason, uint32_t why) {
+  if (reason) *reason = why;
+  set_error("magot_rename_parse: input outside the device path; use the host loop");
+  return MAGOT_ERR_UNSUPPORTED;
+}
+
+template <class T>
+T* at(char* base, uint64_t off) {
+  return reinterpret_cast<T*>(base + off);
+}
+
+// The buffers of a render: the output and one row per piece.  Replaces the
+// handle's last ones.
+int rn_plan_render(magot_rename* p) {
+  if (p->out_mem) MAGOT_HIP_TRY(hipFree(p->out_mem));
+  p->out_mem = nullptr;
+  p->rendered = false;
+  RnRenderArgs& r = p->r;
+  if (!r.n_pieces) return MAGOT_OK;
+  Carve co;
+  const uint64_t q_out = co.take<uint8_t>(r.out_bytes + 16);
+  const uint64_t q_src = co.take<uint64_t>(r.n_pieces), q_dst = co.take<uint64_t>(r.n_pieces);
+  const uint64_t q_len = co.take<uint32_t>(r.n_pieces);
+  MAGOT_HIP_TRY(hipMalloc(&p->out_mem, co.used + 256));
+  char* ob = static_cast<char*>(p->out_mem);
+  r.out = at<uint8_t>(ob, q_out);
+  r.p_src = at<uint64_t>(ob, q_src);
+  r.p_dst = at<uint64_t>(ob, q_dst);
+  r.p_len = at<uint32_t>(ob, q_len);
+  return MAGOT_OK;
+}
+
+// pass k of magot_rename_time on the handle's own buffers
+hipError_t rn_pass(const magot_rename* p, int k, hipStream_t s) {
+  const RnArgs& a = p->a;
+  switch (k) {
+    case 0: return launch_rn_table(a, s);
+    case 1:
+      if (hipError_t e = launch_rn_count(a, p->tmp0, p->tmp0_bytes, s)) return e;
+      return launch_rn_fill(a, s);
+    case 2: return launch_rn_match(a, p->tmp, p->tmp_bytes, s);
+    case 3: return launch_rn_layout(a, p->tmp, p->tmp_bytes, s);
+    case 4: return launch_rn_render(a, p->r, s);
+    default: return hipMemcpyAsync(p->copy_mem, a.text, a.n, hipMemcpyDeviceToDevice, s);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+void magot_rename_destroy(magot_rename* p) {
+  if (!p) return;
+  if (p->ctx) (void)hipSetDevice(p->ctx->device);
+  if (p->copy_mem) (void)hipFree(p->copy_mem);
+  if (p->out_mem) (void)hipFree(p->out_mem);
+  if (p->hit_mem) (void)hipFree(p->hit_mem);
+  if (p->field_mem) (void)hipFree(p->field_mem);
+  if (p->text_mem) (void)hipFree(p->text_mem);
+  delete p;
+}
+
+void magot_rename_params(uint32_t* max_name, uint32_t* text_block, uint32_t* piece) {
+  if (max_name) *max_name = kRnMaxName;
+  if (text_block) *text_block = kTextBlock;
+  if (piece) *piece = kRnPiece;
+}
+
+int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uint8_t* names,
+                       const uint64_t* name_off, const uint8_t* values, const uint64_t* val_off,
+                       const uint32_t* rank, uint64_t n_keys, uint32_t delim, uint32_t hash_bits,
+                       uint64_t max_bytes, magot_rename** out, uint32_t* reason) {
+  if (int rc = bind(ctx)) return rc;
+  if (!out || (len && !text) || (n_keys && (!names || !name_off || !val_off || !rank))) {
+    set_error("magot_rename_parse: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  *out = nullptr;
+  if (reason) *reason = 0;
+  if (hash_bits < 1 || hash_bits > 64) {
+    set_error("magot_rename_parse: hash_bits outside 1..64");
+    return MAGOT_ERR_ARG;
+  }
+  if (delim > 255 || delim == '\n') {
+    set_error("magot_rename_parse: the delimiter is one byte other than LF");
+    return MAGOT_ERR_ARG;
+  }
+  if (n_keys >= kRnMaxKeys) return rn_decline(reason, MAGOT_RENAME_TABLE_TOO_LARGE);
+  const uint64_t names_len = n_keys ? name_off[n_keys] : 0, vals_len = n_keys ? val_off[n_keys] : 0;
+  if (names_len >= kRnMaxBlob || vals_len >= kRnMaxBlob)
+    return rn_decline(reason, MAGOT_RENAME_TABLE_TOO_LARGE);
+  if (vals_len && !values) {
+    set_error("magot_rename_parse: null argument");
+    return MAGOT_ERR_ARG;
+  }
+
+  struct Guard {
+    magot_rename* p;
+    ~Guard() { magot_rename_destroy(p); }
+  } guard{new magot_rename()};
+  magot_rename* p = guard.p;
+  p->ctx = ctx;
+  RnArgs& a = p->a;
+  if (n_keys && (name_off[0] || val_off[0])) {
+    set_error("magot_rename_parse: the offsets begin at 0");
+    return MAGOT_ERR_RANGE;
+  }
+  for (uint64_t k = 0; k < n_keys; ++k) {
+    // monotone below a checked total: every span lies inside its blob
+    if (name_off[k + 1] > names_len || name_off[k] >= name_off[k + 1] ||
+        name_off[k + 1] - name_off[k] > kRnMaxName) {
+      set_error("magot_rename_parse: a name is empty, longer than max_name or leaves the blob");
+      return MAGOT_ERR_RANGE;
+    }
+    if (val_off[k + 1] > vals_len || val_off[k] > val_off[k + 1]) {
+      set_error("magot_rename_parse: a value's offsets decrease or leave the blob");
+      return MAGOT_ERR_RANGE;
+    }
+    if (rank[k] >= n_keys) {
+      set_error("magot_rename_parse: a rank beyond the table");
+      return MAGOT_ERR_RANGE;
+    }
+    const uint32_t l = (uint32_t)(name_off[k + 1] - name_off[k]);
+    a.len_mask[(l - 1) >> 6] |= 1ull << ((l - 1) & 63);
+    a.max_len = std::max(a.max_len, l);
+  }
+  if (!max_bytes) {  // the field tables of a text dense in delimiters take more than the text
+    size_t free_b = 0, total_b = 0;
+    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    max_bytes = free_b / 4;
+  }
+  if (len > max_bytes) return rn_decline(reason, MAGOT_RENAME_TOO_LARGE);
+
+  a.n = len;
+  a.n_blocks = depth_text_blocks(len);
+  a.delim = delim;
+  a.hash_bits = hash_bits;
+  a.n_keys = n_keys;
+  a.cap = 2;
+  a.slot_shift = 63;
+  while (a.cap < 4 * n_keys) {
+    a.cap <<= 1;
+    --a.slot_shift;
+  }
+  hipStream_t s = ctx->stream;
+  {
+    p->tmp0_bytes = rn_tmp_bytes(a.n_blocks + 1);
+    Carve cv;
+    const uint64_t o_text = cv.take<uint8_t>(len + 32);  // 16-byte loads at and behind the last byte
+    const uint64_t o_vals = cv.take<uint8_t>(vals_len + 32);
+    const uint64_t o_names = cv.take<uint8_t>(names_len + 1);
+    const uint64_t o_noff = cv.take<uint64_t>(n_keys + 1), o_voff = cv.take<uint64_t>(n_keys + 1);
+    const uint64_t o_rank = cv.take<uint32_t>(n_keys + 1);
+    const uint64_t o_hash = cv.take<uint64_t>(n_keys + 1);
+    const uint64_t o_claim = cv.take<uint32_t>(a.cap);
+    const uint64_t o_slots = cv.take<RnSlot>(a.cap);
+    const uint64_t o_blk = cv.take<uint64_t>(a.n_blocks + 1);
+    const uint64_t o_pre = cv.take<uint64_t>(a.n_blocks + 1);
+    const uint64_t o_lblk = cv.take<uint64_t>(a.n_blocks + 1);
+    const uint64_t o_lpre = cv.take<uint64_t>(a.n_blocks + 1);
+    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp0_bytes);
+    const uint64_t o_status = cv.take<unsigned long long>(1);
+    MAGOT_HIP_TRY(hipMalloc(&p->text_mem, cv.used + 256));
+    char* base = static_cast<char*>(p->text_mem);
+    a.text = at<const uint8_t>(base, o_text);
+    a.val_base = o_vals - o_text;
+    a.names = at<const uint8_t>(base, o_names);
+    a.name_off = at<const uint64_t>(base, o_noff);
+    a.val_off = at<const uint64_t>(base, o_voff);
+    a.rank = at<const uint32_t>(base, o_rank);
+    a.key_hash = at<uint64_t>(base, o_hash);
+    a.claim = at<uint32_t>(base, o_claim);
+    a.slots = at<RnSlot>(base, o_slots);
+    a.blk = at<uint64_t>(base, o_blk);
+    a.pre = at<uint64_t>(base, o_pre);
+    a.lf_blk = at<uint64_t>(base, o_lblk);
+    a.lf_pre = at<uint64_t>(base, o_lpre);
+    p->tmp0 = base + o_tmp;
+    a.status = at<unsigned long long>(base, o_status);
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
+    if (len)
+      if (int rc = upload_text(ctx, text, len, at<uint8_t>(base, o_text))) return rc;
+    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
+    if (n_keys) {
+      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_names, names, names_len, hipMemcpyHostToDevice, s));
+      if (vals_len)
+        MAGOT_HIP_TRY(hipMemcpyAsync(base + o_vals, values, vals_len, hipMemcpyHostToDevice, s));
+      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_noff, name_off, (n_keys + 1) * 8,
+                                   hipMemcpyHostToDevice, s));
+      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_voff, val_off, (n_keys + 1) * 8,
+                                   hipMemcpyHostToDevice, s));
+      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_rank, rank, n_keys * 4, hipMemcpyHostToDevice, s));
+    }
+    MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
+    MAGOT_HIP_TRY(launch_rn_table(a, s));
+    MAGOT_HIP_TRY(launch_rn_count(a, p->tmp0, p->tmp0_bytes, s));
+    unsigned long long status = 0;
+    uint64_t lfs = 0;
+    MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipMemcpyAsync(&lfs, a.lf_pre + a.n_blocks, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_fields, a.pre + a.n_blocks, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+    MAGOT_HIP_TRY(hipEventElapsedTime(&p->upload_ms, ctx->ev0, ctx->ev1));
+    if (status != ~0ull) return rn_decline(reason, (uint32_t)status);
+    if (a.n_fields > len) {
+      set_error("magot_rename_parse: more delimiters than bytes");
+      return MAGOT_ERR_STATE;
+    }
+    p->n_lines = lfs + (len && text[len - 1] != '\n' ? 1 : 0);
+  }
+  {
+    const uint64_t F = a.n_fields;
+    p->tmp_bytes = rn_tmp_bytes(F + 2);  // the hits are at most the fields
+    Carve cv;
+    const uint64_t o_pos = cv.take<uint64_t>(F + 1);
+    const uint64_t o_hit = cv.take<uint64_t>(F + 1), o_hpos = cv.take<uint64_t>(F + 1);
+    const uint64_t o_key = cv.take<uint32_t>(F + 1);
+    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
+    size_t free_b = 0, total_b = 0;
+    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (cv.used > free_b / 2) return rn_decline(reason, MAGOT_RENAME_TOO_LARGE);
+    MAGOT_HIP_TRY(hipMalloc(&p->field_mem, cv.used + 256));
+    char* base = static_cast<char*>(p->field_mem);
+    a.d_pos = at<uint64_t>(base, o_pos);
+    a.f_hit = at<uint64_t>(base, o_hit);
+    a.f_hpos = at<uint64_t>(base, o_hpos);
+    a.f_key = at<uint32_t>(base, o_key);
+    p->tmp = base + o_tmp;
+    MAGOT_HIP_TRY(launch_rn_fill(a, s));
+    MAGOT_HIP_TRY(launch_rn_match(a, p->tmp, p->tmp_bytes, s));
+    MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_hits, a.f_hpos + F, 8, hipMemcpyDeviceToHost, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+    if (a.n_hits > F) {
+      set_error("magot_rename_parse: more hits than fields");
+      return MAGOT_ERR_STATE;
+    }
+  }
+  {
+    const uint64_t H = a.n_hits;
+    Carve cv;
+    const uint64_t o_end = cv.take<uint64_t>(H + 1);
+    const uint64_t o_delta = cv.take<uint64_t>(H + 1), o_dsum = cv.take<uint64_t>(H + 1);
+    const uint64_t o_pcnt = cv.take<uint64_t>(H + 2), o_pbase = cv.take<uint64_t>(H + 2);
+    const uint64_t o_key = cv.take<uint32_t>(H + 1);
+    MAGOT_HIP_TRY(hipMalloc(&p->hit_mem, cv.used + 256));
+    char* base = static_cast<char*>(p->hit_mem);
+    a.h_end = at<uint64_t>(base, o_end);
+    a.h_delta = at<uint64_t>(base, o_delta);
+    a.h_dsum = at<uint64_t>(base, o_dsum);
+    a.h_pcnt = at<uint64_t>(base, o_pcnt);
+    a.h_pbase = at<uint64_t>(base, o_pbase);
+    a.h_key = at<uint32_t>(base, o_key);
+    uint64_t shift = 0;
+    if (len) {  // an empty text has no run and no piece
+      MAGOT_HIP_TRY(launch_rn_layout(a, p->tmp, p->tmp_bytes, s));
+      MAGOT_HIP_TRY(hipMemcpyAsync(&shift, a.h_dsum + H, 8, hipMemcpyDeviceToHost, s));
+      MAGOT_HIP_TRY(hipMemcpyAsync(&p->r.n_pieces, a.h_pbase + H + 1, 8, hipMemcpyDeviceToHost, s));
+      MAGOT_HIP_TRY(hipStreamSynchronize(s));
+    }
+    p->r.out_bytes = len + shift;  // mod 2^64: the shift may be negative
+    // every hit keeps its d, and a text without one keeps all its bytes
+    if (len && !p->r.out_bytes) {
+      set_error("magot_rename_parse: a text with an empty output");
+      return MAGOT_ERR_STATE;
+    }
+  }
+  guard.p = nullptr;
+  *out = p;
+  return MAGOT_OK;
+}
+
+int magot_rename_sizes(const magot_rename* p, uint64_t* n_lines, uint64_t* n_fields,
+                       uint64_t* n_hits, uint64_t* out_bytes) {
+  if (!p) {
+    set_error("magot_rename_sizes: null handle");
+    return MAGOT_ERR_ARG;
+  }
+  if (n_lines) *n_lines = p->n_lines;
+  if (n_fields) *n_fields = p->a.n_fields;
+  if (n_hits) *n_hits = p->a.n_hits;
+  if (out_bytes) *out_bytes = p->r.out_bytes;
+  return MAGOT_OK;
+}
+
+double magot_rename_upload_ms(const magot_rename* p) { return p ? (double)p->upload_ms : 0.0; }
+
+int magot_rename_hits(magot_ctx* ctx, magot_rename* p, uint64_t* end, uint32_t* key) {
+  if (int rc = handle_of(ctx, p, "magot_rename_hits", "handle")) return rc;
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const uint64_t n = p->a.n_hits;
+  if (end && n) MAGOT_HIP_TRY(hipMemcpy(end, p->a.h_end, n * 8, hipMemcpyDeviceToHost));
+  if (key && n) MAGOT_HIP_TRY(hipMemcpy(key, p->a.h_key, n * 4, hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+int magot_rename_render(magot_ctx* ctx, magot_rename* p, uint64_t* bytes) {
+  if (int rc = handle_of(ctx, p, "magot_rename_render", "handle")) return rc;
+  if (!bytes) {
+    set_error("magot_rename_render: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (int rc = rn_plan_render(p)) return rc;
+  MAGOT_HIP_TRY(launch_rn_render(p->a, p->r, ctx->stream));
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  p->rendered = true;
+  *bytes = p->r.out_bytes;
+  return MAGOT_OK;
+}
+
+int magot_rename_render_fetch(magot_ctx* ctx, magot_rename* p, uint8_t* out, uint64_t cap) {
+  if (int rc = handle_of(ctx, p, "magot_rename_render_fetch", "handle")) return rc;
+  if (!p->rendered) {
+    set_error("magot_rename_render_fetch: nothing rendered");
+    return MAGOT_ERR_STATE;
+  }
+  const uint64_t need = p->r.out_bytes;
+  if (cap < need || (need && !out)) {
+    set_error("magot_rename_render_fetch: buffer too small");
+    return MAGOT_ERR_ARG;
+  }
+  if (need) MAGOT_HIP_TRY(hipMemcpy(out, p->r.out, need, hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+int magot_rename_time(magot_ctx* ctx, magot_rename* p, int iters, double* ms6,
+                      uint64_t* text_bytes, uint64_t* out_bytes) {
+  if (int rc = handle_of(ctx, p, "magot_rename_time", "handle")) return rc;
+  if (iters <= 0 || !ms6) {
+    set_error("magot_rename_time: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  if (text_bytes) *text_bytes = p->a.n;
+  if (out_bytes) *out_bytes = p->r.out_bytes;
+  for (int k = 0; k < kRnPasses; ++k) ms6[k] = 0;
+  if (!p->a.n) return MAGOT_OK;  // an empty text: nothing to time
+  MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.n + 256));
+  if (int rc = rn_plan_render(p)) return rc;
+  // every pass writes what it wrote in magot_rename_parse: the answers stand
+  double total[kRnPasses] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < iters; ++i)
+    for (int k = 0; k < kRnPasses; ++k)
+      if (int rc = time_pass(ctx, &total[k],
+                             [&]() -> hipError_t { return rn_pass(p, k, ctx->stream); }))
+        return rc;
+  for (int k = 0; k < kRnPasses; ++k) ms6[k] = total[k] / iters;
+  return MAGOT_OK;
+}
+
+}  // extern "C"

@@ -394,6 +394,20 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v) {
   return v;
 }
 
+// bit k: byte k of x equals the byte repeated in pat (SWAR: no carry leaves a byte)
+__device__ __forceinline__ uint32_t byte_eq_mask4(uint32_t x, uint32_t pat) {
+  x ^= pat;
+  const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
+  const uint32_t z = ~(t | x | 0x7f7f7f7fu) >> 7;
+  return (z * 0x00204081u) >> 21 & 0xFu;
+}
+
+// bit k: byte k of the 16 bytes of v equals the byte repeated in pat
+__device__ __forceinline__ uint32_t byte_eq_mask16(uint4 v, uint32_t pat) {
+  return byte_eq_mask4(v.x, pat) | byte_eq_mask4(v.y, pat) << 4 | byte_eq_mask4(v.z, pat) << 8 |
+         byte_eq_mask4(v.w, pat) << 12;
+}
+
 // Dynamic LDS (never touched by the kernel) that caps a kernel at `want`
 // resident blocks per CU; 0 when it already fits or want <= 0.
 inline size_t occupancy_lds_pad(const void* fn, int threads, int want) {
@@ -1054,6 +1068,74 @@ hipError_t launch_fa_member(const FaArgs& a, const FaMemberArgs& m, void* tmp, s
 hipError_t launch_fa_render_sizes(const FaArgs& a, const FaRenderArgs& r, void* tmp,
                                   size_t tmp_bytes, hipStream_t s);
 hipError_t launch_fa_render(const FaArgs& a, const FaRenderArgs& r, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// replace_names: words of a resident text renamed from a table (rename.hip;
+// genome_tools.py:431-446; magot_rename_*)
+// ---------------------------------------------------------------------------
+// A key is a name and the one-byte delimiter d.  A field is what lies between
+// two ds of a line; the name that rewrites it is the one of lowest rank among
+// the names that are suffixes of it.  One lane per d walks left over at most the
+// longest name of the table, whatever the field's length.
+constexpr uint32_t kRnMaxName = 256;  // bytes of a name; a longer one never reaches the device
+constexpr uint32_t kRnPiece = 4096;   // bytes of an unchanged run one lane slot of the copy takes
+constexpr uint32_t kRnNoKey = 0xffffffffu;
+constexpr uint64_t kRnMaxKeys = 1ull << 30;   // the slots are numbered in 32 bits
+constexpr uint64_t kRnMaxBlob = 1ull << 32;   // a value is one piece: its length fits 32 bits
+struct alignas(16) RnSlot {  // of the open-addressing table; 16 bytes, one load
+  uint64_t hash;  // the name's masked matching hash
+  uint32_t key;   // kRnNoKey: empty
+  uint32_t len;
+};
+struct RnArgs {
+  const uint8_t* text;  // n bytes, 16-byte aligned, readable to the next multiple of 16 and 16 more
+  uint64_t n;
+  uint64_t n_blocks;    // depth_text_blocks(n)
+  uint32_t delim;
+  uint32_t hash_bits;
+  // the table: n_keys distinct names, each of 1..kRnMaxName bytes without d
+  uint64_t n_keys;
+  const uint8_t* names;
+  const uint64_t *name_off, *val_off;  // n_keys + 1 each
+  uint64_t val_base;     // the value blob's first byte, counted from `text` (as readable as it)
+  const uint32_t* rank;  // n_keys: the key's place in the dict order in use
+  uint64_t* key_hash;    // n_keys: the masked hash, from the name's last byte to its first
+  uint32_t* claim;       // cap: the key that took the slot (compare-and-swap), kRnNoKey
+  RnSlot* slots;         // cap
+  uint64_t cap;          // a power of two, at least 4 * n_keys
+  uint32_t slot_shift;   // 64 - log2(cap)
+  uint32_t max_len;      // the longest name
+  uint64_t len_mask[kRnMaxName / 64];  // bit l - 1: a name of l bytes exists
+  unsigned long long* status;  // min of the MAGOT_RENAME_* reasons met, ~0 when clean
+  uint64_t *blk, *pre;   // n_blocks + 1: ds per text block, the last entry 0; the exclusive scan
+  uint64_t *lf_blk, *lf_pre;  // the same of the LFs: lf_pre[n_blocks] is the text's
+  // per field end (a d of the text), n_fields of each where nothing else is said
+  uint64_t n_fields;
+  uint64_t* d_pos;
+  uint32_t* f_key;            // the key that rewrites the field, kRnNoKey
+  uint64_t *f_hit, *f_hpos;   // n_fields + 1: 1 where there is one, the last entry 0; the scan
+  // per hit in text order
+  uint64_t n_hits;
+  uint64_t* h_end;            // its d
+  uint32_t* h_key;
+  uint64_t *h_delta, *h_dsum;  // n_hits + 1: value less name in bytes (mod 2^64), the last 0; the scan
+  uint64_t *h_pcnt, *h_pbase;  // n_hits + 2: pieces of the run before the hit and 1 for its value;
+                               // entry n_hits: the run behind the last hit; then 0; the scan
+};
+struct RnRenderArgs {
+  uint64_t n_pieces;
+  uint64_t *p_src, *p_dst;  // n_pieces: from `text`, in `out`
+  uint32_t* p_len;
+  uint8_t* out;       // out_bytes, 16-byte aligned
+  uint64_t out_bytes;  // n + h_dsum[n_hits]
+};
+size_t rn_tmp_bytes(uint64_t n);  // of every scan over at most n entries
+hipError_t launch_rn_table(const RnArgs& a, hipStream_t s);
+hipError_t launch_rn_count(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_rn_fill(const RnArgs& a, hipStream_t s);
+hipError_t launch_rn_match(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_rn_layout(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_rn_render(const RnArgs& a, const RnRenderArgs& r, hipStream_t s);
 
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.

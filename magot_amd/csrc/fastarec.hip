@@ -72,19 +72,6 @@ static_assert(kFaGroup <= kSpanGroup, "count_le searches kSpanGroup entries");
 
 inline unsigned fa_blocks_for(uint64_t n) { return (unsigned)((n + kFaThreads - 1) / kFaThreads); }
 
-// bit k: byte k of x equals the byte repeated in pat (psl.hip's psl_lf_mask4)
-__device__ __forceinline__ uint32_t fa_eq_mask4(uint32_t x, uint32_t pat) {
-  x ^= pat;
-  const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-  const uint32_t z = ~(t | x | 0x7f7f7f7fu) >> 7;
-  return (z * 0x00204081u) >> 21 & 0xFu;
-}
-
-__device__ __forceinline__ uint32_t fa_eq_mask16(uint4 v, uint32_t pat) {
-  return fa_eq_mask4(v.x, pat) | fa_eq_mask4(v.y, pat) << 4 | fa_eq_mask4(v.z, pat) << 8 |
-         fa_eq_mask4(v.w, pat) << 12;
-}
-
 // bit j of *lf, of *cr: byte i + j of the text is LF, is CR (i the lane's first byte)
 __device__ __forceinline__ void fa_lane_masks(const uint8_t* __restrict__ text, uint64_t i,
                                               uint64_t n, uint32_t* lf, uint32_t* cr) {
@@ -92,8 +79,8 @@ __device__ __forceinline__ void fa_lane_masks(const uint8_t* __restrict__ text, 
   if (i >= n) return;
   const uint4 v = *reinterpret_cast<const uint4*>(text + i);  // readable to the next 16
   const uint32_t keep = n - i < kFaLane ? (1u << (n - i)) - 1 : 0xffffu;  // behind the text: anything
-  *lf = fa_eq_mask16(v, 0x0A0A0A0Au) & keep;
-  *cr = fa_eq_mask16(v, 0x0D0D0D0Du) & keep;
+  *lf = byte_eq_mask16(v, 0x0A0A0A0Au) & keep;
+  *cr = byte_eq_mask16(v, 0x0D0D0D0Du) & keep;
 }
 
 __global__ __launch_bounds__(kFaThreads) void fa_count_kernel(FaArgs a) {
@@ -374,97 +361,13 @@ __global__ __launch_bounds__(kFaThreads) void fa_piece_kernel(FaArgs a, FaRender
   o.p_len[t] = (uint32_t)(left < kFaPiece ? left : kFaPiece);
 }
 
-// wavecopy.h's SpanGroup for pieces that do not follow one another in the output
-struct FaGroup {
-  uint64_t src[kFaGroup], o[kFaGroup];
-  uint64_t fa[kFaGroup];  // first whole chunk (16-byte aligned)
-  uint64_t g[kFaGroup];   // start of the partial tail chunk
-  uint32_t hl[kFaGroup];  // head bytes, before fa
-  uint32_t fc[kFaGroup];  // whole chunks of pieces 0..k (inclusive count)
-  uint32_t bc[kFaGroup];  // byte-stored bytes of pieces 0..k (inclusive count)
-};
-
 __global__ __launch_bounds__(kFaThreads) void fa_copy_kernel(FaArgs a, FaRenderArgs o) {
-  __shared__ FaGroup groups[kFaWaves];
+  __shared__ PieceGroup groups[kFaWaves];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t t0 = ((uint64_t)blockIdx.x * kFaWaves + wave) * kFaGroup;
   if (t0 >= o.n_pieces) return;  // the whole wave
   const uint32_t m = (uint32_t)(o.n_pieces - t0 < kFaGroup ? o.n_pieces - t0 : kFaGroup);
-  FaGroup& L = groups[wave];
-  const uint8_t* __restrict__ text = a.text;
-  uint8_t* __restrict__ out = o.out;
-  // A piece's whole 16-byte chunks [fa, g) are stored as vectors, its head
-  // [o, fa) and tail [g, e) byte by byte: a chunk shared with a neighbour or
-  // with a literal byte is never stored whole.
-  uint32_t nf = 0, nb = 0;
-  if (lane < m) {
-    const uint64_t d = o.p_dst[t0 + lane], e = d + o.p_len[t0 + lane];
-    const uint64_t a16 = (d + 15) & ~15ull;
-    uint64_t fa = e, g = e;
-    if (a16 + 16 <= e) {
-      fa = a16;
-      g = e & ~15ull;
-      nf = (uint32_t)((g - fa) >> 4);
-    }
-    L.src[lane] = o.p_src[t0 + lane];
-    L.o[lane] = d;
-    L.fa[lane] = fa;
-    L.g[lane] = g;
-    L.hl[lane] = (uint32_t)(fa - d);
-    nb = (uint32_t)(fa - d + e - g);
-  }
-  const uint32_t fc = wave_scan(nf), bc = wave_scan(nb);
-  if (lane < m) {
-    L.fc[lane] = fc;
-    L.bc[lane] = bc;
-  }
-  const uint32_t n_fast = (uint32_t)__builtin_amdgcn_readlane((int)fc, (int)m - 1);
-  const uint32_t n_bytes = (uint32_t)__builtin_amdgcn_readlane((int)bc, (int)m - 1);
-  __builtin_amdgcn_wave_barrier();
-  for (uint32_t q0 = 0; q0 < n_fast; q0 += 64 * kSpanUnroll) {
-    uint4 lo[kSpanUnroll], hi[kSpanUnroll];
-    uint64_t dst[kSpanUnroll];
-    uint32_t sh[kSpanUnroll];
-#pragma unroll
-    for (int j = 0; j < kSpanUnroll; ++j) {
-      const uint32_t q = q0 + lane + 64 * j;
-      if (q < n_fast) {
-        const uint32_t k = count_le(L.fc, m, q);
-        const uint64_t C = L.fa[k] + 16ull * (q - (k ? L.fc[k - 1] : 0u));
-        const uint64_t sa = L.src[k] + (C - L.o[k]);  // sa + 16 <= the piece's end in the text
-        dst[j] = C;
-        sh[j] = (uint32_t)(sa & 15);
-        const uint8_t* sb = text + (sa & ~15ull);
-        lo[j] = *reinterpret_cast<const uint4*>(sb);
-        hi[j] = sh[j] ? *reinterpret_cast<const uint4*>(sb + 16) : lo[j];  // starts below n
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kSpanUnroll; ++j)
-      if (q0 + lane + 64 * j < n_fast)
-        *reinterpret_cast<uint4*>(out + dst[j]) = funnel16_lane(lo[j], hi[j], sh[j]);
-  }
-  for (uint32_t i0 = 0; i0 < n_bytes; i0 += 64 * kSpanBytes) {
-    const uint8_t* sp[kSpanBytes];
-    uint64_t x[kSpanBytes];
-#pragma unroll
-    for (int j = 0; j < kSpanBytes; ++j) {
-      const uint32_t i = i0 + lane + 64 * j;
-      sp[j] = nullptr;
-      if (i < n_bytes) {
-        const uint32_t k = count_le(L.bc, m, i);
-        const uint32_t r = i - (k ? L.bc[k - 1] : 0u);
-        x[j] = r < L.hl[k] ? L.o[k] + r : L.g[k] + (r - L.hl[k]);
-        sp[j] = text + L.src[k] + (x[j] - L.o[k]);
-      }
-    }
-    uint8_t v[kSpanBytes];
-#pragma unroll
-    for (int j = 0; j < kSpanBytes; ++j) v[j] = sp[j] ? *sp[j] : 0;
-#pragma unroll
-    for (int j = 0; j < kSpanBytes; ++j)
-      if (sp[j]) out[x[j]] = v[j];
-  }
+  piece_group_copy(groups[wave], m, o.p_src + t0, o.p_dst + t0, o.p_len + t0, a.text, o.out, lane);
 }
 
 hipError_t fa_sum_scan(void* tmp, size_t& tmp_bytes, const uint64_t* in, uint64_t* out, uint64_t n,

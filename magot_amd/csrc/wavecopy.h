@@ -145,4 +145,101 @@ __device__ __forceinline__ void span_group_copy(SpanGroup& L, uint32_t m,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Grouped piece copy: SpanGroup's deal for pieces that do not follow one
+// another in the output.  One wave copies m <= kSpanGroup pieces, piece k the
+// len[k] bytes at base + src[k] to out + dst[k].  A piece's whole 16-byte
+// chunks [fa, g) are stored as vectors, its head [o, fa) and tail [g, e) byte
+// by byte: a chunk shared with a neighbour or with a byte another kernel
+// writes is never stored whole.  `base` is 16-byte aligned and readable to the
+// next multiple of 16 behind every piece and 16 more.  Used by the FASTA
+// reflow (fastarec.hip) and the renamed text (rename.hip).
+// ---------------------------------------------------------------------------
+struct PieceGroup {
+  uint64_t src[kSpanGroup], o[kSpanGroup];
+  uint64_t fa[kSpanGroup];  // first whole chunk (16-byte aligned)
+  uint64_t g[kSpanGroup];   // start of the partial tail chunk
+  uint32_t hl[kSpanGroup];  // head bytes, before fa
+  uint32_t fc[kSpanGroup];  // whole chunks of pieces 0..k (inclusive count)
+  uint32_t bc[kSpanGroup];  // byte-stored bytes of pieces 0..k (inclusive count)
+};
+
+// every lane of the wave active; src, dst, len point at the group's first piece
+__device__ __forceinline__ void piece_group_copy(PieceGroup& L, uint32_t m,
+                                                 const uint64_t* __restrict__ src,
+                                                 const uint64_t* __restrict__ dst_of,
+                                                 const uint32_t* __restrict__ len,
+                                                 const uint8_t* __restrict__ base,
+                                                 uint8_t* __restrict__ out, uint32_t lane) {
+  uint32_t nf = 0, nb = 0;
+  if (lane < m) {
+    const uint64_t d = dst_of[lane], e = d + len[lane];
+    const uint64_t a16 = (d + 15) & ~15ull;
+    uint64_t fa = e, g = e;
+    if (a16 + 16 <= e) {
+      fa = a16;
+      g = e & ~15ull;
+      nf = (uint32_t)((g - fa) >> 4);
+    }
+    L.src[lane] = src[lane];
+    L.o[lane] = d;
+    L.fa[lane] = fa;
+    L.g[lane] = g;
+    L.hl[lane] = (uint32_t)(fa - d);
+    nb = (uint32_t)(fa - d + e - g);
+  }
+  const uint32_t fc = wave_scan(nf), bc = wave_scan(nb);
+  if (lane < m) {
+    L.fc[lane] = fc;
+    L.bc[lane] = bc;
+  }
+  const uint32_t n_fast = (uint32_t)__builtin_amdgcn_readlane((int)fc, (int)m - 1);
+  const uint32_t n_bytes = (uint32_t)__builtin_amdgcn_readlane((int)bc, (int)m - 1);
+  __builtin_amdgcn_wave_barrier();
+  for (uint32_t q0 = 0; q0 < n_fast; q0 += 64 * kSpanUnroll) {
+    uint4 lo[kSpanUnroll], hi[kSpanUnroll];
+    uint64_t dst[kSpanUnroll];
+    uint32_t sh[kSpanUnroll];
+#pragma unroll
+    for (int j = 0; j < kSpanUnroll; ++j) {
+      const uint32_t q = q0 + lane + 64 * j;
+      if (q < n_fast) {
+        const uint32_t k = count_le(L.fc, m, q);
+        const uint64_t C = L.fa[k] + 16ull * (q - (k ? L.fc[k - 1] : 0u));
+        const uint64_t sa = L.src[k] + (C - L.o[k]);  // sa + 16 <= the piece's end in its source
+        dst[j] = C;
+        sh[j] = (uint32_t)(sa & 15);
+        const uint8_t* sb = base + (sa & ~15ull);
+        lo[j] = *reinterpret_cast<const uint4*>(sb);
+        hi[j] = sh[j] ? *reinterpret_cast<const uint4*>(sb + 16) : lo[j];  // starts inside the piece
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kSpanUnroll; ++j)
+      if (q0 + lane + 64 * j < n_fast)
+        *reinterpret_cast<uint4*>(out + dst[j]) = funnel16_lane(lo[j], hi[j], sh[j]);
+  }
+  for (uint32_t i0 = 0; i0 < n_bytes; i0 += 64 * kSpanBytes) {
+    const uint8_t* sp[kSpanBytes];
+    uint64_t x[kSpanBytes];
+#pragma unroll
+    for (int j = 0; j < kSpanBytes; ++j) {
+      const uint32_t i = i0 + lane + 64 * j;
+      sp[j] = nullptr;
+      if (i < n_bytes) {
+        const uint32_t k = count_le(L.bc, m, i);
+        const uint32_t r = i - (k ? L.bc[k - 1] : 0u);
+        x[j] = r < L.hl[k] ? L.o[k] + r : L.g[k] + (r - L.hl[k]);
+        sp[j] = base + L.src[k] + (x[j] - L.o[k]);
+      }
+    }
+    uint8_t v[kSpanBytes];
+#pragma unroll
+    for (int j = 0; j < kSpanBytes; ++j) v[j] = sp[j] ? *sp[j] : 0;
+#pragma unroll
+    for (int j = 0; j < kSpanBytes; ++j)
+      if (sp[j]) out[x[j]] = v[j];
+  }
+}
+
 }  // namespace magot

@@ -1926,6 +1926,151 @@ class FastaRecords(object):
             pass
 
 
+def _blob_of(items):
+    """(the byte strings joined as a uint8 array, their len + 1 offsets)"""
+    off = np.zeros(len(items) + 1, np.uint64)
+    if items:
+        off[1:] = np.cumsum([len(x) for x in items], dtype=np.uint64)
+    return np.frombuffer(b''.join(items), np.uint8), off
+
+
+def py2_string_hashes(keys):
+    """CPython 2.7's string hash (py2order.str_hash) of every byte string of
+    ``keys`` as a uint64 array: one numpy pass per byte position, over the keys
+    that long."""
+    blob, off = _blob_of(keys)
+    length = np.diff(off)
+    h = np.zeros(len(keys), np.uint64)
+    live = np.flatnonzero(length)
+    h[live] = blob[off[live].astype(np.int64)].astype(np.uint64) << np.uint64(7)
+    with np.errstate(over='ignore'):
+        for i in range(int(length.max()) if len(keys) else 0):
+            live = live[length[live] > i]
+            c = blob[(off[live] + np.uint64(i)).astype(np.int64)].astype(np.uint64)
+            h[live] = (h[live] * np.uint64(1000003)) ^ c
+    h ^= length
+    h[h == np.uint64(0xFFFFFFFFFFFFFFFF)] = np.uint64(0xFFFFFFFFFFFFFFFE)
+    h[length == 0] = 0
+    return h
+
+
+class NameReplacer(object):
+    """replace_names over a resident text (magot_rename_*;
+    genome_tools.py:431-446): the words a table names, each ending at the
+    one-byte delimiter ``d``, replaced by the table's values.  The names go into
+    an open-addressing table keyed by a hash taken from a name's last byte to
+    its first; one lane per ``d`` of the text walks left over at most the
+    longest name, probes at every length the table has, compares the bytes of a
+    hash hit and keeps the hit of lowest rank; a scan lays the output out and a
+    grouped copy writes it.  Exact where no name and no value holds ``d`` and no
+    key's value feeds a later key: genome_tools.replace_names checks that.
+    ``parse`` returns (None, reason) where the device declines: 'too_large',
+    'hash_collision', 'table_too_large'."""
+
+    PASSES = ('table', 'field_ends', 'match', 'layout', 'render', 'copy')
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.n_lines = self.n_fields = self.n_hits = self.out_bytes = 0
+        self.upload_ms = 0.0
+
+    @classmethod
+    def parse(cls, data, names, values, d, ranks=None, hash_bits=64, max_bytes=0, ctx=None):
+        """The text in ``data`` (bytes, a buffer, an mmap, numpy) made resident
+        and matched against the table: ``names`` distinct byte strings of 1 to
+        ``params()['max_name']`` bytes, ``values`` one byte string each, ``d``
+        the delimiter (one byte, not LF), ``ranks`` each name's place in the
+        order the reference tries the keys (default: as listed).  ``hash_bits``:
+        the low bits of the hash the names are looked up by (two names in one
+        bucket decline the call; fewer than 64 bits only serve to test that).
+        ``max_bytes``: a longer text is declined (0: a quarter of the free
+        device memory)."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(data)
+        names, values = [bytes(x) for x in names], [bytes(x) for x in values]
+        if len(values) != len(names):
+            raise ValueError('one value per name')
+        if isinstance(d, str):
+            d = d.encode('latin-1')
+        if len(d) != 1:
+            raise ValueError('the delimiter is one byte')
+        rank = np.ascontiguousarray(np.arange(len(names)) if ranks is None else ranks,
+                                    dtype=np.uint32).reshape(-1)
+        if len(rank) != len(names):
+            raise ValueError('one rank per name')
+        name_blob, name_off = _blob_of(names)
+        val_blob, val_off = _blob_of(values)
+        h, reason = ctypes.c_void_p(), ctypes.c_uint32()
+        rc = _lib.lib().magot_rename_parse(
+            self.ctx.handle, _text_ptr(view), len(view), _text_ptr(name_blob), ptr(name_off),
+            _text_ptr(val_blob), ptr(val_off), ptr(rank) if len(rank) else None, len(names), d[0],
+            int(hash_bits), int(max_bytes or 0), ctypes.byref(h), ctypes.byref(reason))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None, _lib.RENAME_REASONS[reason.value]
+        check(rc, 'magot_rename_parse')
+        self.handle = h
+        sizes = [ctypes.c_uint64() for _ in range(4)]
+        check(_lib.lib().magot_rename_sizes(h, *[ctypes.byref(x) for x in sizes]),
+              'magot_rename_sizes')
+        self.n_lines, self.n_fields, self.n_hits, self.out_bytes = [x.value for x in sizes]
+        self.upload_ms = float(_lib.lib().magot_rename_upload_ms(h))
+        return self
+
+    @staticmethod
+    def params():
+        """{'max_name': the longest name in bytes, 'text_block': the bytes per
+        workgroup of the field index, 'piece': the bytes of an unchanged run one
+        lane slot of the copy takes}"""
+        vals = [ctypes.c_uint32() for _ in range(3)]
+        _lib.lib().magot_rename_params(*[ctypes.byref(v) for v in vals])
+        return dict(zip(('max_name', 'text_block', 'piece'), [v.value for v in vals]))
+
+    def hits(self):
+        """The rewritten fields in text order, as a dict of arrays: 'end' (the
+        offset of the field's delimiter) and 'key' (the index of the name)."""
+        end = np.zeros(max(self.n_hits, 1), np.uint64)
+        key = np.zeros(max(self.n_hits, 1), np.uint32)
+        check(_lib.lib().magot_rename_hits(self.ctx.handle, self.handle, ptr(end), ptr(key)),
+              'magot_rename_hits')
+        return {'end': end[:self.n_hits], 'key': key[:self.n_hits]}
+
+    def render(self):
+        """What the reference prints, as one uint8 array."""
+        need = ctypes.c_uint64()
+        check(_lib.lib().magot_rename_render(self.ctx.handle, self.handle, ctypes.byref(need)),
+              'magot_rename_render')
+        out = np.empty(max(need.value, 1), np.uint8)
+        check(_lib.lib().magot_rename_render_fetch(self.ctx.handle, self.handle, ptr(out),
+                                                   need.value), 'magot_rename_render_fetch')
+        return out[:need.value]
+
+    def time(self, iters):
+        """Mean device ms per pass (PASSES; 'render': the copy into the output,
+        'out_bytes' bytes; 'copy': a device copy of the text, 'text_bytes' bytes)
+        (magot_rename_time)."""
+        ms = np.zeros(len(self.PASSES), np.float64)
+        n, m = ctypes.c_uint64(), ctypes.c_uint64()
+        check(_lib.lib().magot_rename_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                           ctypes.byref(n), ctypes.byref(m)), 'magot_rename_time')
+        out = dict(zip(self.PASSES, ms.tolist()))
+        out['text_bytes'] = n.value
+        out['out_bytes'] = m.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_rename_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SiteCounts(object):
     """composition_by_site's counting pass over a resident genome
     (magot_site_*, genome_tools.py:488-503): the alignment's rows are contigs of

@@ -28,6 +28,8 @@
     python -m magot_amd.genome_tools exclude_from_fasta <fasta> <names.txt | name,name,...>
            [just_firstword=True] [order=py2|insertion] [native=False]
     python -m magot_amd.genome_tools fasta2tab <fasta> [native=False]
+    python -m magot_amd.genome_tools replace_names <text> <names.tsv> [name_end=';']
+           [order=py2|insertion] [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -1798,6 +1800,186 @@ def fasta2tab(fasta_file, native='True'):
 fasta2tab.last_path = None
 
 
+def _replace_table(table):
+    """genome_tools.py:436-440 as bytes: (name, f1) of every line of the table
+    in file order.  Lines end at LF only; f1 of a two-field line keeps its LF.
+    A line without a TAB is the reference's IndexError."""
+    rows = []
+    for line in table.split(b'\n'):
+        rows.append(line + b'\n')
+    if rows[-1] == b'\n':  # what is behind the last LF: nothing
+        rows.pop()
+    else:
+        rows[-1] = rows[-1][:-1]  # a last line without LF
+    out = []
+    for line in rows:
+        fields = line.split(b'\t')
+        if len(fields) < 2:
+            raise IndexError('list index out of range')
+        out.append((fields[0], fields[1]))
+    return out
+
+
+def _replace_dict(rows, name_end, order):
+    """(names, values) of the dict the reference fills, in the order it is
+    iterated (its keys are name + name_end): a repeated name keeps its first
+    place and takes its last value."""
+    table = {}
+    for name, f1 in rows:
+        table[name] = f1
+    names = list(table)
+    if order == 'py2':
+        from . import py2order
+        keys = py2order.dict_order([(n + name_end).decode('latin-1') for n in names])
+        names = [k.encode('latin-1')[:len(k) - len(name_end)] for k in keys]
+    return names, [table[n] for n in names]
+
+
+def _replace_host(text, keys, values):
+    """The reference's loop restated over bytes: for each line every key in
+    dict order, each seeing the result of the keys before it; the line less its
+    last byte, and an LF."""
+    out = []
+    lines = text.split(b'\n')
+    last = lines.pop()
+    lines = [line + b'\n' for line in lines] + ([last] if last else [])
+    pairs = list(zip(keys, values))
+    for line in lines:
+        for word, new in pairs:
+            if word in line:
+                line = line.replace(word, new)
+        out.append(line[:-1] + b'\n')
+    return out
+
+
+def _replace_chains(names, values):
+    """Whether a key's value can feed a later key (names and values in rank
+    order): some name_j, j after i, is a suffix of f1_i, or f1_i is a proper
+    suffix of name_j.  Sets probed with every suffix: table bytes x longest
+    name probes, never all pairs."""
+    rank_of = {n: r for r, n in enumerate(names)}
+    sizes = sorted({len(n) for n in names})  # only a suffix as long as a name can be one
+    first_with = {}  # value -> the lowest rank that has it; only values shorter than a name
+    for r, v in enumerate(values):
+        if v.endswith(b'\n'):  # no name holds an LF: neither relation can hold
+            continue
+        if not v:  # a proper suffix of every name
+            if r != len(names) - 1:
+                return True
+            continue
+        if len(v) < sizes[-1]:
+            first_with.setdefault(v, r)
+        for k in sizes:
+            if k > len(v):
+                break
+            if rank_of.get(v[len(v) - k:], -1) > r:
+                return True
+    if first_with:
+        for r, n in enumerate(names):
+            for k in range(1, len(n)):
+                if first_with.get(n[len(n) - k:], r) < r:
+                    return True
+    return False
+
+
+def _replace_decline(rows, name_end, order):
+    """None when the device path prints what the reference prints, else the
+    reason it is not taken; with None also the table for engine.NameReplacer:
+    (names first seen, their last values, their ranks)."""
+    if len(name_end) != 1 or name_end == b'\n':
+        return 'name_end', None
+    table = {}
+    for name, f1 in rows:
+        table[name] = f1
+    names, values = list(table), list(table.values())
+    if any(not n for n in names):
+        return 'empty_name', None
+    if max([len(n) for n in names] or [0]) > engine.NameReplacer.params()['max_name']:
+        return 'long_name', None
+    if any(name_end in n for n in names):
+        return 'delimiter_in_name', None
+    if any(name_end in v for v in values):
+        return 'delimiter_in_value', None
+    rank = np.arange(len(names), dtype=np.uint32)
+    if order == 'py2' and names:
+        perm = engine.py2_order_of_hashes(engine.py2_string_hashes([n + name_end for n in names]))
+        rank[perm.astype(np.int64)] = np.arange(len(names), dtype=np.uint32)
+    by_rank = np.argsort(rank, kind='stable')
+    if _replace_chains([names[i] for i in by_rank], [values[i] for i in by_rank]):
+        return 'chain', None
+    return None, (names, values, rank)
+
+
+def replace_names(text_file, replace_table, name_end=' ', order='py2', native='True'):
+    """genome_tools.py:431-446: the words of a text renamed from a table.  Every
+    line of ``replace_table`` is ``name TAB value``; the value of a two-field
+    line keeps its LF (and a CR before it), a third field or a trailing TAB ends
+    it before.  A line without a TAB is an IndexError before anything is
+    printed.  A repeated name keeps its first place and takes its last value.
+    For every line of ``text_file``, for every key ``name + name_end`` in the
+    order a Python 2 dict of the keys iterates (``order='py2'``) or first seen
+    (``order='insertion'``), all occurrences of the key become ``value +
+    name_end``, each key seeing the result of the keys before it; the line is
+    printed without its last byte (its LF; the last byte of a final line
+    without one).  Lines end at LF only.
+
+    On the device (engine.NameReplacer) for two regular files when ``name_end``
+    is one byte other than LF, no name is empty, longer than the kernel's bound
+    or holds ``name_end``, no value holds it, and no key's value feeds a later
+    key (some later name a suffix of the value, or the value a proper suffix of
+    a later name): then a field between two delimiters is rewritten at most
+    once, by the first key in dict order whose name is a suffix of it.
+    Otherwise, where the device declines and with ``native=False``, the loop on
+    the host restates the reference.  Nothing is written before the path is
+    known.  ``replace_names.last_path`` names the path the last call took."""
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'py2' or 'insertion'")
+    clock = _Clock()
+    name_end = name_end.encode('latin-1')
+    with open(text_file, 'rb'):  # the reference opens the text first
+        pass
+    with open(replace_table, 'rb') as fh:
+        rows = _replace_table(fh.read())
+    clock.lap('table')
+    text = None
+    if native != 'True':
+        why = "native != 'True'"
+    elif not all(isinstance(p, str) and os.path.isfile(p) for p in (text_file, replace_table)):
+        why = 'not a regular file'
+    else:
+        why, table = _replace_decline(rows, name_end, order)
+        clock.lap('decision')
+        if why is None:
+            data = genome.read_buffer(text_file)
+            clock.lap('open')
+            names, values, rank = table
+            rep = engine.NameReplacer.parse(data, names, values, name_end, rank)
+            clock.lap('kernels')
+            if isinstance(rep, tuple):
+                why = rep[1]
+            else:
+                try:
+                    text = rep.render()
+                finally:
+                    rep.close()
+                clock.lap('render')
+    if text is not None:
+        replace_names.last_path = ('replace_names', 'native', None)
+        _write_bytes(text)
+    else:
+        replace_names.last_path = ('replace_names', 'host', why)
+        with open(text_file, 'rb') as fh:
+            data = fh.read()
+        names, values = _replace_dict(rows, name_end, order)
+        _write_bytes(*_replace_host(data, [n + name_end for n in names],
+                                    [v + name_end for v in values]))
+    clock.lap('write')
+    clock.emit()
+
+
+replace_names.last_path = None
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
          'fqstats': fqstats, 'purge_overlaps': purge_overlaps, 'besthits_from_psl': besthits_from_psl,
          'extract_upstream_downstream': extract_upstream_downstream,
@@ -1807,7 +1989,8 @@ TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at
          'mask_from_gff': mask_from_gff, 'depth_from_gff': depth_from_gff,
          'composition_by_site': composition_by_site,
          'heterozygosity_from_vcf': heterozygosity_from_vcf,
-         'exclude_from_fasta': exclude_from_fasta, 'fasta2tab': fasta2tab}
+         'exclude_from_fasta': exclude_from_fasta, 'fasta2tab': fasta2tab,
+         'replace_names': replace_names}
 
 
 def parse_argv(argv):
