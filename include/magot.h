@@ -361,6 +361,17 @@ int magot_debug_plan(const uint8_t* const* seqs, const uint64_t* lens, uint32_t 
                      uint64_t* tx_nuc, uint64_t* tx_pep, uint64_t* lay_nuc, uint64_t* lay_pep,
                      void* tiles);
 
+/* Debug: the byte index that magot_psl_parse, magot_vcf_parse,
+ * magot_fastarec_parse and magot_rename_parse begin with, on its own.  The
+ * len bytes of text go to the device; the first index_len <= len of them are
+ * the text that is indexed (the rest lie behind its end and must not be
+ * counted).  *n_out: the occurrences of `byte` (0..255) in it; pos_out (NULL,
+ * or room for index_len entries) receives their offsets in text order;
+ * *second_count_out (may be NULL) the occurrences of second_byte, -1 for none. */
+int magot_debug_text_index(magot_ctx* ctx, const uint8_t* text, uint64_t len, uint64_t index_len,
+                           uint32_t byte, int32_t second_byte, uint64_t* pos_out, uint64_t* n_out,
+                           uint64_t* second_count_out);
+
 /*
  * Raw-sequence batch ops over n byte strings (seq_off has n+1 entries).
  * Replaces: Sequence.reverse_compliment (genome.py:784-793).

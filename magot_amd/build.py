@@ -23,8 +23,9 @@ SOURCES = ['abi.hip', 'abi_genome.hip', 'abi_plan.hip', 'abi_seq.hip', 'abi_orf.
            'tileplan.cpp', 'orfcall.hip', 'maskplan.cpp', 'maskgen.hip', 'track.hip', 'depth.hip',
            'fastq.hip', 'overlap.hip', 'overlapplan.cpp', 'abi_psl.hip', 'psl.hip', 'pslhost.cpp',
            'abi_site.hip', 'sitecount.hip', 'sitehost.cpp', 'abi_vcf.hip', 'vcf.hip',
-           'vcfhost.cpp', 'abi_fasta.hip', 'fastarec.hip', 'abi_rename.hip', 'rename.hip']
-HEADERS = ['common.h', 'hostutil.h', 'wavecopy.h', 'abi_internal.h',
+           'vcfhost.cpp', 'abi_fasta.hip', 'fastarec.hip', 'abi_rename.hip', 'rename.hip',
+           'textindex.hip']
+HEADERS = ['common.h', 'hostutil.h', 'wavecopy.h', 'abi_internal.h', 'textindex.h',
            os.path.join('..', '..', 'include', 'magot.h')]
 
 CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function',

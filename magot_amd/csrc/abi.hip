@@ -121,4 +121,59 @@ int magot_ctx_elapsed(magot_ctx* ctx, double* ms) {
   return MAGOT_OK;
 }
 
+// The byte index of the resident-text tools on its own (textindex.hip, plain
+// mode): the tests' direct view of its tail mask and block sums.
+int magot_debug_text_index(magot_ctx* ctx, const uint8_t* text, uint64_t len, uint64_t index_len,
+                           uint32_t byte, int32_t second_byte, uint64_t* pos_out, uint64_t* n_out,
+                           uint64_t* second_count_out) {
+  if (int rc = bind(ctx)) return rc;
+  if (!n_out || (len && !text) || index_len > len || byte > 255 || second_byte < -1 ||
+      second_byte > 255) {
+    set_error("magot_debug_text_index: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  hipStream_t s = ctx->stream;
+  const bool second = second_byte >= 0;
+  TextIndexArgs ix{};
+  ix.n = index_len;
+  ix.n_blocks = depth_text_blocks(index_len);
+  ix.byte = byte;
+  ix.byte2 = second ? (uint32_t)second_byte : kTextNoByte;
+  const size_t tmp_bytes = exclusive_sum_bytes<uint64_t>(ix.n_blocks + 1);
+  Carve cv;
+  const uint64_t o_text = cv.take<uint8_t>(len + kTextPad);
+  uint64_t o_blk[4];  // blk, pre, blk2, pre2
+  for (uint64_t& o : o_blk) o = cv.take<uint64_t>(ix.n_blocks + 1);
+  const uint64_t o_tmp = cv.take<uint8_t>(tmp_bytes);
+  // at most one occurrence per byte; room for every byte a lane loads, so that an
+  // index that counted behind the text's end would be a wrong answer, not a wild store
+  const uint64_t o_pos = cv.take<uint64_t>(len + kTextPad);
+  DevBuf buf;
+  MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
+  char* base = static_cast<char*>(buf.p);
+  ix.text = reinterpret_cast<const uint8_t*>(base + o_text);
+  ix.blk = reinterpret_cast<uint64_t*>(base + o_blk[0]);
+  ix.pre = reinterpret_cast<uint64_t*>(base + o_blk[1]);
+  ix.blk2 = reinterpret_cast<uint64_t*>(base + o_blk[2]);
+  ix.pre2 = reinterpret_cast<uint64_t*>(base + o_blk[3]);
+  ix.pos = reinterpret_cast<uint64_t*>(base + o_pos);
+  if (len) MAGOT_HIP_TRY(hipMemcpyAsync(base + o_text, text, len, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(launch_text_count(ix, base + o_tmp, tmp_bytes, s));
+  MAGOT_HIP_TRY(launch_text_fill(ix, kTextFillPlain, s));
+  uint64_t total = 0, total2 = 0;
+  MAGOT_HIP_TRY(hipMemcpyAsync(&total, ix.pre + ix.n_blocks, 8, hipMemcpyDeviceToHost, s));
+  if (second)
+    MAGOT_HIP_TRY(hipMemcpyAsync(&total2, ix.pre2 + ix.n_blocks, 8, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  if (total > index_len) {
+    set_error("magot_debug_text_index: more occurrences than bytes");
+    return MAGOT_ERR_STATE;
+  }
+  if (pos_out && total)
+    MAGOT_HIP_TRY(hipMemcpy(pos_out, ix.pos, total * 8, hipMemcpyDeviceToHost));
+  *n_out = total;
+  if (second_count_out) *second_count_out = total2;
+  return MAGOT_OK;
+}
+
 }  // extern "C"

@@ -7,7 +7,7 @@ using namespace magot;
 
 struct magot_fastarec {
   magot_ctx* ctx = nullptr;
-  void* text_mem = nullptr;  // the text, the block counts and their scan's scratch
+  ResidentText rt;           // the text and its line index; the status word
   void* line_mem = nullptr;  // everything sized by the lines
   void* rec_mem = nullptr;   // everything sized by the records
   void* out_mem = nullptr;   // the last rendered text and its tables
@@ -16,10 +16,8 @@ struct magot_fastarec {
   FaRenderArgs r{};
   uint64_t out_bytes = 0;
   bool rendered = false;
-  void* tmp0 = nullptr;
   void* tmp = nullptr;
-  size_t tmp0_bytes = 0, tmp_bytes = 0;
-  float upload_ms = 0.f;
+  size_t tmp_bytes = 0;
 };
 
 namespace {
@@ -113,9 +111,7 @@ int fa_plan_render(magot_fastarec* p, const uint32_t* rec, uint64_t n, uint32_t 
 hipError_t fa_pass(const magot_fastarec* p, int k, hipStream_t s) {
   const FaArgs& a = p->a;
   switch (k) {
-    case 0:
-      if (hipError_t e = launch_fa_count(a, p->tmp0, p->tmp0_bytes, s)) return e;
-      return launch_fa_fill(a, s);
+    case 0: return text_index_pass(a.ix, p->rt, kTextFillLinesCr, s);
     case 1: return launch_fa_lines(a, p->tmp, p->tmp_bytes, s);
     case 2: return launch_fa_names(a, p->tmp, p->tmp_bytes, s);
     case 3: return launch_fa_sort(a, p->tmp, p->tmp_bytes, s);
@@ -123,7 +119,7 @@ hipError_t fa_pass(const magot_fastarec* p, int k, hipStream_t s) {
       if (hipError_t e = launch_fa_keys(a, p->tmp, p->tmp_bytes, s)) return e;
       return launch_fa_rows(a, s);
     case 5: return launch_fa_render(a, p->r, s);
-    default: return hipMemcpyAsync(p->copy_mem, a.text, a.n, hipMemcpyDeviceToDevice, s);
+    default: return hipMemcpyAsync(p->copy_mem, a.ix.text, a.ix.n, hipMemcpyDeviceToDevice, s);
   }
 }
 
@@ -138,7 +134,7 @@ void magot_fastarec_destroy(magot_fastarec* p) {
   if (p->out_mem) (void)hipFree(p->out_mem);
   if (p->rec_mem) (void)hipFree(p->rec_mem);
   if (p->line_mem) (void)hipFree(p->line_mem);
-  if (p->text_mem) (void)hipFree(p->text_mem);
+  if (p->rt.mem) (void)hipFree(p->rt.mem);
   delete p;
 }
 
@@ -163,11 +159,7 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
     set_error("magot_fastarec_parse: hash_bits outside 1..64");
     return MAGOT_ERR_ARG;
   }
-  if (!max_bytes) {  // the line tables of short lines take as much again as the text
-    size_t free_b = 0, total_b = 0;
-    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    max_bytes = free_b / 4;
-  }
+  if (int rc = resident_text_budget(&max_bytes)) return rc;
   if (len > max_bytes) return fa_decline(reason, line, MAGOT_FASTAREC_TOO_LARGE, 0);
   if (len && text[0] != '>') return fa_decline(reason, line, MAGOT_FASTAREC_LEADING_TEXT, 1);
 
@@ -178,39 +170,20 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
   magot_fastarec* p = guard.p;
   p->ctx = ctx;
   FaArgs& a = p->a;
-  a.n = len;
-  a.n_blocks = depth_text_blocks(len);
   a.hash_bits = hash_bits;
   hipStream_t s = ctx->stream;
   if (len) {
-    p->tmp0_bytes = fa_count_tmp_bytes(a.n_blocks);
-    Carve cv;
-    const uint64_t o_text = cv.take<uint8_t>(len + 32);  // 16-byte loads at and behind the last byte
-    const uint64_t o_blk = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_pre = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp0_bytes);
-    const uint64_t o_status = cv.take<unsigned long long>(1);
-    MAGOT_HIP_TRY(hipMalloc(&p->text_mem, cv.used + 256));
-    char* base = static_cast<char*>(p->text_mem);
-    a.text = at<const uint8_t>(base, o_text);
-    a.blk = at<uint64_t>(base, o_blk);
-    a.pre = at<uint64_t>(base, o_pre);
-    p->tmp0 = base + o_tmp;
-    a.status = at<unsigned long long>(base, o_status);
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
-    if (int rc = upload_text(ctx, text, len, at<uint8_t>(base, o_text))) return rc;
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
+    if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte, sizeof(unsigned long long),
+                                    &p->rt, &a.ix))
+      return rc;
+    a.status = a.ix.stray_status = reinterpret_cast<unsigned long long*>(p->rt.extra);
+    a.ix.stray_reason = MAGOT_FASTAREC_STRAY_CR;
     MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
-    MAGOT_HIP_TRY(launch_fa_count(a, p->tmp0, p->tmp0_bytes, s));
-    uint64_t lfs = 0;
-    MAGOT_HIP_TRY(hipMemcpyAsync(&lfs, a.pre + a.n_blocks, 8, hipMemcpyDeviceToHost, s));
-    MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    MAGOT_HIP_TRY(hipEventElapsedTime(&p->upload_ms, ctx->ev0, ctx->ev1));
-    a.n_lines = lfs + (text[len - 1] != '\n' ? 1 : 0);
-    if (a.n_lines > kFaMaxLines) return fa_decline(reason, line, MAGOT_FASTAREC_TOO_MANY_LINES, 0);
+    a.ix.n_lines = p->rt.n_lines;
+    if (a.ix.n_lines > kFaMaxLines) return fa_decline(reason, line, MAGOT_FASTAREC_TOO_MANY_LINES, 0);
   }
-  if (a.n_lines) {
-    const uint64_t L = a.n_lines;
+  if (a.ix.n_lines) {
+    const uint64_t L = a.ix.n_lines;
     p->tmp_bytes = fa_tmp_bytes(L);  // records and keys are at most the lines
     {
       Carve cv;
@@ -219,7 +192,7 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
       const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
       MAGOT_HIP_TRY(hipMalloc(&p->line_mem, cv.used + 256));
       char* base = static_cast<char*>(p->line_mem);
-      a.line_start = at<uint64_t>(base, o[0]);
+      a.ix.pos = at<uint64_t>(base, o[0]);
       a.hdr = at<uint64_t>(base, o[1]);
       a.pay = at<uint64_t>(base, o[2]);
       a.pcs = at<uint64_t>(base, o[3]);
@@ -228,7 +201,7 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
       a.pcs_pre = at<uint64_t>(base, o[6]);
       p->tmp = base + o_tmp;
     }
-    MAGOT_HIP_TRY(launch_fa_fill(a, s));
+    MAGOT_HIP_TRY(launch_text_fill(a.ix, kTextFillLinesCr, s));
     MAGOT_HIP_TRY(launch_fa_lines(a, p->tmp, p->tmp_bytes, s));
     MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_rec, a.rec_of + L, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
@@ -305,14 +278,14 @@ int magot_fastarec_sizes(const magot_fastarec* p, uint64_t* n_lines, uint64_t* n
     set_error("magot_fastarec_sizes: null handle");
     return MAGOT_ERR_ARG;
   }
-  if (n_lines) *n_lines = p->a.n_lines;
+  if (n_lines) *n_lines = p->a.ix.n_lines;
   if (n_records) *n_records = p->a.n_rec;
   if (n_with_sequence) *n_with_sequence = p->a.n_ne;
   if (n_keys) *n_keys = p->a.n_keys;
   return MAGOT_OK;
 }
 
-double magot_fastarec_upload_ms(const magot_fastarec* p) { return p ? (double)p->upload_ms : 0.0; }
+double magot_fastarec_upload_ms(const magot_fastarec* p) { return p ? (double)p->rt.upload_ms : 0.0; }
 
 int magot_fastarec_records(magot_ctx* ctx, magot_fastarec* p, uint32_t* line, uint64_t* name_off,
                            uint32_t* name_len, uint64_t* seq_len, uint64_t* hash,
@@ -441,11 +414,11 @@ int magot_fastarec_time(magot_ctx* ctx, magot_fastarec* p, int iters, double* ms
     set_error("magot_fastarec_time: bad argument");
     return MAGOT_ERR_ARG;
   }
-  if (text_bytes) *text_bytes = p->a.n;
+  if (text_bytes) *text_bytes = p->a.ix.n;
   if (reflow_bytes) *reflow_bytes = 0;
   for (int k = 0; k < kFaPasses; ++k) ms7[k] = 0;
-  if (!p->a.n_lines) return MAGOT_OK;  // an empty text: nothing was launched
-  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.n + 256));
+  if (!p->a.ix.n_lines) return MAGOT_OK;  // an empty text: nothing was launched
+  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.ix.n + 256));
   {  // the reflow that is timed: fasta2tab's
     std::vector<uint32_t> all(p->a.n_rec);
     for (uint64_t r = 0; r < p->a.n_rec; ++r) all[r] = (uint32_t)r;

@@ -122,7 +122,7 @@ inline int ensure_pin_ring(magot_ctx* ctx) {  // callers hold ctx->pin_mu
 }
 
 // A text into its device buffer through the context's two pinned buffers
-// (magot_psl_parse, magot_vcf_parse).
+// (resident_text_open).
 inline int upload_text(magot_ctx* ctx, const char* text, uint64_t len, uint8_t* dev) {
   std::lock_guard<std::mutex> lock(ctx->pin_mu);
   if (int rc = ensure_pin_ring(ctx)) return rc;
@@ -144,6 +144,95 @@ struct DevBuf {
     if (p) (void)hipFree(p);
   }
 };
+
+// A whole text resident in HBM with the byte index of textindex.hip counted
+// (magot_psl_parse, magot_vcf_parse, magot_fastarec_parse, magot_rename_parse).
+// One allocation holds the text, the block counts, their scan's scratch and
+// the caller's own slices; the owner frees `mem`.
+constexpr uint64_t kTextPad = 32;  // 16-byte loads at and behind the text's last byte
+struct ResidentText {
+  void* mem = nullptr;
+  char* extra = nullptr;  // the caller's slices, 256-byte aligned
+  void* tmp = nullptr;    // the block scan's scratch
+  size_t tmp_bytes = 0;
+  uint64_t total = 0, total2 = 0;  // occurrences of the indexed byte, of the second
+  uint64_t n_lines = 0;            // from the LF count, when one of the two bytes is LF
+  float upload_ms = 0.f;  // first enqueue to last byte on the device, the staging copies included
+};
+
+// *max_bytes == 0: a quarter of the free memory (the tables take about as much
+// again as the text)
+inline int resident_text_budget(uint64_t* max_bytes) {
+  if (*max_bytes) return MAGOT_OK;
+  size_t free_b = 0, total_b = 0;
+  MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  *max_bytes = free_b / 4;
+  return MAGOT_OK;
+}
+
+// Allocates, uploads the text between the context's event pair, runs
+// before_count(rt->extra) -- what the caller enqueues between the upload and
+// the count --, counts `byte` (and byte2 unless kTextNoByte) per text block and
+// reads the totals back.  Inside before_count ix->text, n, n_blocks, blk and
+// pre are already set (replace_names counts its values' offset from ix->text),
+// and a device-to-host copy it enqueues on the context stream has arrived on
+// return: the stream is idle then.  ix->pos and ix->n_lines are the caller's
+// to set before the fill.
+template <class F>
+int resident_text_open(magot_ctx* ctx, const char* text, uint64_t len, uint32_t byte,
+                       uint32_t byte2, uint64_t extra_bytes, F before_count, ResidentText* rt,
+                       TextIndexArgs* ix) {
+  hipStream_t s = ctx->stream;
+  const bool second = byte2 != kTextNoByte;
+  ix->n = len;
+  ix->n_blocks = depth_text_blocks(len);
+  ix->byte = byte;
+  ix->byte2 = byte2;
+  rt->tmp_bytes = exclusive_sum_bytes<uint64_t>(ix->n_blocks + 1);
+  Carve cv;
+  const uint64_t o_text = cv.take<uint8_t>(len + kTextPad);
+  uint64_t o_blk[4] = {0, 0, 0, 0};  // blk, pre, blk2, pre2
+  for (int k = 0; k < (second ? 4 : 2); ++k) o_blk[k] = cv.take<uint64_t>(ix->n_blocks + 1);
+  const uint64_t o_tmp = cv.take<uint8_t>(rt->tmp_bytes);
+  const uint64_t o_extra = cv.take<uint8_t>(extra_bytes);
+  MAGOT_HIP_TRY(hipMalloc(&rt->mem, cv.used + 256));
+  char* base = static_cast<char*>(rt->mem);
+  ix->text = reinterpret_cast<const uint8_t*>(base + o_text);
+  ix->blk = reinterpret_cast<uint64_t*>(base + o_blk[0]);
+  ix->pre = reinterpret_cast<uint64_t*>(base + o_blk[1]);
+  ix->blk2 = second ? reinterpret_cast<uint64_t*>(base + o_blk[2]) : nullptr;
+  ix->pre2 = second ? reinterpret_cast<uint64_t*>(base + o_blk[3]) : nullptr;
+  rt->tmp = base + o_tmp;
+  rt->extra = base + o_extra;
+  MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
+  if (len)
+    if (int rc = upload_text(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
+  MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
+  if (int rc = before_count(rt->extra)) return rc;
+  MAGOT_HIP_TRY(launch_text_count(*ix, rt->tmp, rt->tmp_bytes, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(&rt->total, ix->pre + ix->n_blocks, 8, hipMemcpyDeviceToHost, s));
+  if (second)
+    MAGOT_HIP_TRY(hipMemcpyAsync(&rt->total2, ix->pre2 + ix->n_blocks, 8, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  MAGOT_HIP_TRY(hipEventElapsedTime(&rt->upload_ms, ctx->ev0, ctx->ev1));
+  const uint64_t lfs = byte == '\n' ? rt->total : byte2 == '\n' ? rt->total2 : 0;
+  rt->n_lines = lfs + (len && text[len - 1] != '\n' ? 1 : 0);
+  return MAGOT_OK;
+}
+
+inline int resident_text_open(magot_ctx* ctx, const char* text, uint64_t len, uint32_t byte,
+                              uint32_t byte2, uint64_t extra_bytes, ResidentText* rt,
+                              TextIndexArgs* ix) {
+  return resident_text_open(
+      ctx, text, len, byte, byte2, extra_bytes, [](char*) { return MAGOT_OK; }, rt, ix);
+}
+
+// The index pass of the *_time entry points: the count, then the fill.
+inline hipError_t text_index_pass(const TextIndexArgs& ix, const ResidentText& rt, TextFill mode,
+                                  hipStream_t s) {
+  if (hipError_t e = launch_text_count(ix, rt.tmp, rt.tmp_bytes, s)) return e;
+  return launch_text_fill(ix, mode, s);
+}
 
 // A device allocation made on another thread while the caller goes on
 // (hipMalloc of C3's 0.8 GB of outputs takes ~10 ms).  It is joined, and

@@ -7,14 +7,12 @@ using namespace magot;
 
 struct magot_psl {
   magot_ctx* ctx = nullptr;
-  void* text_mem = nullptr;  // the text, the block counts and their scan's scratch
+  ResidentText rt;           // the text and its line index; the status words
   void* mem = nullptr;       // everything sized by the lines
   void* copy_mem = nullptr;  // magot_psl_time's copy target
   PslArgs a{};
-  void* tmp0 = nullptr;
   void* tmp = nullptr;
-  size_t tmp0_bytes = 0, tmp_bytes = 0;
-  float upload_ms = 0.f;  // first enqueue to last byte on the device, the staging copies included
+  size_t tmp_bytes = 0;
 };
 
 namespace {
@@ -25,9 +23,7 @@ constexpr int kPslPasses = 8;
 hipError_t psl_pass(const magot_psl* p, int k, hipStream_t s) {
   const PslArgs& a = p->a;
   switch (k) {
-    case 0:
-      if (hipError_t e = launch_psl_count(a, p->tmp0, p->tmp0_bytes, s)) return e;
-      return launch_psl_fill(a, s);
+    case 0: return text_index_pass(a.ix, p->rt, kTextFillLines, s);
     case 1: return launch_psl_parse(a, s);
     case 2:
       if (hipError_t e = launch_psl_compact(a, p->tmp, p->tmp_bytes, s)) return e;
@@ -37,8 +33,8 @@ hipError_t psl_pass(const magot_psl* p, int k, hipStream_t s) {
     case 5: return launch_psl_reduce(a, p->tmp, p->tmp_bytes, s);
     case 6: return launch_psl_order(a, p->tmp, p->tmp_bytes, s);
     default:
-      if (!a.n) return hipSuccess;
-      return hipMemcpyAsync(p->copy_mem, a.text, a.n, hipMemcpyDeviceToDevice, s);
+      if (!a.ix.n) return hipSuccess;
+      return hipMemcpyAsync(p->copy_mem, a.ix.text, a.ix.n, hipMemcpyDeviceToDevice, s);
   }
 }
 
@@ -64,7 +60,7 @@ void magot_psl_destroy(magot_psl* p) {
   if (p->ctx) (void)hipSetDevice(p->ctx->device);
   if (p->copy_mem) (void)hipFree(p->copy_mem);
   if (p->mem) (void)hipFree(p->mem);
-  if (p->text_mem) (void)hipFree(p->text_mem);
+  if (p->rt.mem) (void)hipFree(p->rt.mem);
   delete p;
 }
 
@@ -82,11 +78,7 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     set_error("magot_psl_parse: hash_bits outside 1..64");
     return MAGOT_ERR_ARG;
   }
-  if (!max_bytes) {  // the line tables take about as much again as a PSL's text
-    size_t free_b = 0, total_b = 0;
-    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    max_bytes = free_b / 4;
-  }
+  if (int rc = resident_text_budget(&max_bytes)) return rc;
   if (len > max_bytes) return psl_decline(reason, line, MAGOT_PSL_TOO_LARGE, 0);
 
   struct Guard {
@@ -96,40 +88,20 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
   magot_psl* p = guard.p;
   p->ctx = ctx;
   PslArgs& a = p->a;
-  a.n = len;
-  a.n_blocks = depth_text_blocks(len);
   a.hash_bits = hash_bits;
   hipStream_t s = ctx->stream;
   if (len) {
-    p->tmp0_bytes = psl_count_tmp_bytes(a.n_blocks);
-    Carve cv;
-    const uint64_t o_text = cv.take<uint8_t>(len + 16);  // a 16-byte load at the last byte
-    const uint64_t o_blk = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_pre = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp0_bytes);
-    const uint64_t o_status = cv.take<unsigned long long>(2);
-    MAGOT_HIP_TRY(hipMalloc(&p->text_mem, cv.used + 256));
-    char* base = static_cast<char*>(p->text_mem);
-    a.text = reinterpret_cast<const uint8_t*>(base + o_text);
-    a.blk = reinterpret_cast<uint64_t*>(base + o_blk);
-    a.pre = reinterpret_cast<uint64_t*>(base + o_pre);
-    p->tmp0 = base + o_tmp;
-    a.status = reinterpret_cast<unsigned long long*>(base + o_status);
+    if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte,
+                                    2 * sizeof(unsigned long long), &p->rt, &a.ix))
+      return rc;
+    a.status = reinterpret_cast<unsigned long long*>(p->rt.extra);
     a.n_uniq = a.status + 1;
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
-    if (int rc = upload_text(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
     MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
-    MAGOT_HIP_TRY(launch_psl_count(a, p->tmp0, p->tmp0_bytes, s));
-    uint64_t lfs = 0;
-    MAGOT_HIP_TRY(hipMemcpyAsync(&lfs, a.pre + a.n_blocks, 8, hipMemcpyDeviceToHost, s));
-    MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    MAGOT_HIP_TRY(hipEventElapsedTime(&p->upload_ms, ctx->ev0, ctx->ev1));
-    a.n_lines = lfs + (text[len - 1] != '\n' ? 1 : 0);
-    if (a.n_lines > kPslLineMask) return psl_decline(reason, line, MAGOT_PSL_TOO_MANY_LINES, 0);
+    a.ix.n_lines = p->rt.n_lines;
+    if (a.ix.n_lines > kPslLineMask) return psl_decline(reason, line, MAGOT_PSL_TOO_MANY_LINES, 0);
   }
-  if (a.n_lines) {
-    const uint64_t L = a.n_lines;
+  if (a.ix.n_lines) {
+    const uint64_t L = a.ix.n_lines;
     p->tmp_bytes = psl_tmp_bytes(L);
     Carve cv;
     const uint64_t o_start = cv.take<uint64_t>(L + 1), o_hash = cv.take<uint64_t>(L);
@@ -145,7 +117,7 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
     MAGOT_HIP_TRY(hipMalloc(&p->mem, cv.used + 256));
     char* base = static_cast<char*>(p->mem);
-    a.line_start = reinterpret_cast<uint64_t*>(base + o_start);
+    a.ix.pos = reinterpret_cast<uint64_t*>(base + o_start);
     a.hash = reinterpret_cast<uint64_t*>(base + o_hash);
     a.key_off = reinterpret_cast<uint64_t*>(base + o_koff);
     a.key_len = reinterpret_cast<uint32_t*>(base + o_klen);
@@ -175,7 +147,7 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     a.g_best = g32 + L;
     p->tmp = base + o_tmp;
 
-    MAGOT_HIP_TRY(launch_psl_fill(a, s));
+    MAGOT_HIP_TRY(launch_text_fill(a.ix, kTextFillLines, s));
     MAGOT_HIP_TRY(launch_psl_parse(a, s));
     MAGOT_HIP_TRY(launch_psl_compact(a, p->tmp, p->tmp_bytes, s));
     unsigned long long status = 0;
@@ -215,19 +187,19 @@ int magot_psl_sizes(const magot_psl* p, uint64_t* n_lines, uint64_t* n_pass, uin
     set_error("magot_psl_sizes: null handle");
     return MAGOT_ERR_ARG;
   }
-  if (n_lines) *n_lines = p->a.n_lines;
-  if (n_pass) *n_pass = p->a.n_lines - p->a.n_data;
+  if (n_lines) *n_lines = p->a.ix.n_lines;
+  if (n_pass) *n_pass = p->a.ix.n_lines - p->a.n_data;
   if (n_data) *n_data = p->a.n_data;
   if (n_groups) *n_groups = p->a.n_groups;
   return MAGOT_OK;
 }
 
-double magot_psl_upload_ms(const magot_psl* p) { return p ? (double)p->upload_ms : 0.0; }
+double magot_psl_upload_ms(const magot_psl* p) { return p ? (double)p->rt.upload_ms : 0.0; }
 
 int magot_psl_pass_lines(magot_ctx* ctx, magot_psl* p, uint64_t* off, uint64_t* len) {
   if (int rc = handle_of(ctx, p, "magot_psl_pass_lines", "handle")) return rc;
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  const uint64_t n = p->a.n_lines - p->a.n_data;
+  const uint64_t n = p->a.ix.n_lines - p->a.n_data;
   if (int rc = psl_fetch(off, p->a.pass_off, n)) return rc;
   return psl_fetch(len, p->a.pass_len, n);
 }
@@ -252,10 +224,10 @@ int magot_psl_time(magot_ctx* ctx, magot_psl* p, int iters, double* ms8, uint64_
     set_error("magot_psl_time: bad argument");
     return MAGOT_ERR_ARG;
   }
-  if (text_bytes) *text_bytes = p->a.n;
+  if (text_bytes) *text_bytes = p->a.ix.n;
   for (int k = 0; k < kPslPasses; ++k) ms8[k] = 0;
-  if (!p->a.n_lines) return MAGOT_OK;  // an empty text: nothing was launched
-  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.n + 256));
+  if (!p->a.ix.n_lines) return MAGOT_OK;  // an empty text: nothing was launched
+  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.ix.n + 256));
   // every pass writes what it wrote in magot_psl_parse: the answers stand
   double total[kPslPasses] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int i = 0; i < iters; ++i)

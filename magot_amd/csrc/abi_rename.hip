@@ -7,19 +7,16 @@ using namespace magot;
 
 struct magot_rename {
   magot_ctx* ctx = nullptr;
-  void* text_mem = nullptr;   // the text, the values behind it, the table and the block counts
+  ResidentText rt;            // the text and the index of its ds; the values, the table, the status
   void* field_mem = nullptr;  // everything sized by the fields
   void* hit_mem = nullptr;    // everything sized by the hits
   void* out_mem = nullptr;    // the rendered text and its pieces
   void* copy_mem = nullptr;   // magot_rename_time's copy target
   RnArgs a{};
   RnRenderArgs r{};
-  uint64_t n_lines = 0;
   bool rendered = false;
-  void* tmp0 = nullptr;  // the block scan's scratch
   void* tmp = nullptr;   // the field and hit scans' scratch
-  size_t tmp0_bytes = 0, tmp_bytes = 0;
-  float upload_ms = 0.f;
+  size_t tmp_bytes = 0;
 };
 
 namespace {
@@ -63,13 +60,11 @@ hipError_t rn_pass(const magot_rename* p, int k, hipStream_t s) {
   const RnArgs& a = p->a;
   switch (k) {
     case 0: return launch_rn_table(a, s);
-    case 1:
-      if (hipError_t e = launch_rn_count(a, p->tmp0, p->tmp0_bytes, s)) return e;
-      return launch_rn_fill(a, s);
+    case 1: return text_index_pass(a.ix, p->rt, kTextFillPlain, s);
     case 2: return launch_rn_match(a, p->tmp, p->tmp_bytes, s);
     case 3: return launch_rn_layout(a, p->tmp, p->tmp_bytes, s);
     case 4: return launch_rn_render(a, p->r, s);
-    default: return hipMemcpyAsync(p->copy_mem, a.text, a.n, hipMemcpyDeviceToDevice, s);
+    default: return hipMemcpyAsync(p->copy_mem, a.ix.text, a.ix.n, hipMemcpyDeviceToDevice, s);
   }
 }
 
@@ -84,7 +79,7 @@ void magot_rename_destroy(magot_rename* p) {
   if (p->out_mem) (void)hipFree(p->out_mem);
   if (p->hit_mem) (void)hipFree(p->hit_mem);
   if (p->field_mem) (void)hipFree(p->field_mem);
-  if (p->text_mem) (void)hipFree(p->text_mem);
+  if (p->rt.mem) (void)hipFree(p->rt.mem);
   delete p;
 }
 
@@ -152,16 +147,9 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
     a.len_mask[(l - 1) >> 6] |= 1ull << ((l - 1) & 63);
     a.max_len = std::max(a.max_len, l);
   }
-  if (!max_bytes) {  // the field tables of a text dense in delimiters take more than the text
-    size_t free_b = 0, total_b = 0;
-    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    max_bytes = free_b / 4;
-  }
+  if (int rc = resident_text_budget(&max_bytes)) return rc;
   if (len > max_bytes) return rn_decline(reason, MAGOT_RENAME_TOO_LARGE);
 
-  a.n = len;
-  a.n_blocks = depth_text_blocks(len);
-  a.delim = delim;
   a.hash_bits = hash_bits;
   a.n_keys = n_keys;
   a.cap = 2;
@@ -172,73 +160,56 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
   }
   hipStream_t s = ctx->stream;
   {
-    p->tmp0_bytes = rn_tmp_bytes(a.n_blocks + 1);
-    Carve cv;
-    const uint64_t o_text = cv.take<uint8_t>(len + 32);  // 16-byte loads at and behind the last byte
-    const uint64_t o_vals = cv.take<uint8_t>(vals_len + 32);
+    Carve cv;  // the caller's slices: the values (pieces are copied from them), the table, the status
+    const uint64_t o_vals = cv.take<uint8_t>(vals_len + kTextPad);
     const uint64_t o_names = cv.take<uint8_t>(names_len + 1);
     const uint64_t o_noff = cv.take<uint64_t>(n_keys + 1), o_voff = cv.take<uint64_t>(n_keys + 1);
     const uint64_t o_rank = cv.take<uint32_t>(n_keys + 1);
     const uint64_t o_hash = cv.take<uint64_t>(n_keys + 1);
     const uint64_t o_claim = cv.take<uint32_t>(a.cap);
     const uint64_t o_slots = cv.take<RnSlot>(a.cap);
-    const uint64_t o_blk = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_pre = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_lblk = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_lpre = cv.take<uint64_t>(a.n_blocks + 1);
-    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp0_bytes);
     const uint64_t o_status = cv.take<unsigned long long>(1);
-    MAGOT_HIP_TRY(hipMalloc(&p->text_mem, cv.used + 256));
-    char* base = static_cast<char*>(p->text_mem);
-    a.text = at<const uint8_t>(base, o_text);
-    a.val_base = o_vals - o_text;
-    a.names = at<const uint8_t>(base, o_names);
-    a.name_off = at<const uint64_t>(base, o_noff);
-    a.val_off = at<const uint64_t>(base, o_voff);
-    a.rank = at<const uint32_t>(base, o_rank);
-    a.key_hash = at<uint64_t>(base, o_hash);
-    a.claim = at<uint32_t>(base, o_claim);
-    a.slots = at<RnSlot>(base, o_slots);
-    a.blk = at<uint64_t>(base, o_blk);
-    a.pre = at<uint64_t>(base, o_pre);
-    a.lf_blk = at<uint64_t>(base, o_lblk);
-    a.lf_pre = at<uint64_t>(base, o_lpre);
-    p->tmp0 = base + o_tmp;
-    a.status = at<unsigned long long>(base, o_status);
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
-    if (len)
-      if (int rc = upload_text(ctx, text, len, at<uint8_t>(base, o_text))) return rc;
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
-    if (n_keys) {
-      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_names, names, names_len, hipMemcpyHostToDevice, s));
-      if (vals_len)
-        MAGOT_HIP_TRY(hipMemcpyAsync(base + o_vals, values, vals_len, hipMemcpyHostToDevice, s));
-      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_noff, name_off, (n_keys + 1) * 8,
-                                   hipMemcpyHostToDevice, s));
-      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_voff, val_off, (n_keys + 1) * 8,
-                                   hipMemcpyHostToDevice, s));
-      MAGOT_HIP_TRY(hipMemcpyAsync(base + o_rank, rank, n_keys * 4, hipMemcpyHostToDevice, s));
-    }
-    MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
-    MAGOT_HIP_TRY(launch_rn_table(a, s));
-    MAGOT_HIP_TRY(launch_rn_count(a, p->tmp0, p->tmp0_bytes, s));
+    // between the text's upload and the count: the table's upload, its lookup structure and
+    // the status word's way back, which resident_text_open's synchronisation completes.
+    // a.ix.text is set by then: the values' offset is counted from it.
     unsigned long long status = 0;
-    uint64_t lfs = 0;
-    MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
-    MAGOT_HIP_TRY(hipMemcpyAsync(&lfs, a.lf_pre + a.n_blocks, 8, hipMemcpyDeviceToHost, s));
-    MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_fields, a.pre + a.n_blocks, 8, hipMemcpyDeviceToHost, s));
-    MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    MAGOT_HIP_TRY(hipEventElapsedTime(&p->upload_ms, ctx->ev0, ctx->ev1));
+    auto table = [&](char* base) -> int {
+      a.val_base = (uint64_t)(base + o_vals - reinterpret_cast<const char*>(a.ix.text));
+      a.names = at<const uint8_t>(base, o_names);
+      a.name_off = at<const uint64_t>(base, o_noff);
+      a.val_off = at<const uint64_t>(base, o_voff);
+      a.rank = at<const uint32_t>(base, o_rank);
+      a.key_hash = at<uint64_t>(base, o_hash);
+      a.claim = at<uint32_t>(base, o_claim);
+      a.slots = at<RnSlot>(base, o_slots);
+      a.status = at<unsigned long long>(base, o_status);
+      if (n_keys) {
+        MAGOT_HIP_TRY(hipMemcpyAsync(base + o_names, names, names_len, hipMemcpyHostToDevice, s));
+        if (vals_len)
+          MAGOT_HIP_TRY(hipMemcpyAsync(base + o_vals, values, vals_len, hipMemcpyHostToDevice, s));
+        MAGOT_HIP_TRY(hipMemcpyAsync(base + o_noff, name_off, (n_keys + 1) * 8,
+                                     hipMemcpyHostToDevice, s));
+        MAGOT_HIP_TRY(hipMemcpyAsync(base + o_voff, val_off, (n_keys + 1) * 8,
+                                     hipMemcpyHostToDevice, s));
+        MAGOT_HIP_TRY(hipMemcpyAsync(base + o_rank, rank, n_keys * 4, hipMemcpyHostToDevice, s));
+      }
+      MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
+      MAGOT_HIP_TRY(launch_rn_table(a, s));
+      MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
+      return MAGOT_OK;
+    };
+    if (int rc = resident_text_open(ctx, text, len, delim, '\n', cv.used, table, &p->rt, &a.ix))
+      return rc;
     if (status != ~0ull) return rn_decline(reason, (uint32_t)status);
+    a.n_fields = p->rt.total;
     if (a.n_fields > len) {
       set_error("magot_rename_parse: more delimiters than bytes");
       return MAGOT_ERR_STATE;
     }
-    p->n_lines = lfs + (len && text[len - 1] != '\n' ? 1 : 0);
   }
   {
     const uint64_t F = a.n_fields;
-    p->tmp_bytes = rn_tmp_bytes(F + 2);  // the hits are at most the fields
+    p->tmp_bytes = exclusive_sum_bytes<uint64_t>(F + 2);  // the hits are at most the fields
     Carve cv;
     const uint64_t o_pos = cv.take<uint64_t>(F + 1);
     const uint64_t o_hit = cv.take<uint64_t>(F + 1), o_hpos = cv.take<uint64_t>(F + 1);
@@ -249,12 +220,12 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
     if (cv.used > free_b / 2) return rn_decline(reason, MAGOT_RENAME_TOO_LARGE);
     MAGOT_HIP_TRY(hipMalloc(&p->field_mem, cv.used + 256));
     char* base = static_cast<char*>(p->field_mem);
-    a.d_pos = at<uint64_t>(base, o_pos);
+    a.ix.pos = at<uint64_t>(base, o_pos);
     a.f_hit = at<uint64_t>(base, o_hit);
     a.f_hpos = at<uint64_t>(base, o_hpos);
     a.f_key = at<uint32_t>(base, o_key);
     p->tmp = base + o_tmp;
-    MAGOT_HIP_TRY(launch_rn_fill(a, s));
+    MAGOT_HIP_TRY(launch_text_fill(a.ix, kTextFillPlain, s));
     MAGOT_HIP_TRY(launch_rn_match(a, p->tmp, p->tmp_bytes, s));
     MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_hits, a.f_hpos + F, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
@@ -303,14 +274,14 @@ int magot_rename_sizes(const magot_rename* p, uint64_t* n_lines, uint64_t* n_fie
     set_error("magot_rename_sizes: null handle");
     return MAGOT_ERR_ARG;
   }
-  if (n_lines) *n_lines = p->n_lines;
+  if (n_lines) *n_lines = p->rt.n_lines;
   if (n_fields) *n_fields = p->a.n_fields;
   if (n_hits) *n_hits = p->a.n_hits;
   if (out_bytes) *out_bytes = p->r.out_bytes;
   return MAGOT_OK;
 }
 
-double magot_rename_upload_ms(const magot_rename* p) { return p ? (double)p->upload_ms : 0.0; }
+double magot_rename_upload_ms(const magot_rename* p) { return p ? (double)p->rt.upload_ms : 0.0; }
 
 int magot_rename_hits(magot_ctx* ctx, magot_rename* p, uint64_t* end, uint32_t* key) {
   if (int rc = handle_of(ctx, p, "magot_rename_hits", "handle")) return rc;
@@ -358,12 +329,12 @@ int magot_rename_time(magot_ctx* ctx, magot_rename* p, int iters, double* ms6,
     set_error("magot_rename_time: bad argument");
     return MAGOT_ERR_ARG;
   }
-  if (text_bytes) *text_bytes = p->a.n;
+  if (text_bytes) *text_bytes = p->a.ix.n;
   if (out_bytes) *out_bytes = p->r.out_bytes;
   for (int k = 0; k < kRnPasses; ++k) ms6[k] = 0;
-  if (!p->a.n) return MAGOT_OK;  // an empty text: nothing to time
+  if (!p->a.ix.n) return MAGOT_OK;  // an empty text: nothing to time
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.n + 256));
+  if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.ix.n + 256));
   if (int rc = rn_plan_render(p)) return rc;
   // every pass writes what it wrote in magot_rename_parse: the answers stand
   double total[kRnPasses] = {0, 0, 0, 0, 0, 0};

@@ -1,6 +1,6 @@
 // C ABI: heterozygosity_from_vcf's parse, sort and counting on the device
-// (vcf.hip; magot_variants.py:16-139).  The text is made resident and indexed
-// as a PSL's (upload_text, psl.hip's line index).  The renderer is in
+// (vcf.hip; magot_variants.py:16-139).  The text is made resident and its lines
+// indexed by resident_text_open and textindex.hip.  The renderer is in
 // vcfhost.cpp.
 #include "abi_internal.h"
 
@@ -8,20 +8,19 @@ using namespace magot;
 
 struct magot_vcf {
   magot_ctx* ctx = nullptr;
-  void* text_mem = nullptr;  // the text, the block counts and their scan's scratch
+  ResidentText rt;           // the text and its line index; the status words and last_line
   void* mem = nullptr;       // everything sized by the lines
   void* data_mem = nullptr;  // everything sized by the data lines
   void* loci_mem = nullptr;  // the last magot_vcf_count's tables
   void* copy_mem = nullptr;  // magot_vcf_time's copy target
-  PslArgs ix{};              // the line index
+  TextIndexArgs ix{};        // the line index
   VcfArgs a{};
   VcfCountArgs c{};
-  void *tmp0 = nullptr, *tmp = nullptr, *ctmp = nullptr;
-  size_t tmp0_bytes = 0, tmp_bytes = 0, ctmp_bytes = 0;
+  void *tmp = nullptr, *ctmp = nullptr;
+  size_t tmp_bytes = 0, ctmp_bytes = 0;
   uint32_t* last_line = nullptr;
   uint64_t head_off = 0, head_len = 0;
   bool resolved = false;
-  float upload_ms = 0.f;
 };
 
 namespace {
@@ -45,7 +44,7 @@ int vcf_fetch(T* dst, const T* src, uint64_t n) {
 int vcf_line_span(const magot_vcf* p, const char* host_text, uint64_t k, uint64_t* off,
                   uint64_t* len) {
   uint64_t se[2] = {0, 0};
-  MAGOT_HIP_TRY(hipMemcpy(se, p->ix.line_start + k, sizeof se, hipMemcpyDeviceToHost));
+  MAGOT_HIP_TRY(hipMemcpy(se, p->a.line_start + k, sizeof se, hipMemcpyDeviceToHost));
   uint8_t last = 0;
   if (host_text) last = (uint8_t)host_text[se[1] - 1];
   else MAGOT_HIP_TRY(hipMemcpy(&last, p->a.text + se[1] - 1, 1, hipMemcpyDeviceToHost));
@@ -57,9 +56,7 @@ int vcf_line_span(const magot_vcf* p, const char* host_text, uint64_t k, uint64_
 hipError_t vcf_pass(const magot_vcf* p, int k, hipStream_t s) {
   const VcfArgs& a = p->a;
   switch (k) {
-    case 0:
-      if (hipError_t e = launch_psl_count(p->ix, p->tmp0, p->tmp0_bytes, s)) return e;
-      return launch_psl_fill(p->ix, s);
+    case 0: return text_index_pass(p->ix, p->rt, kTextFillLines, s);
     case 1:
       if (hipError_t e = launch_vcf_classify(a, p->tmp, p->tmp_bytes, s)) return e;
       return launch_vcf_compact(a, s);
@@ -84,7 +81,7 @@ extern "C" {
 void magot_vcf_destroy(magot_vcf* p) {
   if (!p) return;
   if (p->ctx) (void)hipSetDevice(p->ctx->device);
-  for (void* m : {p->copy_mem, p->loci_mem, p->data_mem, p->mem, p->text_mem})
+  for (void* m : {p->copy_mem, p->loci_mem, p->data_mem, p->mem, p->rt.mem})
     if (m) (void)hipFree(m);
   delete p;
 }
@@ -110,11 +107,7 @@ int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max
   if (line) *line = 0;
   if (!max_samples || max_samples > kVcfMaxSamples) max_samples = kVcfMaxSamples;
   if (!max_runs || max_runs > kVcfMaxRuns) max_runs = kVcfMaxRuns;
-  if (!max_bytes) {  // the bit rows and the line tables beside the text
-    size_t free_b = 0, total_b = 0;
-    MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    max_bytes = free_b / 4;
-  }
+  if (int rc = resident_text_budget(&max_bytes)) return rc;
   if (len > max_bytes) return vcf_decline(reason, line, MAGOT_VCF_TOO_LARGE, 0);
   if (!len) return vcf_decline(reason, line, MAGOT_VCF_NO_HEADER, 0);
 
@@ -124,38 +117,20 @@ int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max
   } guard{new magot_vcf()};
   magot_vcf* p = guard.p;
   p->ctx = ctx;
-  PslArgs& ix = p->ix;
+  TextIndexArgs& ix = p->ix;
   VcfArgs& a = p->a;
   hipStream_t s = ctx->stream;
-  ix.n = a.n = len;
-  ix.n_blocks = depth_text_blocks(len);
-  ix.hash_bits = 64;
   {
-    p->tmp0_bytes = psl_count_tmp_bytes(ix.n_blocks);
-    Carve cv;
-    const uint64_t o_text = cv.take<uint8_t>(len + 32);  // a 16-byte load at the last byte
-    const uint64_t o_blk = cv.take<uint64_t>(ix.n_blocks + 1);
-    const uint64_t o_pre = cv.take<uint64_t>(ix.n_blocks + 1);
-    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp0_bytes);
+    Carve cv;  // the caller's slices: eight status words and last_line
     const uint64_t o_status = cv.take<unsigned long long>(8);
     const uint64_t o_last = cv.take<uint32_t>(1);
-    MAGOT_HIP_TRY(hipMalloc(&p->text_mem, cv.used + 256));
-    char* base = static_cast<char*>(p->text_mem);
-    ix.text = a.text = reinterpret_cast<const uint8_t*>(base + o_text);
-    ix.blk = reinterpret_cast<uint64_t*>(base + o_blk);
-    ix.pre = reinterpret_cast<uint64_t*>(base + o_pre);
-    p->tmp0 = base + o_tmp;
-    a.status = reinterpret_cast<unsigned long long*>(base + o_status);
-    p->last_line = reinterpret_cast<uint32_t*>(base + o_last);
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
-    if (int rc = upload_text(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
-    MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
-    MAGOT_HIP_TRY(launch_psl_count(ix, p->tmp0, p->tmp0_bytes, s));
-    uint64_t lfs = 0;
-    MAGOT_HIP_TRY(hipMemcpyAsync(&lfs, ix.pre + ix.n_blocks, 8, hipMemcpyDeviceToHost, s));
-    MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    MAGOT_HIP_TRY(hipEventElapsedTime(&p->upload_ms, ctx->ev0, ctx->ev1));
-    ix.n_lines = lfs + (text[len - 1] != '\n' ? 1 : 0);
+    if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte, cv.used, &p->rt, &ix))
+      return rc;
+    a.text = ix.text;
+    a.n = len;
+    a.status = reinterpret_cast<unsigned long long*>(p->rt.extra + o_status);
+    p->last_line = reinterpret_cast<uint32_t*>(p->rt.extra + o_last);
+    ix.n_lines = p->rt.n_lines;
     if (ix.n_lines > kPslLineMask) return vcf_decline(reason, line, MAGOT_VCF_TOO_MANY_LINES, 0);
   }
   const uint64_t L = a.n_lines = ix.n_lines;  // at least 1
@@ -168,13 +143,12 @@ int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max
     const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
     MAGOT_HIP_TRY(hipMalloc(&p->mem, cv.used + 256));
     char* base = static_cast<char*>(p->mem);
-    ix.line_start = reinterpret_cast<uint64_t*>(base + o_start);
-    a.line_start = ix.line_start;
+    a.line_start = ix.pos = reinterpret_cast<uint64_t*>(base + o_start);
     a.kind = reinterpret_cast<uint64_t*>(base + o_kind);
     a.kpos = reinterpret_cast<uint64_t*>(base + o_kpos);
     p->tmp = base + o_tmp;
   }
-  MAGOT_HIP_TRY(launch_psl_fill(ix, s));
+  MAGOT_HIP_TRY(launch_text_fill(ix, kTextFillLines, s));
   MAGOT_HIP_TRY(launch_vcf_classify(a, p->tmp, p->tmp_bytes, s));
   unsigned long long st[5] = {0, 0, 0, 0, 0};
   uint64_t totals = 0;
@@ -271,7 +245,7 @@ int magot_vcf_sizes(const magot_vcf* p, uint64_t* n_lines, uint64_t* n_data, uin
   return MAGOT_OK;
 }
 
-double magot_vcf_upload_ms(const magot_vcf* p) { return p ? (double)p->upload_ms : 0.0; }
+double magot_vcf_upload_ms(const magot_vcf* p) { return p ? (double)p->rt.upload_ms : 0.0; }
 
 int magot_vcf_header_lines(magot_ctx* ctx, magot_vcf* p, uint64_t* off, uint64_t* len) {
   if (int rc = handle_of(ctx, p, "magot_vcf_header_lines", "handle")) return rc;

@@ -10,6 +10,7 @@
 
 #include "../../include/magot.h"
 #include "hostutil.h"
+#include "textindex.h"
 
 namespace magot {
 
@@ -673,9 +674,7 @@ hipError_t launch_track_count(const magot_mask_interval* rows, uint64_t n_rows,
 // 256 depths = 1 KiB: a prefix reads one directory entry and at most 64
 // 16-byte loads of one block; the directory adds 1/128 to the arena.
 constexpr int kDepthBlock = 256;
-constexpr int kTextBlock = 4096;  // text bytes per workgroup of the line index and the parse
 constexpr uint64_t depth_blocks(uint64_t n_lines) { return (n_lines + kDepthBlock - 1) / kDepthBlock; }
-constexpr uint64_t depth_text_blocks(uint64_t n) { return (n + kTextBlock - 1) / kTextBlock; }
 // what links a chunk to the next: the lines so far, and the last line's name
 // and position
 struct DepthCarry {
@@ -844,14 +843,8 @@ struct PslAgg {  // per key: the best rank, and the rank's low bits of its first
   uint64_t best, first;
 };
 struct PslArgs {
-  const uint8_t* text;  // n bytes, 16-byte aligned, readable to the next multiple of 16
-  uint64_t n;
-  uint64_t n_blocks;    // depth_text_blocks(n)
-  uint64_t* blk;        // n_blocks + 1: LFs per text block, the last entry 0
-  uint64_t* pre;        // their exclusive scan; pre[n_blocks]: the LFs of the text
-  // per line, n_lines of each (line_start: n_lines + 1, the last entry n)
-  uint64_t n_lines;
-  uint64_t* line_start;
+  TextIndexArgs ix;     // the text and its line index: ix.pos[k] is where line k starts
+  // per line, ix.n_lines of each
   uint64_t* hash;       // CPython 2.7's hash of the key (data lines)
   uint64_t* key_off;
   uint32_t* key_len;
@@ -875,12 +868,9 @@ struct PslArgs {
   int64_t* g_score;
   uint32_t *g_first, *g_best;
 };
-// rocprim scratch: of the block scan, and of every later pass over a text of
-// n_lines lines (n_data and n_groups are at most n_lines)
-size_t psl_count_tmp_bytes(uint64_t n_blocks);
+// rocprim scratch of every pass over a text of n_lines lines (n_data and n_groups
+// are at most n_lines)
 size_t psl_tmp_bytes(uint64_t n_lines);
-hipError_t launch_psl_count(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
-hipError_t launch_psl_fill(const PslArgs& a, hipStream_t s);
 hipError_t launch_psl_parse(const PslArgs& a, hipStream_t s);
 hipError_t launch_psl_compact(const PslArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_psl_scatter(const PslArgs& a, hipStream_t s);
@@ -920,7 +910,7 @@ hipError_t launch_site_count(const SiteArgs& a, hipStream_t s);
 // ---------------------------------------------------------------------------
 // heterozygosity_from_vcf (vcf.hip; magot_variants.py:16-139; magot_vcf_*)
 // ---------------------------------------------------------------------------
-// The text is resident and indexed by psl.hip's line index.  Data lines are
+// The text is resident and indexed by textindex.hip's line index.  Data lines are
 // compacted, parsed a wave each into (POS, key hash, CHROM run head, one het bit
 // per sample column), keyed (contig << 32 | POS) once the host has named the
 // runs' contigs, and sorted; a locus is a range of the sorted keys.
@@ -934,7 +924,7 @@ struct VcfArgs {
   uint64_t n;
   uint64_t n_lines;
   uint32_t final_lf;             // 1: the text's last byte is LF (every line has one)
-  const uint64_t* line_start;  // n_lines + 1 (PslArgs::line_start)
+  const uint64_t* line_start;  // n_lines + 1 (TextIndexArgs::pos, line mode)
   // per line: 1 for a data line, 1 << 32 for a "##" line; n_lines + 1, the last 0
   uint64_t* kind;
   uint64_t* kpos;  // their exclusive scan: both counts before each line, the totals last
@@ -1003,15 +993,11 @@ constexpr uint64_t kFaMaxLines = (1ull << 31) - 1;
 constexpr int kFaGroup = 16;           // pieces per wave of the reflow's copy
 static_assert((kFaPiece & (kFaPiece - 1)) == 0, "a power of two");
 struct FaArgs {
-  const uint8_t* text;  // n bytes, 16-byte aligned, readable to the next multiple of 16 and 16 more
-  uint64_t n;
-  uint64_t n_blocks;    // depth_text_blocks(n)
-  uint64_t* blk;        // n_blocks + 1: LFs per text block, the last entry 0
-  uint64_t* pre;        // their exclusive scan; pre[n_blocks]: the LFs of the text
+  // the text (readable to the next multiple of 16 and 16 more) and its line index:
+  // ix.pos[k] is where line k starts
+  TextIndexArgs ix;
   unsigned long long* status;  // min of (line << 8 | MAGOT_FASTAREC_* reason); ~0 when clean
-  // per line, n_lines + 1 of each (the last entry of the first four 0, of the scans the total)
-  uint64_t n_lines;
-  uint64_t* line_start;  // the last entry n
+  // per line, ix.n_lines + 1 of each (the last entry of the first three 0, of the scans the total)
   uint64_t *hdr, *pay, *pcs;              // 1 for a header; payload bytes; pieces of kFaPiece
   uint64_t *rec_of, *pay_pre, *pcs_pre;   // their exclusive scans
   // per record (header line), n_rec of each where nothing else is said
@@ -1054,10 +1040,7 @@ struct FaRenderArgs {
   uint32_t* p_len;
   uint8_t* out;  // obase[n_out] bytes, 16-byte aligned
 };
-size_t fa_count_tmp_bytes(uint64_t n_blocks);
 size_t fa_tmp_bytes(uint64_t n);  // of every pass over at most n lines, records, names or pieces
-hipError_t launch_fa_count(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
-hipError_t launch_fa_fill(const FaArgs& a, hipStream_t s);
 hipError_t launch_fa_lines(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_fa_names(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_fa_sort(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
@@ -1088,10 +1071,10 @@ struct alignas(16) RnSlot {  // of the open-addressing table; 16 bytes, one load
   uint32_t len;
 };
 struct RnArgs {
-  const uint8_t* text;  // n bytes, 16-byte aligned, readable to the next multiple of 16 and 16 more
-  uint64_t n;
-  uint64_t n_blocks;    // depth_text_blocks(n)
-  uint32_t delim;
+  // the text (readable to the next multiple of 16 and 16 more) and the index of
+  // its ds: ix.byte is d, ix.pos[j] the offset of field end j; the LFs are
+  // counted beside them
+  TextIndexArgs ix;
   uint32_t hash_bits;
   // the table: n_keys distinct names, each of 1..kRnMaxName bytes without d
   uint64_t n_keys;
@@ -1107,11 +1090,8 @@ struct RnArgs {
   uint32_t max_len;      // the longest name
   uint64_t len_mask[kRnMaxName / 64];  // bit l - 1: a name of l bytes exists
   unsigned long long* status;  // min of the MAGOT_RENAME_* reasons met, ~0 when clean
-  uint64_t *blk, *pre;   // n_blocks + 1: ds per text block, the last entry 0; the exclusive scan
-  uint64_t *lf_blk, *lf_pre;  // the same of the LFs: lf_pre[n_blocks] is the text's
   // per field end (a d of the text), n_fields of each where nothing else is said
   uint64_t n_fields;
-  uint64_t* d_pos;
   uint32_t* f_key;            // the key that rewrites the field, kRnNoKey
   uint64_t *f_hit, *f_hpos;   // n_fields + 1: 1 where there is one, the last entry 0; the scan
   // per hit in text order
@@ -1129,10 +1109,7 @@ struct RnRenderArgs {
   uint8_t* out;       // out_bytes, 16-byte aligned
   uint64_t out_bytes;  // n + h_dsum[n_hits]
 };
-size_t rn_tmp_bytes(uint64_t n);  // of every scan over at most n entries
 hipError_t launch_rn_table(const RnArgs& a, hipStream_t s);
-hipError_t launch_rn_count(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
-hipError_t launch_rn_fill(const RnArgs& a, hipStream_t s);
 hipError_t launch_rn_match(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_rn_layout(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_rn_render(const RnArgs& a, const RnRenderArgs& r, hipStream_t s);

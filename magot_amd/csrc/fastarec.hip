@@ -4,13 +4,11 @@
 // list of names, and the text reflowed into one line per record.  A header line
 // is short; a sequence line may be a whole chromosome, so no pass walks one.
 //
-//   count_kernel    psl.hip's: the LFs per text block of kTextBlock bytes, then one
-//                   rocprim exclusive scan; the total gives n_lines on the host.
-//   fill_kernel     psl.hip's, from the same 16-byte load: LF number j at byte p
-//                   gives line_start[j + 1] = p + 1.  The load's CRs are looked at
-//                   too: a CR that is neither before an LF nor the text's last
-//                   byte atomic-mins (line, stray_cr) into the status word.  A CR
-//                   in a lane's last byte reads the one byte after it.
+//   the line index  textindex.hip's count and fill over the LFs, line mode with the
+//                   stray-CR check: the total gives n_lines on the host, ix.pos[k]
+//                   is where line k starts, and a CR that is neither before an LF
+//                   nor the text's last byte atomic-mins (line, stray_cr) into the
+//                   status word.
 //   lines_kernel    one lane per line, O(1) bytes: the first byte (header or not),
 //                   the byte before the LF (a CR or not).  payload = the line less
 //                   its LF and that CR, 0 for a header; pieces = ceil(payload /
@@ -45,13 +43,14 @@
 //                   per piece: two binary searches name its record and its line,
 //                   the payload scan its destination; the lane of a name piece
 //                   also stores the record's literal bytes ('>', TAB, LF).
-//                   copy_kernel: one wave per kFaGroup pieces, wavecopy.h's deal of
-//                   lanes over the group's whole 16-byte chunks (a funnel-shifted
-//                   pair of aligned loads, one vector store) and then over its
-//                   remaining bytes.  Every output byte is written exactly once.
+//                   wavecopy.h's launch_piece_copy: one wave per kFaGroup pieces,
+//                   its lanes dealt over the group's whole 16-byte chunks (a
+//                   funnel-shifted pair of aligned loads, one vector store) and
+//                   then over its remaining bytes.  Every output byte is written
+//                   exactly once.
 //
-// No LDS beyond the wave totals of the two index kernels and the copy's piece
-// table, no spin-wait, no compare-and-swap loop; nothing is float.
+// No LDS beyond the copy's piece table, no spin-wait, no compare-and-swap loop;
+// nothing is float.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -65,79 +64,8 @@ namespace magot {
 namespace {
 
 constexpr int kFaThreads = 256;
-constexpr int kFaLane = 16;
-constexpr int kFaWaves = kFaThreads / 64;
-static_assert(kTextBlock == kFaThreads * kFaLane, "one 16-byte load per lane");
-static_assert(kFaGroup <= kSpanGroup, "count_le searches kSpanGroup entries");
 
 inline unsigned fa_blocks_for(uint64_t n) { return (unsigned)((n + kFaThreads - 1) / kFaThreads); }
-
-// bit j of *lf, of *cr: byte i + j of the text is LF, is CR (i the lane's first byte)
-__device__ __forceinline__ void fa_lane_masks(const uint8_t* __restrict__ text, uint64_t i,
-                                              uint64_t n, uint32_t* lf, uint32_t* cr) {
-  *lf = *cr = 0;
-  if (i >= n) return;
-  const uint4 v = *reinterpret_cast<const uint4*>(text + i);  // readable to the next 16
-  const uint32_t keep = n - i < kFaLane ? (1u << (n - i)) - 1 : 0xffffu;  // behind the text: anything
-  *lf = byte_eq_mask16(v, 0x0A0A0A0Au) & keep;
-  *cr = byte_eq_mask16(v, 0x0D0D0D0Du) & keep;
-}
-
-__global__ __launch_bounds__(kFaThreads) void fa_count_kernel(FaArgs a) {
-  __shared__ uint32_t wave_count[kFaWaves];
-  const int t = threadIdx.x;
-  uint32_t c = 0;
-  if (blockIdx.x < a.n_blocks) {  // block n_blocks is the sentinel: its prefix is the total
-    uint32_t lf, cr;
-    fa_lane_masks(a.text, (uint64_t)blockIdx.x * kTextBlock + kFaLane * t, a.n, &lf, &cr);
-    c = __popc(lf);
-  }
-  for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
-  if ((t & 63) == 0) wave_count[t >> 6] = c;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t sum = 0;
-    for (int w = 0; w < kFaWaves; ++w) sum += wave_count[w];
-    a.blk[blockIdx.x] = sum;
-  }
-}
-
-__global__ __launch_bounds__(kFaThreads) void fa_fill_kernel(FaArgs a) {
-  __shared__ uint32_t wave_count[kFaWaves];
-  const int t = threadIdx.x;
-  const uint32_t lane = t & 63, wave = t >> 6;
-  const uint64_t p0 = (uint64_t)blockIdx.x * kTextBlock + kFaLane * t;
-  uint32_t lf, cr;
-  fa_lane_masks(a.text, p0, a.n, &lf, &cr);
-  const uint32_t c = __popc(lf);
-  uint32_t inc = c;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(inc, d, 64);
-    if ((int)lane >= d) inc += up;
-  }
-  if (lane == 63) wave_count[wave] = inc;
-  __syncthreads();
-  if (lf | cr) {  // p0 < n
-    // the LFs before this lane's bytes: below the text's LFs, and those are at most n_lines
-    uint64_t j = a.pre[blockIdx.x] + (inc - c);
-    for (uint32_t w = 0; w < wave; ++w) j += wave_count[w];
-    if (cr) {
-      uint32_t ok = lf >> 1;                                  // the next byte is LF
-      if (a.n - p0 <= kFaLane) ok |= 1u << (a.n - 1 - p0);     // the text's last byte
-      else if ((cr >> 15) && a.text[p0 + kFaLane] == '\n') ok |= 1u << 15;  // p0 + 16 < n
-      const uint32_t stray = cr & ~ok;
-      if (stray) {  // the lane's first one is on its lowest line
-        const uint64_t line = j + __popc(lf & ((1u << (__ffs(stray) - 1)) - 1));
-        atomicMin(a.status, (unsigned long long)(line << 8 | MAGOT_FASTAREC_STRAY_CR));
-      }
-    }
-    for (uint32_t m = lf; m; m &= m - 1, ++j) a.line_start[j + 1] = p0 + __ffs(m);
-  }
-  if (blockIdx.x == 0 && t == 0) {
-    a.line_start[0] = 0;
-    a.line_start[a.n_lines] = a.n;  // a last line without LF ends with the text
-  }
-}
 
 // the end of line k's bytes, its LF and a CR before it left out (start < end)
 __device__ __forceinline__ uint64_t fa_line_end(const uint8_t* __restrict__ text, uint64_t start,
@@ -149,12 +77,12 @@ __device__ __forceinline__ uint64_t fa_line_end(const uint8_t* __restrict__ text
 
 __global__ __launch_bounds__(kFaThreads) void fa_lines_kernel(FaArgs a) {
   const uint64_t k = (uint64_t)blockIdx.x * kFaThreads + threadIdx.x;
-  if (k > a.n_lines) return;
+  if (k > a.ix.n_lines) return;
   uint64_t hdr = 0, pay = 0;
-  if (k < a.n_lines) {
-    const uint64_t start = a.line_start[k], end = a.line_start[k + 1];  // start < end <= n
-    hdr = a.text[start] == '>' ? 1 : 0;
-    if (!hdr) pay = fa_line_end(a.text, start, end) - start;
+  if (k < a.ix.n_lines) {
+    const uint64_t start = a.ix.pos[k], end = a.ix.pos[k + 1];  // start < end <= n
+    hdr = a.ix.text[start] == '>' ? 1 : 0;
+    if (!hdr) pay = fa_line_end(a.ix.text, start, end) - start;
   }
   a.hdr[k] = hdr;
   a.pay[k] = pay;
@@ -163,23 +91,12 @@ __global__ __launch_bounds__(kFaThreads) void fa_lines_kernel(FaArgs a) {
 
 __global__ __launch_bounds__(kFaThreads) void fa_heads_kernel(FaArgs a) {
   const uint64_t k = (uint64_t)blockIdx.x * kFaThreads + threadIdx.x;
-  if (k > a.n_lines) return;
-  if (k == a.n_lines) a.hdr_line[a.n_rec] = (uint32_t)k;
+  if (k > a.ix.n_lines) return;
+  if (k == a.ix.n_lines) a.hdr_line[a.n_rec] = (uint32_t)k;
   else if (a.hdr[k]) a.hdr_line[a.rec_of[k]] = (uint32_t)k;  // rec_of[k] < n_rec: a header's own
 }
 
 __device__ __forceinline__ bool fa_py2_space(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13); }
-
-// CPython 2.7's string hash, a byte at a time: begin with the first byte, end with the length
-__device__ __forceinline__ void fa_hash_byte(uint64_t& h, uint32_t len_so_far, uint32_t c) {
-  if (!len_so_far) h = (uint64_t)c << 7;
-  h = (h * 1000003ull) ^ c;
-}
-__device__ __forceinline__ uint64_t fa_hash_end(uint64_t h, uint32_t len) {
-  if (!len) return 0;
-  h ^= len;
-  return h == ~0ull ? ~0ull - 1 : h;
-}
 
 __global__ __launch_bounds__(kFaThreads) void fa_names_kernel(FaArgs a) {
   const uint64_t r = (uint64_t)blockIdx.x * kFaThreads + threadIdx.x;
@@ -189,17 +106,17 @@ __global__ __launch_bounds__(kFaThreads) void fa_names_kernel(FaArgs a) {
     return;
   }
   const uint64_t k = a.hdr_line[r];  // below n_lines
-  const uint64_t start = a.line_start[k];
+  const uint64_t start = a.ix.pos[k];
   const uint64_t off = start + 1;    // behind the '>'
-  const uint64_t full = fa_line_end(a.text, start, a.line_start[k + 1]) - off;
+  const uint64_t full = fa_line_end(a.ix.text, start, a.ix.pos[k + 1]) - off;
   if (full > kFaMaxName)
     atomicMin(a.status, (unsigned long long)(k << 8 | MAGOT_FASTAREC_LONG_NAME));
   const uint32_t len = (uint32_t)(full > kFaMaxName ? kFaMaxName : full);
   uint64_t h = 0, wh = 0, woff = off;
   uint32_t wlen = 0, state = 0;  // 0: before the first word, 1: in it, 2: behind it
   for (uint32_t i = 0; i < len; ++i) {
-    const uint32_t c = a.text[off + i];
-    fa_hash_byte(h, i, c);
+    const uint32_t c = a.ix.text[off + i];
+    h = py27_hash_step(h, i, c);
     const bool ws = fa_py2_space(c);
     if (state == 0 && !ws) {
       state = 1;
@@ -207,16 +124,16 @@ __global__ __launch_bounds__(kFaThreads) void fa_names_kernel(FaArgs a) {
     }
     if (state == 1) {
       if (ws) state = 2;
-      else fa_hash_byte(wh, wlen++, c);
+      else wh = py27_hash_step(wh, wlen++, c);
     }
   }
   const uint64_t seq = a.pay_pre[a.hdr_line[r + 1]] - a.pay_pre[k];
   a.name_off[r] = off;
   a.name_len[r] = len;
-  a.hash[r] = fa_hash_end(h, len);
+  a.hash[r] = py27_hash_end(h, len);
   a.word_off[r] = woff;
   a.word_len[r] = wlen;
-  a.word_hash[r] = fa_hash_end(wh, wlen);
+  a.word_hash[r] = py27_hash_end(wh, wlen);
   a.no_word[r] = state == 0 ? 1u : 0u;
   a.seq_len[r] = seq;
   a.ne[r] = seq ? 1 : 0;
@@ -249,7 +166,7 @@ __global__ __launch_bounds__(kFaThreads) void fa_runs_kernel(FaArgs a) {
   if (head) return;
   const uint32_t ra = a.sval_sorted[i], rb = a.sval_sorted[i - 1];  // records, below n_rec
   // a name's span ends inside its line, and its length is at most kFaMaxName
-  if (!fa_same(a.text + a.name_off[ra], a.name_len[ra], a.text + a.name_off[rb], a.name_len[rb]))
+  if (!fa_same(a.ix.text + a.name_off[ra], a.name_len[ra], a.ix.text + a.name_off[rb], a.name_len[rb]))
     atomicMin(a.status,
               (unsigned long long)((uint64_t)a.hdr_line[ra] << 8 | MAGOT_FASTAREC_HASH_COLLISION));
 }
@@ -279,8 +196,8 @@ __global__ __launch_bounds__(kFaThreads) void fa_list_kernel(FaArgs a, FaMemberA
   const uint64_t s = m.off[j], full = m.off[j + 1] - s;  // the host checked the offsets
   const uint32_t len = (uint32_t)(full > kFaMaxName ? kFaMaxName : full);
   uint64_t h = 0;
-  for (uint32_t i = 0; i < len; ++i) fa_hash_byte(h, i, m.blob[s + i]);
-  m.lkey[j] = fa_hash_end(h, len) & fa_mask(a.hash_bits);
+  for (uint32_t i = 0; i < len; ++i) h = py27_hash_step(h, i, m.blob[s + i]);
+  m.lkey[j] = py27_hash_end(h, len) & fa_mask(a.hash_bits);
   m.lidx[j] = (uint32_t)j;
 }
 
@@ -301,7 +218,7 @@ __global__ __launch_bounds__(kFaThreads) void fa_member_kernel(FaArgs a, FaMembe
   // an equal hash with other bytes is no match: the run is walked to its end
   for (uint64_t i = lo; i < m.m && m.lkey_sorted[i] == key && !found; ++i) {
     const uint64_t s = m.off[m.lidx_sorted[i]];
-    found = fa_same(a.text + off, len, m.blob + s, m.off[m.lidx_sorted[i] + 1] - s);
+    found = fa_same(a.ix.text + off, len, m.blob + s, m.off[m.lidx_sorted[i] + 1] - s);
   }
   m.keep[q] = found ? 0 : 1;
 }
@@ -356,24 +273,9 @@ __global__ __launch_bounds__(kFaThreads) void fa_piece_kernel(FaArgs a, FaRender
   const uint64_t k = fa_last_le(a.pcs_pre, k0, a.hdr_line[r + 1], g);
   const uint64_t in_line = (g - a.pcs_pre[k]) * kFaPiece;  // below pay[k]
   const uint64_t left = a.pay[k] - in_line;
-  o.p_src[t] = a.line_start[k] + in_line;
+  o.p_src[t] = a.ix.pos[k] + in_line;
   o.p_dst[t] = at + lead + name_len + 1 + (a.pay_pre[k] - a.pay_pre[k0]) + in_line;
   o.p_len[t] = (uint32_t)(left < kFaPiece ? left : kFaPiece);
-}
-
-__global__ __launch_bounds__(kFaThreads) void fa_copy_kernel(FaArgs a, FaRenderArgs o) {
-  __shared__ PieceGroup groups[kFaWaves];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t t0 = ((uint64_t)blockIdx.x * kFaWaves + wave) * kFaGroup;
-  if (t0 >= o.n_pieces) return;  // the whole wave
-  const uint32_t m = (uint32_t)(o.n_pieces - t0 < kFaGroup ? o.n_pieces - t0 : kFaGroup);
-  piece_group_copy(groups[wave], m, o.p_src + t0, o.p_dst + t0, o.p_len + t0, a.text, o.out, lane);
-}
-
-hipError_t fa_sum_scan(void* tmp, size_t& tmp_bytes, const uint64_t* in, uint64_t* out, uint64_t n,
-                       hipStream_t s) {
-  return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, uint64_t(0), (size_t)n,
-                                 rocprim::plus<uint64_t>(), s);
 }
 
 hipError_t fa_pair_sort(void* tmp, size_t& tmp_bytes, const uint64_t* k, uint64_t* k2,
@@ -384,47 +286,29 @@ hipError_t fa_pair_sort(void* tmp, size_t& tmp_bytes, const uint64_t* k, uint64_
 
 }  // namespace
 
-size_t fa_count_tmp_bytes(uint64_t n_blocks) {
-  size_t b = 0;
-  (void)fa_sum_scan(nullptr, b, nullptr, nullptr, n_blocks + 1, hipStream_t(0));
-  return b;
-}
-
 size_t fa_tmp_bytes(uint64_t n) {
-  size_t a = 0, b = 0, c = 0;
-  (void)fa_sum_scan(nullptr, a, nullptr, nullptr, n + 1, hipStream_t(0));
+  size_t b = 0, c = 0;
+  const size_t a = exclusive_sum_bytes<uint64_t>(n + 1);
   (void)fa_pair_sort(nullptr, b, nullptr, nullptr, nullptr, nullptr, n, 64, hipStream_t(0));
   (void)rocprim::inclusive_scan(nullptr, c, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                 (size_t)n, rocprim::maximum<uint64_t>(), hipStream_t(0));
   return std::max(a, std::max(b, c));
 }
 
-hipError_t launch_fa_count(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
-  fa_count_kernel<<<(unsigned)a.n_blocks + 1, kFaThreads, 0, s>>>(a);
-  if (hipError_t e = hipGetLastError()) return e;
-  return fa_sum_scan(tmp, tmp_bytes, a.blk, a.pre, a.n_blocks + 1, s);
-}
-
-hipError_t launch_fa_fill(const FaArgs& a, hipStream_t s) {
-  if (!a.n_blocks) return hipSuccess;
-  fa_fill_kernel<<<(unsigned)a.n_blocks, kFaThreads, 0, s>>>(a);
-  return hipGetLastError();
-}
-
 hipError_t launch_fa_lines(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
-  fa_lines_kernel<<<fa_blocks_for(a.n_lines + 1), kFaThreads, 0, s>>>(a);
+  fa_lines_kernel<<<fa_blocks_for(a.ix.n_lines + 1), kFaThreads, 0, s>>>(a);
   if (hipError_t e = hipGetLastError()) return e;
-  if (hipError_t e = fa_sum_scan(tmp, tmp_bytes, a.hdr, a.rec_of, a.n_lines + 1, s)) return e;
-  if (hipError_t e = fa_sum_scan(tmp, tmp_bytes, a.pay, a.pay_pre, a.n_lines + 1, s)) return e;
-  return fa_sum_scan(tmp, tmp_bytes, a.pcs, a.pcs_pre, a.n_lines + 1, s);
+  if (hipError_t e = exclusive_sum(tmp, tmp_bytes, a.hdr, a.rec_of, a.ix.n_lines + 1, s)) return e;
+  if (hipError_t e = exclusive_sum(tmp, tmp_bytes, a.pay, a.pay_pre, a.ix.n_lines + 1, s)) return e;
+  return exclusive_sum(tmp, tmp_bytes, a.pcs, a.pcs_pre, a.ix.n_lines + 1, s);
 }
 
 hipError_t launch_fa_names(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
-  fa_heads_kernel<<<fa_blocks_for(a.n_lines + 1), kFaThreads, 0, s>>>(a);
+  fa_heads_kernel<<<fa_blocks_for(a.ix.n_lines + 1), kFaThreads, 0, s>>>(a);
   if (hipError_t e = hipGetLastError()) return e;
   fa_names_kernel<<<fa_blocks_for(a.n_rec + 1), kFaThreads, 0, s>>>(a);
   if (hipError_t e = hipGetLastError()) return e;
-  return fa_sum_scan(tmp, tmp_bytes, a.ne, a.ne_pos, a.n_rec + 1, s);
+  return exclusive_sum(tmp, tmp_bytes, a.ne, a.ne_pos, a.n_rec + 1, s);
 }
 
 hipError_t launch_fa_sort(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
@@ -446,7 +330,7 @@ hipError_t launch_fa_keys(const FaArgs& a, void* tmp, size_t tmp_bytes, hipStrea
     fa_ends_kernel<<<fa_blocks_for(a.n_ne), kFaThreads, 0, s>>>(a);
     if (hipError_t e = hipGetLastError()) return e;
   }
-  return fa_sum_scan(tmp, tmp_bytes, a.is_first, a.kpos, a.n_rec + 1, s);
+  return exclusive_sum(tmp, tmp_bytes, a.is_first, a.kpos, a.n_rec + 1, s);
 }
 
 hipError_t launch_fa_rows(const FaArgs& a, hipStream_t s) {
@@ -473,17 +357,15 @@ hipError_t launch_fa_render_sizes(const FaArgs& a, const FaRenderArgs& r, void* 
                                   size_t tmp_bytes, hipStream_t s) {
   fa_size_kernel<<<fa_blocks_for(r.n_out + 1), kFaThreads, 0, s>>>(a, r);
   if (hipError_t e = hipGetLastError()) return e;
-  if (hipError_t e = fa_sum_scan(tmp, tmp_bytes, r.olen, r.obase, r.n_out + 1, s)) return e;
-  return fa_sum_scan(tmp, tmp_bytes, r.pcnt, r.pbase, r.n_out + 1, s);
+  if (hipError_t e = exclusive_sum(tmp, tmp_bytes, r.olen, r.obase, r.n_out + 1, s)) return e;
+  return exclusive_sum(tmp, tmp_bytes, r.pcnt, r.pbase, r.n_out + 1, s);
 }
 
 hipError_t launch_fa_render(const FaArgs& a, const FaRenderArgs& r, hipStream_t s) {
   if (!r.n_pieces) return hipSuccess;
   fa_piece_kernel<<<fa_blocks_for(r.n_pieces), kFaThreads, 0, s>>>(a, r);
   if (hipError_t e = hipGetLastError()) return e;
-  const uint64_t waves = (r.n_pieces + kFaGroup - 1) / kFaGroup;
-  fa_copy_kernel<<<(unsigned)((waves + kFaWaves - 1) / kFaWaves), kFaThreads, 0, s>>>(a, r);
-  return hipGetLastError();
+  return launch_piece_copy<kFaGroup>(r.p_src, r.p_dst, r.p_len, r.n_pieces, a.ix.text, r.out, s);
 }
 
 }  // namespace magot

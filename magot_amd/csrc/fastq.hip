@@ -46,21 +46,13 @@ constexpr uint32_t kFqLocal = 4096;  // bins a workgroup counts in LDS
 static_assert(kTextBlock == kFqThreads * kLaneBytes, "one 16-byte load per lane");
 static_assert(kFqLocal % kFqThreads == 0 && kFqLocal <= kFqDense, "the flush's stride");
 
-// bit k: byte k of x is LF
-__device__ __forceinline__ uint32_t lf_mask4(uint32_t x) {
-  x ^= 0x0A0A0A0Au;
-  const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;  // bit 7: low seven bits non-zero
-  const uint32_t z = ~(t | x | 0x7f7f7f7fu) >> 7;      // bits 0, 8, 16, 24
-  return (z * 0x00204081u) >> 21 & 0xFu;
-}
-
 // bit j: byte i + j of the chunk is LF (i the lane's first byte)
 __device__ __forceinline__ uint32_t lane_lfs(const uint8_t* __restrict__ text, int64_t i,
                                              int64_t n) {
   if (i >= n) return 0;
   if (i + kLaneBytes <= n) {
     const uint4 v = *reinterpret_cast<const uint4*>(text + i);
-    return lf_mask4(v.x) | lf_mask4(v.y) << 4 | lf_mask4(v.z) << 8 | lf_mask4(v.w) << 12;
+    return byte_eq_mask16(v, 0x0A0A0A0Au);
   }
   uint32_t m = 0;
   for (int j = 0; j < kLaneBytes && i + j < n; ++j)

@@ -16,9 +16,9 @@
 //                   MAGOT_RENAME_HASH_COLLISION: the matcher relies on one name
 //                   per masked hash.
 //   slots_kernel    one lane per slot: (hash, key, length) in 16 bytes.
-//   count_kernel    the ds and the LFs per text block of kTextBlock bytes (one
-//                   16-byte load per lane), then a rocprim exclusive scan of each.
-//   fill_kernel     from the same load: d number j at byte p gives d_pos[j] = p.
+//   the d index     textindex.hip's count over the ds, the LFs counted beside
+//                   them, and its fill in plain mode: d number j at byte p gives
+//                   ix.pos[j] = p.
 //   match_kernel    one lane per d.  It walks left over at most max_len bytes
 //                   and stops at the previous d, at an LF and at offset 0, so
 //                   its cost does not depend on the field's or the line's
@@ -34,15 +34,12 @@
 //   piece_kernel    one lane per piece: a binary search names its hit; source,
 //                   destination, length.  The values lie behind the text in one
 //                   allocation, so a piece's source is an offset from `text`.
-//   copy_kernel     wavecopy.h's piece_group_copy, as the FASTA reflow's.
+//   the copy        wavecopy.h's launch_piece_copy, as the FASTA reflow's.
 // The last output byte is the LF `print` adds after taking the line's last byte.
 //
-// LDS: the wave totals of the two index kernels and the copy's piece table.
-// No spin-wait; the only compare-and-swap is insert_kernel's bounded probe.
+// LDS: the copy's piece table.  No spin-wait; the only compare-and-swap is
+// insert_kernel's bounded probe.
 #include <hip/hip_runtime.h>
-
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/functional.hpp>
 
 #include "common.h"
 #include "wavecopy.h"
@@ -51,10 +48,7 @@ namespace magot {
 namespace {
 
 constexpr int kRnThreads = 256;
-constexpr int kRnLane = 16;
-constexpr int kRnWaves = kRnThreads / 64;
 constexpr int kRnGroup = kSpanGroup;  // pieces per wave of the copy
-static_assert(kTextBlock == kRnThreads * kRnLane, "one 16-byte load per lane");
 
 constexpr uint64_t kRnSeed = 0xcbf29ce484222325ull, kRnPrime = 0x100000001b3ull;
 constexpr uint64_t kRnSpread = 0x9E3779B97F4A7C15ull;
@@ -109,64 +103,6 @@ __global__ __launch_bounds__(kRnThreads) void rn_slots_kernel(RnArgs a) {
   a.slots[s] = slot;
 }
 
-// bit j of *dm, of *lf: byte i + j of the text is d, is LF (i the lane's first byte)
-__device__ __forceinline__ void rn_lane_masks(const RnArgs& a, uint64_t i, uint32_t* dm,
-                                              uint32_t* lf) {
-  *dm = *lf = 0;
-  if (i >= a.n) return;
-  const uint4 v = *reinterpret_cast<const uint4*>(a.text + i);  // readable to the next 16
-  const uint32_t keep = a.n - i < kRnLane ? (1u << (a.n - i)) - 1 : 0xffffu;  // behind the text: anything
-  *dm = byte_eq_mask16(v, a.delim * 0x01010101u) & keep;
-  *lf = byte_eq_mask16(v, 0x0A0A0A0Au) & keep;
-}
-
-__global__ __launch_bounds__(kRnThreads) void rn_count_kernel(RnArgs a) {
-  __shared__ uint32_t wave_d[kRnWaves], wave_lf[kRnWaves];
-  const int t = threadIdx.x;
-  uint32_t c = 0, l = 0;
-  if (blockIdx.x < a.n_blocks) {  // block n_blocks is the sentinel: its prefix is the total
-    uint32_t dm, lf;
-    rn_lane_masks(a, (uint64_t)blockIdx.x * kTextBlock + kRnLane * t, &dm, &lf);
-    c = __popc(dm);
-    l = __popc(lf);
-  }
-  for (int d = 32; d; d >>= 1) {
-    c += __shfl_xor(c, d, 64);
-    l += __shfl_xor(l, d, 64);
-  }
-  if ((t & 63) == 0) {
-    wave_d[t >> 6] = c;
-    wave_lf[t >> 6] = l;
-  }
-  __syncthreads();
-  if (t == 0) {
-    uint32_t sum = 0, lfs = 0;
-    for (int w = 0; w < kRnWaves; ++w) {
-      sum += wave_d[w];
-      lfs += wave_lf[w];
-    }
-    a.blk[blockIdx.x] = sum;
-    a.lf_blk[blockIdx.x] = lfs;
-  }
-}
-
-__global__ __launch_bounds__(kRnThreads) void rn_fill_kernel(RnArgs a) {
-  __shared__ uint32_t wave_count[kRnWaves];
-  const int t = threadIdx.x;
-  const uint32_t lane = t & 63, wave = t >> 6;
-  const uint64_t p0 = (uint64_t)blockIdx.x * kTextBlock + kRnLane * t;
-  uint32_t dm, lf;
-  rn_lane_masks(a, p0, &dm, &lf);
-  const uint32_t c = __popc(dm);
-  const uint32_t inc = wave_scan(c);
-  if (lane == 63) wave_count[wave] = inc;
-  __syncthreads();
-  if (!dm) return;
-  uint64_t j = a.pre[blockIdx.x] + (inc - c);  // the ds before this lane's bytes
-  for (uint32_t w = 0; w < wave; ++w) j += wave_count[w];
-  for (uint32_t m = dm; m; m &= m - 1, ++j) a.d_pos[j] = p0 + __ffs(m) - 1;  // j < n_fields
-}
-
 __device__ __forceinline__ bool rn_len_present(const RnArgs& a, uint32_t len) {
   const uint32_t b = len - 1;
   uint64_t w = a.len_mask[0];
@@ -182,16 +118,16 @@ __global__ __launch_bounds__(kRnThreads) void rn_match_kernel(RnArgs a) {
     a.f_hit[j] = 0;
     return;
   }
-  const uint64_t p = a.d_pos[j];  // below n
+  const uint64_t p = a.ix.pos[j];  // below n
   const uint32_t lim = (uint32_t)(p < a.max_len ? p : a.max_len);
   const uint64_t mask = rn_mask(a.hash_bits);
   uint64_t h = kRnSeed;
   uint32_t best = kRnNoKey, best_rank = 0xffffffffu;
-  uint32_t next = lim ? a.text[p - 1] : 0;
+  uint32_t next = lim ? a.ix.text[p - 1] : 0;
   for (uint32_t i = 1; i <= lim; ++i) {
     const uint32_t c = next;
-    if (c == a.delim || c == '\n') break;
-    if (i < lim) next = a.text[p - i - 1];  // in flight while this length is probed
+    if (c == a.ix.byte || c == '\n') break;
+    if (i < lim) next = a.ix.text[p - i - 1];  // in flight while this length is probed
     h = rn_hash_byte(h, c);
     if (!rn_len_present(a, i)) continue;
     const uint64_t hm = h & mask;
@@ -204,7 +140,7 @@ __global__ __launch_bounds__(kRnThreads) void rn_match_kernel(RnArgs a) {
       // the one name with this masked hash
       bool same = slot.len == i;
       const uint8_t* name = a.names + a.name_off[slot.key];
-      for (uint32_t q = 0; q < i && same; ++q) same = name[q] == a.text[p - i + q];
+      for (uint32_t q = 0; q < i && same; ++q) same = name[q] == a.ix.text[p - i + q];
       if (same) {
         const uint32_t r = a.rank[slot.key];
         if (r < best_rank) {
@@ -223,7 +159,7 @@ __global__ __launch_bounds__(kRnThreads) void rn_compact_kernel(RnArgs a) {
   const uint64_t j = (uint64_t)blockIdx.x * kRnThreads + threadIdx.x;
   if (j >= a.n_fields || !a.f_hit[j]) return;
   const uint64_t k = a.f_hpos[j];  // below n_hits
-  a.h_end[k] = a.d_pos[j];
+  a.h_end[k] = a.ix.pos[j];
   a.h_key[k] = a.f_key[j];
 }
 
@@ -233,7 +169,7 @@ __device__ __forceinline__ void rn_run(const RnArgs& a, uint64_t k, uint64_t* fr
                                        uint64_t* name_len, uint64_t* val_len) {
   *from = k ? a.h_end[k - 1] : 0;
   *name_len = *val_len = 0;
-  uint64_t to = a.n;
+  uint64_t to = a.ix.n;
   if (k < a.n_hits) {
     const uint32_t key = a.h_key[k];
     *name_len = a.name_off[key + 1] - a.name_off[key];
@@ -289,28 +225,7 @@ __global__ __launch_bounds__(kRnThreads) void rn_piece_kernel(RnArgs a, RnRender
   }
 }
 
-__global__ __launch_bounds__(kRnThreads) void rn_copy_kernel(RnArgs a, RnRenderArgs o) {
-  __shared__ PieceGroup groups[kRnWaves];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t t0 = ((uint64_t)blockIdx.x * kRnWaves + wave) * kRnGroup;
-  if (t0 >= o.n_pieces) return;  // the whole wave
-  const uint32_t m = (uint32_t)(o.n_pieces - t0 < kRnGroup ? o.n_pieces - t0 : kRnGroup);
-  piece_group_copy(groups[wave], m, o.p_src + t0, o.p_dst + t0, o.p_len + t0, a.text, o.out, lane);
-}
-
-hipError_t rn_sum_scan(void* tmp, size_t& tmp_bytes, const uint64_t* in, uint64_t* out, uint64_t n,
-                       hipStream_t s) {
-  return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, uint64_t(0), (size_t)n,
-                                 rocprim::plus<uint64_t>(), s);
-}
-
 }  // namespace
-
-size_t rn_tmp_bytes(uint64_t n) {
-  size_t b = 0;
-  (void)rn_sum_scan(nullptr, b, nullptr, nullptr, n, hipStream_t(0));
-  return b;
-}
 
 hipError_t launch_rn_table(const RnArgs& a, hipStream_t s) {
   if (hipError_t e = hipMemsetAsync(a.claim, 0xff, a.cap * sizeof(uint32_t), s)) return e;
@@ -324,23 +239,10 @@ hipError_t launch_rn_table(const RnArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_rn_count(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
-  rn_count_kernel<<<(unsigned)a.n_blocks + 1, kRnThreads, 0, s>>>(a);
-  if (hipError_t e = hipGetLastError()) return e;
-  if (hipError_t e = rn_sum_scan(tmp, tmp_bytes, a.lf_blk, a.lf_pre, a.n_blocks + 1, s)) return e;
-  return rn_sum_scan(tmp, tmp_bytes, a.blk, a.pre, a.n_blocks + 1, s);
-}
-
-hipError_t launch_rn_fill(const RnArgs& a, hipStream_t s) {
-  if (!a.n_fields) return hipSuccess;
-  rn_fill_kernel<<<(unsigned)a.n_blocks, kRnThreads, 0, s>>>(a);
-  return hipGetLastError();
-}
-
 hipError_t launch_rn_match(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
   rn_match_kernel<<<rn_blocks_for(a.n_fields + 1), kRnThreads, 0, s>>>(a);
   if (hipError_t e = hipGetLastError()) return e;
-  return rn_sum_scan(tmp, tmp_bytes, a.f_hit, a.f_hpos, a.n_fields + 1, s);
+  return exclusive_sum(tmp, tmp_bytes, a.f_hit, a.f_hpos, a.n_fields + 1, s);
 }
 
 hipError_t launch_rn_layout(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
@@ -350,17 +252,17 @@ hipError_t launch_rn_layout(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStr
   }
   rn_items_kernel<<<rn_blocks_for(a.n_hits + 2), kRnThreads, 0, s>>>(a);
   if (hipError_t e = hipGetLastError()) return e;
-  if (hipError_t e = rn_sum_scan(tmp, tmp_bytes, a.h_delta, a.h_dsum, a.n_hits + 1, s)) return e;
-  return rn_sum_scan(tmp, tmp_bytes, a.h_pcnt, a.h_pbase, a.n_hits + 2, s);
+  if (hipError_t e = exclusive_sum(tmp, tmp_bytes, a.h_delta, a.h_dsum, a.n_hits + 1, s)) return e;
+  return exclusive_sum(tmp, tmp_bytes, a.h_pcnt, a.h_pbase, a.n_hits + 2, s);
 }
 
 hipError_t launch_rn_render(const RnArgs& a, const RnRenderArgs& r, hipStream_t s) {
   if (!r.n_pieces) return hipSuccess;
   rn_piece_kernel<<<rn_blocks_for(r.n_pieces), kRnThreads, 0, s>>>(a, r);
   if (hipError_t e = hipGetLastError()) return e;
-  const uint64_t waves = (r.n_pieces + kRnGroup - 1) / kRnGroup;
-  rn_copy_kernel<<<(unsigned)((waves + kRnWaves - 1) / kRnWaves), kRnThreads, 0, s>>>(a, r);
-  if (hipError_t e = hipGetLastError()) return e;
+  if (hipError_t e = launch_piece_copy<kRnGroup>(r.p_src, r.p_dst, r.p_len, r.n_pieces, a.ix.text,
+                                                 r.out, s))
+    return e;
   return hipMemsetAsync(r.out + r.out_bytes - 1, '\n', 1, s);  // n > 0 gives out_bytes > 0
 }
 

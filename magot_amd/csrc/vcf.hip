@@ -1,6 +1,6 @@
 // heterozygosity_from_vcf on the device (magot_variants.py:16-139): the het
 // calls of every sample column of a VCF, counted per locus.  The whole text is
-// resident; its line index is psl.hip's.
+// resident; its line index is textindex.hip's (the LFs, line mode).
 //
 //   classify_kernel  one lane per line, its first two bytes: blank, "##", the
 //                    '#' line, or data.  One rocprim scan of the two flags packed
@@ -36,8 +36,6 @@
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/functional.hpp>
 
 #include "common.h"
 
@@ -50,25 +48,12 @@ constexpr uint32_t kVcfFixed = 9;  // CHROM .. FORMAT
 
 inline unsigned vcf_blocks_for(uint64_t n) { return (unsigned)((n + kVcfThreads - 1) / kVcfThreads); }
 
-// bit k: byte k of x is the byte that fills `pattern`
-__device__ __forceinline__ uint32_t vcf_byte_mask4(uint32_t x, uint32_t pattern) {
-  x ^= pattern;
-  const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-  const uint32_t z = ~(t | x | 0x7f7f7f7fu) >> 7;
-  return (z * 0x00204081u) >> 21 & 0xFu;
-}
-
-__device__ __forceinline__ uint32_t vcf_byte_mask16(uint4 v, uint32_t pattern) {
-  return vcf_byte_mask4(v.x, pattern) | vcf_byte_mask4(v.y, pattern) << 4 |
-         vcf_byte_mask4(v.z, pattern) << 8 | vcf_byte_mask4(v.w, pattern) << 12;
-}
-
 // read_vcf drops every CR of the text before it splits it: a text with one is
 // the host path's
 __global__ __launch_bounds__(kVcfThreads) void vcf_cr_kernel(VcfArgs a) {
   const uint64_t p = ((uint64_t)blockIdx.x * kVcfThreads + threadIdx.x) * 16;
   if (p >= a.n) return;
-  uint32_t m = vcf_byte_mask16(*reinterpret_cast<const uint4*>(a.text + p), 0x0D0D0D0Du);
+  uint32_t m = byte_eq_mask16(*reinterpret_cast<const uint4*>(a.text + p), 0x0D0D0D0Du);
   if (a.n - p < 16) m &= (1u << (a.n - p)) - 1;
   if (m) atomicMax(a.status + 4, 1ull);
 }
@@ -196,7 +181,7 @@ __global__ __launch_bounds__(64) void vcf_parse_kernel(VcfArgs a) {
       uint32_t m = 0;
       if (p < end) {
         const uint4 v = *reinterpret_cast<const uint4*>(a.text + p);
-        m = vcf_byte_mask16(v, 0x09090909u);  // TAB
+        m = byte_eq_mask16(v, 0x09090909u);  // TAB
         if (base - abase < kVcfStage) stage[(base - abase) / 16 + lane] = v;
         if (p < start) m &= ~((1u << (start - p)) - 1);      // start - p is below 16
         if (end - p < 16) m &= (1u << (end - p)) - 1;
@@ -241,11 +226,7 @@ __global__ __launch_bounds__(64) void vcf_parse_kernel(VcfArgs a) {
       const uint32_t klen = clen + 3 + plen;
       uint64_t h = 0;
       uint32_t k = 0;
-      auto feed = [&](uint32_t c) {
-        if (!k) h = (uint64_t)c << 7;
-        h = (h * 1000003ull) ^ c;
-        ++k;
-      };
+      auto feed = [&](uint32_t c) { h = py27_hash_step(h, k++, c); };
       for (uint32_t j = 0; j < clen; ++j) {
         feed(at(j));
         if (j + 2 < clen && at(j) == '<' && at(j + 1) == ':' && at(j + 2) == '>')
@@ -262,8 +243,7 @@ __global__ __launch_bounds__(64) void vcf_parse_kernel(VcfArgs a) {
         if (c < '0' || c > '9') digits = false;
         else if (j < 10) v = v * 10 + (c - '0');
       }
-      h ^= klen;
-      if (h == ~0ull) h = ~0ull - 1;
+      h = py27_hash_end(h, klen);  // klen >= 3
       if (!reason) {
         if (!digits || (plen > 1 && at(p0) == '0')) reason = MAGOT_VCF_POS_FORM;
         else if (plen > 10 || v > 0x7fffffffull) reason = MAGOT_VCF_POS_RANGE;
@@ -452,25 +432,16 @@ __global__ __launch_bounds__(64) void vcf_count_kernel(VcfArgs a, VcfCountArgs c
 }  // namespace
 
 size_t vcf_tmp_bytes(uint64_t n_lines) {
-  size_t x = 0, y = 0, z = 0;
+  size_t z = 0;
   const size_t n = (size_t)n_lines;
-  (void)rocprim::exclusive_scan(nullptr, x, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                uint64_t(0), n + 1, rocprim::plus<uint64_t>(), hipStream_t(0));
-  (void)rocprim::exclusive_scan(nullptr, y, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                uint32_t(0), n + 1, rocprim::plus<uint32_t>(), hipStream_t(0));
+  const size_t x = exclusive_sum_bytes<uint64_t>(n + 1), y = exclusive_sum_bytes<uint32_t>(n + 1);
   (void)rocprim::radix_sort_pairs(nullptr, z, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 64,
                                   hipStream_t(0));
   return std::max(x, std::max(y, z));
 }
 
-size_t vcf_count_tmp_bytes(uint64_t n_loci) {
-  size_t x = 0;
-  (void)rocprim::exclusive_scan(nullptr, x, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                uint64_t(0), (size_t)n_loci + 1, rocprim::plus<uint64_t>(),
-                                hipStream_t(0));
-  return x;
-}
+size_t vcf_count_tmp_bytes(uint64_t n_loci) { return exclusive_sum_bytes<uint64_t>(n_loci + 1); }
 
 hipError_t launch_vcf_classify(const VcfArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
   // status: nothing declined, no '#' line, no first '#' line, no first data line, no CR
@@ -481,8 +452,7 @@ hipError_t launch_vcf_classify(const VcfArgs& a, void* tmp, size_t tmp_bytes, hi
   if (hipError_t e = hipGetLastError()) return e;
   vcf_classify_kernel<<<vcf_blocks_for(a.n_lines + 1), kVcfThreads, 0, s>>>(a);
   if (hipError_t e = hipGetLastError()) return e;
-  return rocprim::exclusive_scan(tmp, tmp_bytes, (const uint64_t*)a.kind, a.kpos, uint64_t(0),
-                                 (size_t)a.n_lines + 1, rocprim::plus<uint64_t>(), s);
+  return exclusive_sum(tmp, tmp_bytes, a.kind, a.kpos, a.n_lines + 1, s);
 }
 
 hipError_t launch_vcf_compact(const VcfArgs& a, hipStream_t s) {
@@ -503,8 +473,7 @@ hipError_t launch_vcf_parse(const VcfArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_vcf_runs_scan(const VcfArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s) {
-  return rocprim::exclusive_scan(tmp, tmp_bytes, (const uint32_t*)a.head, a.run, uint32_t(0),
-                                 (size_t)a.n_data + 1, rocprim::plus<uint32_t>(), s);
+  return exclusive_sum(tmp, tmp_bytes, a.head, a.run, a.n_data + 1, s);
 }
 
 hipError_t launch_vcf_runs(const VcfArgs& a, hipStream_t s) {
@@ -537,8 +506,7 @@ hipError_t launch_vcf_ranges(const VcfArgs& a, const VcfCountArgs& c, void* tmp,
                              hipStream_t s) {
   vcf_ranges_kernel<<<vcf_blocks_for(c.n_loci + 1), kVcfThreads, 0, s>>>(a, c);
   if (hipError_t e = hipGetLastError()) return e;
-  return rocprim::exclusive_scan(tmp, tmp_bytes, (const uint64_t*)c.pieces, c.piece_off,
-                                 uint64_t(0), (size_t)c.n_loci + 1, rocprim::plus<uint64_t>(), s);
+  return exclusive_sum(tmp, tmp_bytes, c.pieces, c.piece_off, c.n_loci + 1, s);
 }
 
 hipError_t launch_vcf_count(const VcfArgs& a, const VcfCountArgs& c, hipStream_t s) {

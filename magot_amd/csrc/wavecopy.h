@@ -242,4 +242,31 @@ __device__ __forceinline__ void piece_group_copy(PieceGroup& L, uint32_t m,
   }
 }
 
+// n_pieces pieces, kGroup consecutive ones per wave of a 256-thread workgroup
+constexpr int kPieceThreads = 256;
+template <int kGroup>
+__global__ __launch_bounds__(kPieceThreads) void piece_copy_kernel(
+    const uint64_t* p_src, const uint64_t* p_dst, const uint32_t* p_len, uint64_t n_pieces,
+    const uint8_t* base, uint8_t* out) {
+  static_assert(kGroup >= 1 && kGroup <= kSpanGroup, "count_le searches kSpanGroup entries");
+  constexpr int kWavesPerBlock = kPieceThreads / 64;
+  __shared__ PieceGroup groups[kWavesPerBlock];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t t0 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kGroup;
+  if (t0 >= n_pieces) return;  // the whole wave
+  const uint32_t m = (uint32_t)(n_pieces - t0 < kGroup ? n_pieces - t0 : kGroup);
+  piece_group_copy(groups[wave], m, p_src + t0, p_dst + t0, p_len + t0, base, out, lane);
+}
+
+template <int kGroup>
+hipError_t launch_piece_copy(const uint64_t* p_src, const uint64_t* p_dst, const uint32_t* p_len,
+                             uint64_t n_pieces, const uint8_t* base, uint8_t* out, hipStream_t s) {
+  constexpr int kWavesPerBlock = kPieceThreads / 64;
+  const uint64_t waves = (n_pieces + kGroup - 1) / kGroup;
+  piece_copy_kernel<kGroup>
+      <<<(unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock), kPieceThreads, 0, s>>>(
+          p_src, p_dst, p_len, n_pieces, base, out);
+  return hipGetLastError();
+}
+
 }  // namespace magot
