@@ -372,6 +372,53 @@ int magot_debug_text_index(magot_ctx* ctx, const uint8_t* text, uint64_t len, ui
                            uint32_t byte, int32_t second_byte, uint64_t* pos_out, uint64_t* n_out,
                            uint64_t* second_count_out);
 
+/* Debug: the same index in line mode, as the four tools run it: the count of
+ * LF, then the fill of the line starts, with the stray-CR check when check_cr
+ * is not 0.  len and index_len as above.  *n_lines_out: the LFs of the text,
+ * and one more when it does not end in LF; pos_out (NULL, or room for
+ * index_len + 2 entries) receives n_lines + 1 line starts, pos[0] = 0 and
+ * pos[n_lines] = index_len; nothing is filled or written when n_lines is 0.
+ * *stray_out (may be NULL) receives the raw status word, the lowest
+ * line << 8 | stray_reason (0..255) over the CRs that are neither before an LF
+ * nor the text's last byte, or all ones when there is none (always, without
+ * check_cr). */
+int magot_debug_text_lines(magot_ctx* ctx, const uint8_t* text, uint64_t len, uint64_t index_len,
+                           int check_cr, uint32_t stray_reason, uint64_t* pos_out,
+                           uint64_t* n_lines_out, uint64_t* stray_out);
+
+/* Debug: the grouped piece copy of the FASTA reflow and the renamed text on
+ * its own: piece i is the len[i] bytes at base + src[i], copied to
+ * out + dst[i], 16 consecutive pieces per wave.  base (base_len bytes) goes
+ * to the device with the padding the copy asks for; out (out_len bytes) is
+ * uploaded, written by the copy and copied back whole, so every byte no piece
+ * covers comes back as the caller's.  A piece outside base or out is
+ * MAGOT_ERR_RANGE before any launch (out is then untouched); base_len and
+ * out_len are below 2^28 (MAGOT_ERR_ARG).  Destinations must not overlap. */
+int magot_debug_piece_copy(magot_ctx* ctx, const uint8_t* base, uint64_t base_len,
+                           const uint64_t* src, const uint64_t* dst, const uint32_t* len,
+                           uint64_t n, uint8_t* out, uint64_t out_len);
+
+/* Debug: the FASTA text assembly of magot_fasta_text_execute on its own, over
+ * tables of the caller's.  Unit i is text[text_off, text_off + text_len)
+ * followed by the payload of record rec, pay[rspan[2 rec], rspan[2 rec + 1]),
+ * or by nothing (rec = MAGOT_NO_RECORD); with protein not 0 a payload that
+ * begins with 'X' loses that byte.  The units are written one behind the
+ * other from out[0]; out (out_len bytes) is uploaded and copied back whole as
+ * in magot_debug_piece_copy, and *written is the text's length.  A unit or a
+ * record span outside its buffer, a rec >= n_rec and a text longer than
+ * out_len are MAGOT_ERR_RANGE before any launch; text_len, pay_len and
+ * out_len are below 2^28 (MAGOT_ERR_ARG). */
+#define MAGOT_NO_RECORD 0xFFFFFFFFu
+typedef struct magot_text_unit {
+  uint64_t text_off;
+  uint32_t text_len;
+  uint32_t rec;
+} magot_text_unit;
+int magot_debug_text_assembly(magot_ctx* ctx, const magot_text_unit* units, uint64_t n,
+                              const uint8_t* text, uint64_t text_len, const uint64_t* rspan,
+                              uint64_t n_rec, const uint8_t* pay, uint64_t pay_len, int protein,
+                              uint8_t* out, uint64_t out_len, uint64_t* written);
+
 /*
  * Raw-sequence batch ops over n byte strings (seq_off has n+1 entries).
  * Replaces: Sequence.reverse_compliment (genome.py:784-793).

@@ -49,7 +49,8 @@ EXPORTS = (
     'magot_copy_segments', 'magot_ctx_mark', 'magot_ctx_elapsed', 'magot_orf6_copy_outputs',
     'magot_genome_wire_export', 'magot_genome_wire_import',
     'magot_debug_tile_blocks', 'magot_debug_tile_cut', 'magot_debug_plan',
-    'magot_debug_text_index',
+    'magot_debug_text_index', 'magot_debug_text_lines', 'magot_debug_piece_copy',
+    'magot_debug_text_assembly',
     'magot_orfcall_tile', 'magot_orfcall_create', 'magot_orfcall_fetch', 'magot_orfcall_text',
     'magot_orfcall_text_fetch', 'magot_orfcall_time', 'magot_orfcall_destroy',
     'magot_mask_piece', 'magot_mask_plan', 'magot_maskplan_table', 'magot_maskplan_destroy',
@@ -185,6 +186,15 @@ def _declare(lib):
         'magot_debug_text_index': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
                                                   ctypes.c_uint32, ctypes.c_int32, _vp, _u64p,
                                                   _u64p]),
+        'magot_debug_text_lines': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                                  ctypes.c_int, ctypes.c_uint32, _vp, _u64p,
+                                                  _u64p]),
+        'magot_debug_piece_copy': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                                  ctypes.c_uint64, _vp, ctypes.c_uint64]),
+        'magot_debug_text_assembly': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp,
+                                                     ctypes.c_uint64, _vp, ctypes.c_uint64, _vp,
+                                                     ctypes.c_uint64, ctypes.c_int, _vp,
+                                                     ctypes.c_uint64, _u64p]),
         'magot_revcomp_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp]),
         'magot_translate_sizes': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp]),
         'magot_translate_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,

@@ -1,11 +1,32 @@
 // C ABI of libmagot.so (declarations and contracts: include/magot.h): errors,
-// devices and contexts.  The features are in the abi_*.hip units.
+// devices and contexts, and the debug entries of the routines the text tools
+// share (textindex.hip, wavecopy.h).  The features are in the abi_*.hip units.
 #include "abi_internal.h"
+#include "wavecopy.h"
 
 namespace magot {
 
 namespace {
 thread_local std::string g_last_error;
+
+// the debug copies: the grouped copies count a group's chunks and bytes in 32
+// bits (wavecopy.h)
+constexpr uint64_t kDebugCopyMax = 1ull << 28;
+// [at, at + len) lies in a buffer of `size` bytes
+inline bool span_inside(uint64_t at, uint64_t len, uint64_t size) {
+  return at <= size && len <= size - at;
+}
+// n bytes (or none) to and from the device on s
+inline hipError_t to_device(void* dev, const void* host, uint64_t n, hipStream_t s) {
+  return n ? hipMemcpyAsync(dev, host, n, hipMemcpyHostToDevice, s) : hipSuccess;
+}
+inline hipError_t to_host(void* host, const void* dev, uint64_t n, hipStream_t s) {
+  return n ? hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, s) : hipSuccess;
+}
+template <class T>
+T* at(char* mem, uint64_t off) {
+  return reinterpret_cast<T*>(mem + off);
+}
 }
 
 void set_error(const std::string& msg) { g_last_error = msg; }
@@ -173,6 +194,177 @@ int magot_debug_text_index(magot_ctx* ctx, const uint8_t* text, uint64_t len, ui
     MAGOT_HIP_TRY(hipMemcpy(pos_out, ix.pos, total * 8, hipMemcpyDeviceToHost));
   *n_out = total;
   if (second_count_out) *second_count_out = total2;
+  return MAGOT_OK;
+}
+
+// The same index in line mode, the way resident_text_open and the four tools
+// run it: the LF count, n_lines from it and the text's last byte, the status
+// word preset to all ones, then the fill (with the stray-CR check or without).
+int magot_debug_text_lines(magot_ctx* ctx, const uint8_t* text, uint64_t len, uint64_t index_len,
+                           int check_cr, uint32_t stray_reason, uint64_t* pos_out,
+                           uint64_t* n_lines_out, uint64_t* stray_out) {
+  if (int rc = bind(ctx)) return rc;
+  if (!n_lines_out || (len && !text) || index_len > len || stray_reason > 255) {
+    set_error("magot_debug_text_lines: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  hipStream_t s = ctx->stream;
+  TextIndexArgs ix{};
+  ix.n = index_len;
+  ix.n_blocks = depth_text_blocks(index_len);
+  ix.byte = '\n';
+  ix.byte2 = kTextNoByte;
+  ix.stray_reason = stray_reason;
+  const size_t tmp_bytes = exclusive_sum_bytes<uint64_t>(ix.n_blocks + 1);
+  Carve cv;
+  const uint64_t o_text = cv.take<uint8_t>(len + kTextPad);
+  const uint64_t o_blk = cv.take<uint64_t>(ix.n_blocks + 1);
+  const uint64_t o_pre = cv.take<uint64_t>(ix.n_blocks + 1);
+  const uint64_t o_tmp = cv.take<uint8_t>(tmp_bytes);
+  const uint64_t o_status = cv.take<unsigned long long>(1);
+  // a line start per byte and the two end entries; room for every byte a lane loads
+  const uint64_t o_pos = cv.take<uint64_t>(len + kTextPad + 2);
+  DevBuf buf;
+  MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
+  char* base = static_cast<char*>(buf.p);
+  ix.text = reinterpret_cast<const uint8_t*>(base + o_text);
+  ix.blk = reinterpret_cast<uint64_t*>(base + o_blk);
+  ix.pre = reinterpret_cast<uint64_t*>(base + o_pre);
+  ix.pos = reinterpret_cast<uint64_t*>(base + o_pos);
+  ix.stray_status = reinterpret_cast<unsigned long long*>(base + o_status);
+  if (len) MAGOT_HIP_TRY(hipMemcpyAsync(base + o_text, text, len, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(hipMemsetAsync(ix.stray_status, 0xff, sizeof(unsigned long long), s));
+  MAGOT_HIP_TRY(launch_text_count(ix, base + o_tmp, tmp_bytes, s));
+  uint64_t total = 0;
+  MAGOT_HIP_TRY(hipMemcpyAsync(&total, ix.pre + ix.n_blocks, 8, hipMemcpyDeviceToHost, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  if (total > index_len) {
+    set_error("magot_debug_text_lines: more line feeds than bytes");
+    return MAGOT_ERR_STATE;
+  }
+  ix.n_lines = total + (index_len && text[index_len - 1] != '\n' ? 1 : 0);
+  unsigned long long status = ~0ull;
+  if (ix.n_lines) {
+    MAGOT_HIP_TRY(launch_text_fill(ix, check_cr ? kTextFillLinesCr : kTextFillLines, s));
+    MAGOT_HIP_TRY(hipMemcpyAsync(&status, ix.stray_status, 8, hipMemcpyDeviceToHost, s));
+    if (pos_out) MAGOT_HIP_TRY(to_host(pos_out, ix.pos, (ix.n_lines + 1) * 8, s));
+    MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  }
+  *n_lines_out = ix.n_lines;
+  if (stray_out) *stray_out = status;
+  return MAGOT_OK;
+}
+
+// wavecopy.h's grouped piece copy on its own, as fastarec.hip and rename.hip
+// launch it (kFaGroup = kRnGroup = 16).
+int magot_debug_piece_copy(magot_ctx* ctx, const uint8_t* base, uint64_t base_len,
+                           const uint64_t* src, const uint64_t* dst, const uint32_t* len,
+                           uint64_t n, uint8_t* out, uint64_t out_len) {
+  if (int rc = bind(ctx)) return rc;
+  if ((n && (!src || !dst || !len)) || (base_len && !base) || (out_len && !out) ||
+      base_len >= kDebugCopyMax || out_len >= kDebugCopyMax) {
+    set_error("magot_debug_piece_copy: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  for (uint64_t i = 0; i < n; ++i)
+    if (!span_inside(src[i], len[i], base_len) || !span_inside(dst[i], len[i], out_len)) {
+      set_error("magot_debug_piece_copy: piece " + std::to_string(i) +
+                " lies outside its buffer");
+      return MAGOT_ERR_RANGE;
+    }
+  hipStream_t s = ctx->stream;
+  Carve cv;
+  const uint64_t o_base = cv.take<uint8_t>(((base_len + 15) & ~15ull) + kTextPad);
+  const uint64_t o_out = cv.take<uint8_t>(out_len);
+  const uint64_t o_src = cv.take<uint64_t>(n), o_dst = cv.take<uint64_t>(n);
+  const uint64_t o_len = cv.take<uint32_t>(n);
+  DevBuf buf;
+  MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
+  char* mem = static_cast<char*>(buf.p);
+  MAGOT_HIP_TRY(to_device(mem + o_base, base, base_len, s));
+  MAGOT_HIP_TRY(to_device(mem + o_out, out, out_len, s));
+  MAGOT_HIP_TRY(to_device(mem + o_src, src, n * 8, s));
+  MAGOT_HIP_TRY(to_device(mem + o_dst, dst, n * 8, s));
+  MAGOT_HIP_TRY(to_device(mem + o_len, len, n * 4, s));
+  if (n)
+    MAGOT_HIP_TRY(launch_piece_copy<16>(
+        at<const uint64_t>(mem, o_src), at<const uint64_t>(mem, o_dst),
+        at<const uint32_t>(mem, o_len), n, at<const uint8_t>(mem, o_base),
+        at<uint8_t>(mem, o_out), s));
+  MAGOT_HIP_TRY(to_host(out, mem + o_out, out_len, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  return MAGOT_OK;
+}
+
+// render.hip's text assembly on its own, as magot_fasta_text_execute launches
+// it: the unit lengths, their scan, the grouped span copy with text parts.
+int magot_debug_text_assembly(magot_ctx* ctx, const magot_text_unit* units, uint64_t n,
+                              const uint8_t* text, uint64_t text_len, const uint64_t* rspan,
+                              uint64_t n_rec, const uint8_t* pay, uint64_t pay_len, int protein,
+                              uint8_t* out, uint64_t out_len, uint64_t* written) {
+  static_assert(sizeof(magot_text_unit) == sizeof(TextUnit) && MAGOT_NO_RECORD == kNoRecord,
+                "magot_text_unit is TextUnit");
+  if (int rc = bind(ctx)) return rc;
+  if (!written || (n && !units) || (text_len && !text) || (n_rec && !rspan) ||
+      (pay_len && !pay) || (out_len && !out) || n_rec >= kNoRecord ||
+      text_len >= kDebugCopyMax || pay_len >= kDebugCopyMax || out_len >= kDebugCopyMax) {
+    set_error("magot_debug_text_assembly: bad argument");
+    return MAGOT_ERR_ARG;
+  }
+  for (uint64_t r = 0; r < n_rec; ++r)
+    if (rspan[2 * r] > rspan[2 * r + 1] || rspan[2 * r + 1] > pay_len) {
+      set_error("magot_debug_text_assembly: record " + std::to_string(r) + " lies outside pay");
+      return MAGOT_ERR_RANGE;
+    }
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const magot_text_unit& u = units[i];
+    if (!span_inside(u.text_off, u.text_len, text_len) ||
+        (u.rec != MAGOT_NO_RECORD && u.rec >= n_rec)) {
+      set_error("magot_debug_text_assembly: unit " + std::to_string(i) +
+                " lies outside text, or names no record");
+      return MAGOT_ERR_RANGE;
+    }
+    total += u.text_len;
+    if (u.rec != MAGOT_NO_RECORD) {
+      uint64_t a = rspan[2 * (uint64_t)u.rec];
+      const uint64_t e = rspan[2 * (uint64_t)u.rec + 1];
+      if (protein && e > a && pay[a] == 'X') ++a;  // unit_payload's rule (render.hip)
+      total += e - a;
+    }
+    if (total > out_len) {
+      set_error("magot_debug_text_assembly: the text is longer than out_len");
+      return MAGOT_ERR_RANGE;
+    }
+  }
+  hipStream_t s = ctx->stream;
+  const size_t scan_bytes = text_scan_bytes(n);
+  Carve cv;
+  const uint64_t o_units = cv.take<TextUnit>(n);
+  const uint64_t o_rspan = cv.take<uint64_t>(2 * n_rec);
+  const uint64_t o_text = cv.take<uint8_t>(((text_len + 15) & ~15ull) + kTextPad);
+  const uint64_t o_pay = cv.take<uint8_t>(((pay_len + 15) & ~15ull) + kTextPad);
+  const uint64_t o_len = cv.take<uint64_t>(n), o_psrc = cv.take<uint64_t>(n);
+  const uint64_t o_end = cv.take<uint64_t>(n);
+  const uint64_t o_tmp = cv.take<uint8_t>(scan_bytes);
+  const uint64_t o_out = cv.take<uint8_t>(out_len);
+  DevBuf buf;
+  MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
+  char* mem = static_cast<char*>(buf.p);
+  MAGOT_HIP_TRY(to_device(mem + o_units, units, n * sizeof(TextUnit), s));
+  MAGOT_HIP_TRY(to_device(mem + o_rspan, rspan, 2 * n_rec * 8, s));
+  MAGOT_HIP_TRY(to_device(mem + o_text, text, text_len, s));
+  MAGOT_HIP_TRY(to_device(mem + o_pay, pay, pay_len, s));
+  MAGOT_HIP_TRY(to_device(mem + o_out, out, out_len, s));
+  launch_text_assembly(at<const TextUnit>(mem, o_units), n, at<const uint64_t>(mem, o_rspan),
+                       at<const uint8_t>(mem, o_pay), protein, at<const uint8_t>(mem, o_text),
+                       at<uint64_t>(mem, o_len), at<uint64_t>(mem, o_psrc),
+                       at<uint64_t>(mem, o_end), mem + o_tmp, scan_bytes,
+                       at<uint8_t>(mem, o_out), s);
+  MAGOT_HIP_TRY(hipGetLastError());
+  MAGOT_HIP_TRY(to_host(out, mem + o_out, out_len, s));
+  MAGOT_HIP_TRY(hipStreamSynchronize(s));
+  *written = total;
   return MAGOT_OK;
 }
 
