@@ -35,6 +35,9 @@
 // retried on the same slot; nothing is float.
 #include <hip/hip_runtime.h>
 
+#include <cerrno>
+#include <cstdlib>
+
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
@@ -461,13 +464,27 @@ hipError_t launch_vcf_compact(const VcfArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the most workgroups of the parse pass: 2^20, above which its workgroups stride
+// over the data lines.  MAGOT_VCF_PARSE_GRID = 1 .. 2^20 lowers it (test hook:
+// force the stride); read on every call, anything else is 2^20.
+static uint64_t vcf_parse_grid_cap() {
+  constexpr uint64_t kCap = 1u << 20;
+  const char* e = std::getenv("MAGOT_VCF_PARSE_GRID");
+  if (!e || !*e) return kCap;
+  char* end = nullptr;
+  errno = 0;
+  const unsigned long long v = std::strtoull(e, &end, 10);
+  if (errno || *end || *e < '0' || *e > '9' || v < 1 || v > kCap) return kCap;
+  return v;
+}
+
 hipError_t launch_vcf_parse(const VcfArgs& a, hipStream_t s) {
   if (!a.n_data) return hipSuccess;
   // what a line outside the grammar leaves unwritten is zero, and head[n_data] ends the scan
   if (hipError_t e = hipMemsetAsync(a.head, 0, (a.n_data + 1) * sizeof(uint32_t), s)) return e;
   if (hipError_t e = hipMemsetAsync(a.bits, 0, a.n_data * a.words * sizeof(uint32_t), s)) return e;
   // a workgroup per line (a grid of 8192 that strides over the lines measured 22 % slower)
-  const unsigned grid = (unsigned)std::min<uint64_t>(a.n_data, 1u << 20);
+  const unsigned grid = (unsigned)std::min<uint64_t>(a.n_data, vcf_parse_grid_cap());
   vcf_parse_kernel<<<grid, 64, vcf_parse_lds(a.n_samples), s>>>(a);
   return hipGetLastError();
 }

@@ -44,12 +44,17 @@ def _spans(text, off, length):
     return [text[int(o):int(o) + int(n)] for o, n in zip(off.tolist(), length.tolist())]
 
 
-def _locus_columns(loci):
+def _locus_columns(loci, ids=None):
+    """``ids``: the contig id of every name; without it the names are numbered
+    as the loci bring them"""
     contig, lo, hi = [], [], []
-    ids = {}
+    if ids is None:
+        ids = {}
+        for locus in loci:
+            ids.setdefault(locus.split(',')[0], len(ids))
     for locus in loci:
         f = locus.split(',')
-        contig.append(ids.setdefault(f[0], len(ids)))
+        contig.append(ids[f[0]])
         a, b = (int(f[1]), int(f[2])) if len(f) > 2 else (0, 2 ** 32 - 1)
         a, b = max(a, 0), min(b, 2 ** 32 - 1)
         lo.append(a if a <= b else 1)
@@ -57,8 +62,8 @@ def _locus_columns(loci):
     return ids, contig, lo, hi
 
 
-def _assert_equals_table(hets, text, loci, order):
-    want = ve.table(text, loci, order)
+def _assert_equals_table(hets, text, loci, order, ids=None):
+    want = ve.table(text, loci, order, ids)
     n = len(want['line'])
     assert (hets.n_data, hets.n_runs) == (n, len(want['runs']))
     lines = ve.split_lines(text)
@@ -68,7 +73,7 @@ def _assert_equals_table(hets, text, loci, order):
     assert text[hets.header[0]:sum(hets.header)] == [ln for _, ln in lines
                                                      if ln[:1] == '#' and ln[:2] != '##'][0]
     assert _spans(text, *hets.runs()) == want['runs']
-    ids, contig, lo, hi = _locus_columns(loci)
+    ids, contig, lo, hi = _locus_columns(loci, ids)
     hets.resolve([ids[name] for name in want['runs']])
     t = hets.tables()
     assert t['bits'].shape == (n, hets.words) and hets.words == (hets.n_samples + 31) // 32

@@ -3,7 +3,10 @@ without magot_amd.magot_variants: ``expected`` (the three prints, the returned
 string, the exception name), ``table`` (the device tables: per data line POS,
 key hash, het bits, kept and first flags, and the counts per locus),
 ``native_note`` (which path answers, from the native grammar as the issue
-states it), the recorded cases and the seeded worlds of the device tests.
+states it), the recorded cases, the seeded worlds of the device tests and the
+edge builders of test_gpu_vcf_edges.py (phases, seams, chroms, table7,
+table1024, kinds, no_final_lf, cr_cases, sort_text, many_loci, pieces,
+alternating, decline_texts).
 
 Text is latin-1 str here; files are its bytes."""
 
@@ -243,18 +246,23 @@ def native_note(text, loci=None, window=10000, order='py2'):
     return 'foreign_name' if t['foreign'] else 'native'
 
 
-def table(text, loci, order):
+def table(text, loci, order, ids=None):
     """For a text inside the native grammar and loci of plain numbers: per data
     line 'line', 'pos', 'hash', 'bits' (a Python int, bit s for sample column s),
     'kept', 'first'; 'contig_of_run'; 'first_line' (the line of
     list(variant_set)[0]); 'allowed' (an int); 'counts' (per locus a list per
-    sample column) and 'foreign'."""
+    sample column) and 'foreign'.  ``ids`` (CHROM -> contig id) is what the
+    caller resolves the runs with: names with one id are one contig to the
+    sort, the flags and the counts; without it every name is its own."""
     lines = split_lines(text)
     data = [(k, ln.split('\t')) for k, ln in lines if ln and ln[0] != '#']
     n_samples = len(data[0][1]) - 9
+    cid = (lambda name: name) if ids is None else (lambda name: ids[name])
     seq_ids = {}
     for locus in loci:
         seq_ids.setdefault(locus.split(',')[0], len(seq_ids))
+    if ids is not None:
+        seq_ids = ids
     t = {'line': [], 'pos': [], 'hash': [], 'bits': [], 'key': [], 'runs': []}
     for k, f in data:
         gi = f[8].split(':').index('GT')
@@ -267,7 +275,7 @@ def table(text, loci, order):
         t['pos'].append(int(f[1]))
         t['hash'].append(py2order.str_hash(f[0] + '<:>' + f[1]))
         t['bits'].append(bits)
-        t['key'].append((f[0], int(f[1])))
+        t['key'].append((cid(f[0]), int(f[1])))
         if not t['runs'] or t['runs'][-1] != f[0]:
             t['runs'].append(f[0])
     t['contig_of_run'] = [seq_ids.get(name) for name in t['runs']]
@@ -277,9 +285,9 @@ def table(text, loci, order):
         first_of.setdefault(key, d)
     t['kept'] = [int(last_of[key] == d) for d, key in enumerate(t['key'])]
     t['first'] = [int(first_of[key] == d) for d, key in enumerate(t['key'])]
-    codes = keys_in_order(['%s<:>%d' % key for key in first_of], order)
-    chrom, _, pos = codes[0].rpartition('<:>')
-    d0 = last_of[(chrom, int(pos))]
+    # a key is spelt as its first line spells it
+    spelt = {'%s<:>%s' % tuple(data[d][1][:2]): key for key, d in first_of.items()}
+    d0 = last_of[spelt[keys_in_order(list(spelt), order)[0]]]
     t['first_line'] = t['line'][d0]
     f0 = data[d0][1]
     t['allowed'] = 0
@@ -290,7 +298,7 @@ def table(text, loci, order):
         f = locus.split(',')
         row = [0] * n_samples
         for d, (chrom, pos) in enumerate(t['key']):
-            if not t['kept'][d] or chrom != f[0]:
+            if not t['kept'][d] or chrom != cid(f[0]):
                 continue
             if len(f) > 2 and not int(f[1]) <= pos <= int(f[2]):
                 continue
@@ -434,6 +442,24 @@ def cases():
                            names=('only',)), None, 10000)
     c['names_to_escape'] = (vcf([row('c1', 5, '0/1:5', '0/0:6', '1/0:7')],
                                 names=("it's", 'a"b\'c', 'caf\xe9\\')), None, 10000)
+    # CHROMs beyond the 64 lanes that compare one with the line before, an empty
+    # one, and one beyond the 4 KB of a line that the parse pass keeps in LDS
+    for name, n in (('chrom_64_bytes', 64), ('chrom_65_bytes_loci', 65)):
+        x = ('scaffold_' + 'ACGT0123456789' * 5)[:n]
+        near, longer = x[:-1] + 'x', x + 'z'
+        text = vcf([row(x, 5, '0/1:5', '0/0:6', '1/1:7'), row(x, 6, '0/0:5', '0/1:6', '1/1:7'),
+                    row(near, 5, '0/1:5', '0/1:6', '1/1:7'), row(longer, 5, '1/1:5', '0/1:6', '0/1:7'),
+                    row(x, 5, '0/0:5', '0/1:6', '0/1:7')],
+                   contigs=((x, 250), (near, 90), (longer, 30)))
+        c[name] = (text, None if n == 64 else [x + ',1,100', x + ',50', near + ',50', longer + ',1,5'],
+                   100)
+    c['chrom_empty'] = (vcf([row('', 5, '0/1:5', '0/0:6', '1/1:7'), row('', 6, '0/0:5', '0/1:6', '1/1:7'),
+                             row('c1', 5, '0/1:5', '0/1:6', '1/1:7'), row('', 5, '0/0:5', '0/1:6', '0/1:7')]),
+                        [',1,100', ',7', 'c1,1,100'], 10000)
+    x = ('K' + 'ACGTTGCA' * 600)[:4097]
+    c['chrom_above_4k'] = (vcf([row(x, 5, '0/1:5', '0/0:6', '1/1:7'), row(x, 6, '0/0:5', '0/1:6', '1/1:7'),
+                                row(x, 5, '0/0:5', '0/1:6', '0/1:7')], contigs=()),
+                           [x + ',1,100'], 10000)
     rnd = random.Random(20261020)
     for k in range(6):
         c['random_%d' % k] = (random_text(rnd), None, rnd.choice([50, 100, 1000]))
@@ -517,3 +543,500 @@ def world(n_data, n_samples, seed=20261020):
              'ctgA,%d,%d' % (top + 5, top + 9), 'ctgB,3,%d' % top, 'ctgA,%d,%d' % (w, 3 * w)]
     _worlds[(n_data, n_samples, seed)] = (text, loci)
     return text, loci
+
+
+# ---------------------------------------------------------------------------
+# the edge builders of the device tests: what each holds is asserted without a
+# device in test_vcf_edges_expect.py, and test_gpu_vcf_edges.py runs them
+# ---------------------------------------------------------------------------
+
+STAGE = 4096  # bytes of a line, from its aligned base, that the parse pass keeps in LDS
+ROUND = 1024  # bytes a wave reads per round of the tab pass
+HEAD9 = ('#CHROM', 'POS', 'ID', 'REF', 'ALT', 'QUAL', 'FILTER', 'INFO', 'FORMAT')
+UPPER = 'ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789'
+
+
+class Text(object):
+    """a text grown line by line with its length at hand, so that a '##' line
+    of the right length puts the next line at a chosen offset mod 16.  Such a
+    line ends in TAB and one byte, as the data lines of phases() do."""
+
+    def __init__(self, names, head=('##fileformat=VCFv4.2',)):
+        self.lines, self.n = [], 0
+        for line in head:
+            self.add(line)
+        self.add(list(HEAD9) + list(names))
+
+    def add(self, line):
+        if not isinstance(line, str):
+            line = '\t'.join(line)
+        self.lines.append(line)
+        self.n += len(line) + 1
+
+    def phase(self, p):
+        k = (p - self.n) % 16
+        if k:
+            k += 16 if k < 5 else 0
+            self.add('##' + 'p' * (k - 5) + '\tp')
+
+    def text(self, final=True):
+        return '\n'.join(self.lines) + ('\n' if final else '')
+
+
+def data_layout(text):
+    """[(offset of the line in the text, its fields, where each field starts in
+    the line)] per data line"""
+    out, at = [], 0
+    for _, line in split_lines(text):
+        if line and line[0] != '#':
+            f, col = line.split('\t'), [0]
+            for x in f[:-1]:
+                col.append(col[-1] + len(x) + 1)
+            out.append((at, f, col))
+        at += len(line) + 1
+    return out
+
+
+def first_decline(text):
+    """(reason, 1-based line) of the first data line outside the line grammar,
+    or None"""
+    lines = split_lines(text)
+    head = [k for k, ln in lines if ln[:1] == '#' and ln[:2] != '##']
+    n_samples = len(lines[head[0]][1].split('\t')) - 9
+    for k, ln in lines:
+        if ln and ln[0] != '#':
+            why = _line_reason(ln.split('\t'), n_samples)
+            if why:
+                return why, k + 1
+    return None
+
+
+def _padded(fields, k, offset):
+    """``fields`` with the ID filled so that field k starts at ``offset`` of
+    the line"""
+    f = list(fields)
+    f[2] = ''
+    at = sum(len(x) + 1 for x in f[:k])
+    assert k > 2 and offset - at >= 1
+    f[2] = 'i' * (offset - at)
+    return f
+
+
+# (a) every start phase with every content length mod 16 ----------------------
+
+def phases(seed=20261020):
+    """(text, loci), S = 2: a data line for every (start mod 16, length mod 16).
+    CHROM and the last column are one byte, so that a neighbour's TAB lies
+    within 3 bytes of both ends of a line.  A line follows the line before it
+    wherever a class of its phase is still open; a '##' line moves on else."""
+    rnd = random.Random(seed)
+    b = Text(['a', 'b'])
+    todo = {p: list(range(16)) for p in range(16)}
+    for p in range(16):
+        rnd.shuffle(todo[p])
+    chrom = 'c'
+    while any(todo.values()):
+        if not todo[b.n % 16]:
+            b.phase(max(range(16), key=lambda p: (len(todo[p]), -p)))
+        q = todo[b.n % 16].pop()
+        if rnd.random() < 0.1:
+            chrom = 'cd'[chrom == 'c']
+        f = [chrom, str(rnd.randint(10, 40)), 'i', 'A', 'C', '.', '.', '.', 'GT',
+             rnd.choice(('0/1', '1/1', '0|1', '1/0', './.')), rnd.choice('01')]
+        f[2] = 'i' * (1 + (q - len('\t'.join(f))) % 16)
+        b.add(f)
+    return b.text(), ['c,0,25', 'c,100', 'd,100', 'd,20,60', 'c,26,40']
+
+
+# (b) the round seams of the tab pass and the stage seam ------------------------
+
+SEAM_TABS = (ROUND - 1, ROUND, 2 * ROUND - 1, 2 * ROUND, STAGE - 1, STAGE)
+SEAM_TAB_FIELDS = (8, 9, 11)  # FORMAT, the first and the last sample column
+STRADDLERS = {'format': 'DP:GT', 'het': '5:0/1', 'hom': '5:1/1', 'ten': '7:10/1', 'equal': '5:0/1'}
+
+
+def seams(skew, seed=20261020):
+    """(text, loci), S = 3, every data line at ``skew`` mod 16: a TAB before
+    each of SEAM_TAB_FIELDS at each aligned offset of SEAM_TABS; each of
+    STRADDLERS with 0 .. all of its bytes before aligned offset STAGE
+    ('equal': the last column, equal to an earlier one inside the stage); one
+    line whose tabs spread over four rounds."""
+    rnd = random.Random(seed * 31 + skew)
+    b = Text(['s0', 's1', 's2'])
+
+    def put(fields, k, aligned):
+        b.phase(skew)
+        fields[0], fields[1] = rnd.choice('cd'), str(rnd.randint(1, 200))
+        b.add(_padded(fields, k, aligned - skew))
+
+    def plain():
+        calls = ['%s:%d' % (rnd.choice(_GTS), 10 + s) for s in range(3)]
+        if rnd.random() < 0.3:
+            calls[2] = calls[0]
+        return ['', '', '', 'A', 'C', '.', '.', 'DP=9', 'GT:DP'] + calls
+
+    for k in SEAM_TAB_FIELDS:
+        for tab in SEAM_TABS:
+            put(plain(), k, tab + 1)
+    for kind in sorted(STRADDLERS):
+        v = STRADDLERS[kind]
+        for before in range(len(v) + 1):
+            f = ['', '', '', 'A', 'C', '.', '.', 'DP=9', 'DP:GT']
+            if kind == 'format':
+                f, k = f + ['5:0/1', '6:1/1', '7:1|0'], 8
+            elif kind == 'equal':
+                k = 11
+                f += ['5:0/1', '6:1/1', v] if before % 2 else ['6:1/1', '5:0/1', v]
+            else:
+                k = 9 + before % 3
+                others = [c for c in ('5:0/1', '6:1/1', '7:1|0', '8:0|1') if c[0] != v[0]][:2]
+                f += others[:k - 9] + [v] + others[k - 9:]
+            put(f, k, STAGE - before)
+    b.phase(skew)
+    b.add(['c', '77', 'r' * (1100 + 7 * skew), '', '', '', '', 'L=' + 'x' * 1100,
+           'GT:' + 'Q' * 1000, '0/1', '1/1', '0/1'])
+    return b.text(), ['c,0,100', 'c,300', 'd,300', 'd,101,200']
+
+
+# (c) CHROM against the data line before ---------------------------------------
+
+CHROM_LENGTHS = (1, 2, 15, 16, 17, 62, 63, 64, 65, 66, 127, 128, 200, 5000)
+CHROM_PAIRS = (62, 63, 64)  # the byte at which two CHROMs of 70 bytes differ
+CHROM_SEAM = tuple(range(4085, 4101))
+CHROM_SEAM_SKEWS = (0, 9)
+CHROM_SEAM_TWICE = (4095, 4096, 4097, 4100)
+
+
+def chroms(seed=20261020):
+    """(text, loci), S = 1.  Per L of CHROM_LENGTHS, with X of L bytes, eight
+    data lines in a row: X, X, X with its last byte changed, X with its first
+    byte changed, X + 'z', X, 'c' (a line of 22 bytes), X; POS 7, 8, 7, 7, 7, 7,
+    9, 8, so that two keys of X come again in a later run.  Then CHROM_PAIRS, two
+    lines with an empty CHROM, a '##' line and a blank line inside a run, and
+    CHROMs of CHROM_SEAM bytes at CHROM_SEAM_SKEWS."""
+    rnd = random.Random(seed)
+    b = Text(['s0'])
+    seen = []
+
+    def line(chrom, pos):
+        if chrom not in seen:
+            seen.append(chrom)
+        b.add([chrom, str(pos), '.', 'A', 'C', '.', '.', '.', 'GT', rnd.choice(('0/1', '1/1', '1|0'))])
+
+    def name(n):
+        return ''.join(rnd.choice(UPPER) for _ in range(n))
+
+    def other(ch):
+        return 'B' if ch == 'A' else 'A'
+
+    for n in CHROM_LENGTHS:
+        x = name(n)
+        for chrom, pos in ((x, 7), (x, 8), (x[:-1] + other(x[-1]), 7), (other(x[0]) + x[1:], 7),
+                           (x + 'z', 7), (x, 7), ('c', 9), (x, 8)):
+            line(chrom, pos)
+    for at in CHROM_PAIRS:
+        y = name(70)
+        z = y[:at] + other(y[at]) + y[at + 1:]
+        for chrom, pos in ((y, 5), (z, 5), (z, 6), (y, 5)):
+            line(chrom, pos)
+    line('', 5)
+    line('', 6)
+    x = name(40)
+    line(x, 5)
+    b.add('##note=inside a run')
+    b.add('')
+    line(x, 6)
+    for skew in CHROM_SEAM_SKEWS:
+        for n in CHROM_SEAM:
+            x = name(n)
+            b.phase(skew)
+            line(x, 12345)
+            if n in CHROM_SEAM_TWICE:
+                line(x, 12345 + skew)
+    loci = [('%s,0,7' if k % 3 == 0 else '%s,50' if k % 3 == 1 else '%s,8,20000') % c
+            for k, c in enumerate(seen)]
+    return b.text(), loci + ['%s,8,8' % seen[0]]
+
+
+# (d) the field table's probing -------------------------------------------------
+# fnv1a and table_slots restate vcf.hip's hash (FNV-1a, 2166136261 and
+# 16777619) and vcf_slots, only to steer columns into chosen home slots: no
+# expectation comes from them.  If the kernel's hash ever changes, the texts
+# stay valid and the tables stay right, but what test_vcf_edges_expect.py
+# asserts about these builders' chains must be derived again.
+
+def fnv1a(s):
+    h = 2166136261
+    for c in s.encode('latin-1'):
+        h = ((h ^ c) * 16777619) & 0xffffffff
+    return h
+
+
+def table_slots(n_samples):
+    slots = 16
+    while slots < 2 * (9 + n_samples):
+        slots <<= 1
+    return slots
+
+
+def fnv1a_numbered(prefix, count, width=7):
+    """fnv1a of prefix + '%0*d' % (width, d) for every d below count (numpy)"""
+    import numpy as np
+    h = np.full(count, fnv1a(prefix), np.uint64)
+    d = np.arange(count, dtype=np.uint64)
+    for k in range(width - 1, -1, -1):
+        digit = (d // np.uint64(10 ** k)) % np.uint64(10) + np.uint64(48)
+        h = ((h ^ digit) * np.uint64(16777619)) & np.uint64(0xffffffff)
+    return h
+
+
+TABLE7_FIXED = ['c', '17', '.', 'A', 'C', '.', '.', '.', 'GT:DP']
+
+
+def table7(seed=20261020):
+    """(text, loci), S = 7 (16 fields, 32 slots): five distinct columns of home
+    slot 31 with the second and the fifth again behind them; seven columns on
+    the home slots of the line's own fixed fields; seven equal columns; equal
+    columns at both ends; and the first line once more, hom."""
+    rnd = random.Random(seed)
+    slots = table_slots(7)
+    het = ['0/1:%d' % d for d in range(2000)]
+    hom = ['1/1:%d' % d for d in range(2000)]
+    last = [c for c in het if fnv1a(c) & (slots - 1) == slots - 1]
+    h = rnd.sample(last, 5)
+    homes = {fnv1a(x) & (slots - 1) for x in TABLE7_FIXED}
+    shared = rnd.sample([c for c in het + hom if fnv1a(c) & (slots - 1) in homes], 7)
+    g = rnd.sample([c for c in hom if fnv1a(c) & (slots - 1) == slots - 1], 5)
+    free = rnd.sample(het, 5)
+    b = Text(['s%d' % s for s in range(7)])
+    for k, calls in enumerate((h + [h[1], h[4]], shared, ['0/1:5'] * 7, ['0|1:9'] + free + ['0|1:9'],
+                               g + [g[1], g[4]])):
+        f = list(TABLE7_FIXED)
+        f[1] = str(17 + k)
+        b.add(f + calls)
+    return b.text(), ['c,100', 'c,18,19']
+
+
+TABLE1024_LAST = 300  # distinct columns of home slot 4095
+TABLE1024_AGAIN = 220  # columns that repeat an earlier one
+
+
+def table1024(seed=20261020):
+    """(text, loci), S = 1024 (4,096 slots): between two plain lines one line
+    with TABLE1024_LAST distinct columns of home slot 4095, het and hom, and
+    TABLE1024_AGAIN columns that repeat an earlier column, both spread over the
+    whole line."""
+    import numpy as np
+    rnd = random.Random(seed)
+    n, slots = 1024, table_slots(1024)
+    last = []
+    for prefix in ('0/1:', '1/1:'):
+        hit = np.flatnonzero(fnv1a_numbered(prefix, 1200000) & np.uint64(slots - 1)
+                             == np.uint64(slots - 1))
+        last += ['%s%07d' % (prefix, d) for d in hit[:TABLE1024_LAST // 2].tolist()]
+    assert len(last) == TABLE1024_LAST
+    where = list(range(n))
+    rnd.shuffle(where)
+    calls = ['%s:%07d' % (rnd.choice(('0|1', '1|1', '1|0')), 5000000 + s) for s in range(n)]
+    for s, c in zip(where[:TABLE1024_LAST], last):
+        calls[s] = c
+    for s in sorted(where[TABLE1024_LAST:TABLE1024_LAST + TABLE1024_AGAIN]):
+        if s:
+            calls[s] = calls[rnd.randrange(s)]
+    plain = [['%s:%d' % (('0/1', '1/1', '0|1')[(s + k) % 3], s) for s in range(n)] for k in range(2)]
+    b = Text(['n%d' % s for s in range(n)])
+    b.add(row('c', 5, *plain[0]))
+    b.add(row('c', 6, *calls))
+    b.add(row('c', 7, *plain[1]))
+    return b.text(), ['c,100', 'c,6,6']
+
+
+# (e) line kinds ---------------------------------------------------------------
+
+HEADER_COUNTS = (0, 1, 62, 63, 64, 254, 255, 256, 257, 600)
+KINDS_DATA = 200
+
+
+def kinds(n_hdr, seed=20261020):
+    """(text, loci), S = 2: n_hdr '##' lines, the '#' line, KINDS_DATA data
+    lines; a '##' or a blank line behind each of the first eight data lines,
+    a '##' line behind every 63rd and a blank line behind every 64th."""
+    rnd = random.Random(seed * 7 + n_hdr)
+    b = Text(['a', 'b'], head=['##h%d=%s' % (k, 'x' * rnd.randint(0, 30)) for k in range(n_hdr)])
+    for d in range(KINDS_DATA):
+        b.add(row('c' if d < 120 else 'd', rnd.randint(0, 150),
+                  *['%s:%d' % (rnd.choice(_GTS), 3 + s) for s in range(2)]))
+        if d < 8:
+            b.add('' if d % 2 else '##in=%d' % d)
+        if d % 63 == 62:
+            b.add('##after=%d' % d)
+        if d % 64 == 63:
+            b.add('')
+    return b.text(), ['c,0,75', 'c,200', 'd,200', 'd,9,8']
+
+
+def _tail_line(pad, call):
+    return ['c', '9', 'i' * (1 + pad), 'A', 'C', '.', '.', '.', 'GT', call]
+
+
+def no_final_lf(m):
+    """(text, loci), S = 1: len(text) is m mod 16 and the last data line has no LF"""
+    b = Text(['s0'])
+    b.add(row('c', 5, '0/1:5'))
+    b.add(row('c', 6, '1/1:5'))
+    b.add(_tail_line((m - b.n - len('\t'.join(_tail_line(0, '0/1')))) % 16, '0/1'))
+    return b.text(final=False), ['c,100', 'c,6,9']
+
+
+def cr_cases():
+    """[(label, text with one CR, the same text with 'x' in its place)], S = 1:
+    a CR at every offset mod 16, in the middle of a text, and a CR as the last
+    byte of a text of every length mod 16"""
+    out = []
+    b = Text(['s0'])
+    b.add(row('c', 5, '0/1:5'))
+    b.add(row('c', 6, '1/1:5', id='i' * 40))
+    b.add(row('c', 7, '0/1:5'))
+    text = b.text()
+    first = text.index('i' * 40)
+    for p in range(16):
+        at = first + (p - first) % 16
+        assert text[at] == 'i'
+        out.append(('at_%d' % p, text[:at] + '\r' + text[at + 1:], text[:at] + 'x' + text[at + 1:]))
+    for m in range(16):
+        text = no_final_lf((m - 1) % 16)[0]
+        out.append(('last_%d' % m, text + '\r', text + 'x'))
+    return out
+
+
+CR_LOCI = ['c,100', 'c,6,9']
+
+
+# (f) the sort and the counts ----------------------------------------------------
+
+SORT_CHROMS = ('ctgA', 'ctgB', 'ctgC')
+ID_SETS = ((0, 0, 0), (0, 1, 1), (1, 2, 3), (3, 4, 0), (255, 256, 1), (65535, 65536, 7),
+           (INT_MAX, INT_MAX + 1, 0), (0, 2 ** 32 - 2, 2 ** 32 - 1))
+LOCI_COUNTS = (1, 255, 256, 257, 1000)
+
+
+def sort_text(seed=20261020):
+    """a text of 257 data lines, S = 3, runs of three CHROMs; POS 0, 77 and
+    INT_MAX on every CHROM more than once, the other POS from a small range,
+    so that keys repeat within a CHROM and POS repeat across CHROMs"""
+    rnd = random.Random(seed)
+    b = Text(['s0', 's1', 's2'])
+    chrom = 'ctgA'
+    for d in range(257):
+        if d < 18:
+            chrom, pos = SORT_CHROMS[d % 3], (0, 77, INT_MAX)[d // 3 % 3]
+        else:
+            if rnd.random() < 0.15:
+                chrom = rnd.choice(SORT_CHROMS)
+            pos = rnd.choice((0, 77, INT_MAX)) if rnd.random() < 0.1 else rnd.randint(1, 60)
+        b.add(row(chrom, pos, *['%s:%d' % (rnd.choice(_GTS), 3 + s) for s in range(3)]))
+    return b.text()
+
+
+def sort_loci():
+    """per CHROM: the whole contig, one repeated key, INT_MAX and above, nothing"""
+    loci = []
+    for c in SORT_CHROMS:
+        loci += ['%s,9' % c, '%s,77,77' % c, '%s,%d,%d' % (c, INT_MAX, 2 ** 32 - 1), '%s,5,4' % c,
+                 '%s,0,0' % c]
+    return loci
+
+
+def many_loci(n, seed=20261020):
+    """n loci for sort_text(): one that holds lines, its duplicate, then 58
+    that hold none; the last three hold none"""
+    rnd = random.Random(seed + n)
+    loci = []
+    for k in range(n):
+        if k % 60 == 0:
+            lo = rnd.randint(0, 40)
+            loci.append('%s,%d,%d' % (rnd.choice(SORT_CHROMS), lo, lo + rnd.randint(0, 30)))
+        elif k % 60 == 1:
+            loci.append(loci[-1])
+        else:
+            loci.append('%s,%d,%d' % (rnd.choice(SORT_CHROMS), 61 + k % 9, 60 + k % 9))
+    if n > 3:
+        loci[-3:] = ['ctgC,70,60', 'ctgA,5,4', 'ctgA,5,4']
+    return loci
+
+
+def piece_counts(split):
+    return [split - 1, split, split + 1, 2 * split, 2 * split + 1]
+
+
+def pieces(n, split, seed=20261020):
+    """(text, loci), S = 2, one CHROM, n data lines.  Sorted row i has POS
+    10 + 2 i, but a row takes the POS of the row before it at a piece edge --
+    row ``split`` (the whole contig's pieces), or with 2 split + 1 lines rows
+    split + 1 (the pieces of the locus from the second row on) and 2 split --
+    and at every 500th row.  The lines stand in a seeded order."""
+    rnd = random.Random(seed + n)
+    pos = [10 + 2 * i for i in range(n)]
+    again = set(range(250, n, 500))
+    again |= {split + 1, 2 * split} if n == 2 * split + 1 else {split}
+    for i in sorted(again):
+        if 1 < i < n:
+            pos[i] = pos[i - 1]
+    order = list(range(n))
+    rnd.shuffle(order)
+    b = Text(['a', 'b'])
+    for i in order:
+        b.add(['c', str(pos[i]), '.', 'A', 'C', '.', '.', '.', 'GT', rnd.choice(('0/1', '1/1', '0|1')),
+               rnd.choice(('0/1', '1/1'))])
+    return b.text(), ['c,9', 'c,%d,%d' % (pos[1], 2 ** 32 - 1)]
+
+
+# (g) what one workgroup leaves behind for its next line -------------------------
+
+def alternating():
+    """(text, loci), S = 5: four kinds of line five times over: above 8 KB with
+    five equal columns, 38 bytes with five distinct ones, above 8 KB with five
+    distinct ones, 38 bytes with five equal ones"""
+    b = Text(['s%d' % s for s in range(5)])
+    apart, equal = ['0/1', '1/1', '0|1', '1|1', '1/2'], ['1/2'] * 5
+    for k in range(5):
+        for long, calls in ((True, equal), (False, apart), (True, apart), (False, equal)):
+            b.add(['c', str(4 * k + long + 2 * (calls is equal)), '.', 'A', 'C', '.', '.',
+                   'L=' + 'x' * 8200 if long else '.', 'GT'] + calls)
+    return b.text(), ['c,100', 'c,3,11']
+
+
+DECLINES = {
+    'few_tabs': ('field_count', row('c', 5, '0/1:5')),
+    'many_tabs': ('field_count', row('c', 5, '0/1:5', '0/0:6', '1/1:7')),
+    'chrom_form': ('chrom_form', row('c<:>1', 5, '0/1:5', '0/0:6')),
+    'pos_form': ('pos_form', row('c', '05', '0/1:5', '0/0:6')),
+    'pos_range': ('pos_range', row('c', 1 << 31, '0/1:5', '0/0:6')),
+    'no_gt': ('no_gt', row('c', 5, '5', '6', fmt='DP')),
+    'empty_gt': ('empty_gt', row('c', 5, '0/1:5', ':6')),
+    'equals_fixed': ('equals_fixed', row('c', 5, '.', '0/1', id='.', fmt='GT')),
+}
+
+
+def decline_texts():
+    """[(label, text, reason, 1-based line)], S = 2, 40 data lines: each of
+    DECLINES as the first, the 21st and the last data line, and two texts with
+    two offending lines of different reasons"""
+    def text_with(bad):
+        b = Text(['a', 'b'])
+        at = {}
+        for d in range(40):
+            at[d] = len(b.lines) + 1
+            b.add(bad[d] if d in bad else row('c', 100 + d, '0/1:5', '1/1:%d' % d))
+        return b.text(), at
+
+    out = []
+    for name in sorted(DECLINES):
+        reason, line = DECLINES[name]
+        for d in (0, 20, 39):
+            text, at = text_with({d: line})
+            out.append(('%s_%d' % (name, d), text, reason, at[d]))
+    for a, z in (('pos_form', 'empty_gt'), ('empty_gt', 'pos_form')):
+        text, at = text_with({10: DECLINES[a][1], 30: DECLINES[z][1]})
+        out.append(('%s_then_%s' % (a, z), text, DECLINES[a][0], at[10]))
+    return out
