@@ -23,10 +23,6 @@ inline hipError_t to_device(void* dev, const void* host, uint64_t n, hipStream_t
 inline hipError_t to_host(void* host, const void* dev, uint64_t n, hipStream_t s) {
   return n ? hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, s) : hipSuccess;
 }
-template <class T>
-T* at(char* mem, uint64_t off) {
-  return reinterpret_cast<T*>(mem + off);
-}
 }
 
 void set_error(const std::string& msg) { g_last_error = msg; }
@@ -162,24 +158,20 @@ int magot_debug_text_index(magot_ctx* ctx, const uint8_t* text, uint64_t len, ui
   ix.byte2 = second ? (uint32_t)second_byte : kTextNoByte;
   const size_t tmp_bytes = exclusive_sum_bytes<uint64_t>(ix.n_blocks + 1);
   Carve cv;
-  const uint64_t o_text = cv.take<uint8_t>(len + kTextPad);
-  uint64_t o_blk[4];  // blk, pre, blk2, pre2
-  for (uint64_t& o : o_blk) o = cv.take<uint64_t>(ix.n_blocks + 1);
-  const uint64_t o_tmp = cv.take<uint8_t>(tmp_bytes);
+  uint8_t* d_text;  // uploaded into; the index reads it as const
+  void* tmp;
+  cv.take(&d_text, len + kTextPad);
+  for (uint64_t** f : {&ix.blk, &ix.pre, &ix.blk2, &ix.pre2}) cv.take(f, ix.n_blocks + 1);
+  cv.take(&tmp, tmp_bytes);
   // at most one occurrence per byte; room for every byte a lane loads, so that an
   // index that counted behind the text's end would be a wrong answer, not a wild store
-  const uint64_t o_pos = cv.take<uint64_t>(len + kTextPad);
+  cv.take(&ix.pos, len + kTextPad);
   DevBuf buf;
   MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
-  char* base = static_cast<char*>(buf.p);
-  ix.text = reinterpret_cast<const uint8_t*>(base + o_text);
-  ix.blk = reinterpret_cast<uint64_t*>(base + o_blk[0]);
-  ix.pre = reinterpret_cast<uint64_t*>(base + o_blk[1]);
-  ix.blk2 = reinterpret_cast<uint64_t*>(base + o_blk[2]);
-  ix.pre2 = reinterpret_cast<uint64_t*>(base + o_blk[3]);
-  ix.pos = reinterpret_cast<uint64_t*>(base + o_pos);
-  if (len) MAGOT_HIP_TRY(hipMemcpyAsync(base + o_text, text, len, hipMemcpyHostToDevice, s));
-  MAGOT_HIP_TRY(launch_text_count(ix, base + o_tmp, tmp_bytes, s));
+  cv.place(buf.p);
+  ix.text = d_text;
+  if (len) MAGOT_HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(launch_text_count(ix, tmp, tmp_bytes, s));
   MAGOT_HIP_TRY(launch_text_fill(ix, kTextFillPlain, s));
   uint64_t total = 0, total2 = 0;
   MAGOT_HIP_TRY(hipMemcpyAsync(&total, ix.pre + ix.n_blocks, 8, hipMemcpyDeviceToHost, s));
@@ -217,24 +209,22 @@ int magot_debug_text_lines(magot_ctx* ctx, const uint8_t* text, uint64_t len, ui
   ix.stray_reason = stray_reason;
   const size_t tmp_bytes = exclusive_sum_bytes<uint64_t>(ix.n_blocks + 1);
   Carve cv;
-  const uint64_t o_text = cv.take<uint8_t>(len + kTextPad);
-  const uint64_t o_blk = cv.take<uint64_t>(ix.n_blocks + 1);
-  const uint64_t o_pre = cv.take<uint64_t>(ix.n_blocks + 1);
-  const uint64_t o_tmp = cv.take<uint8_t>(tmp_bytes);
-  const uint64_t o_status = cv.take<unsigned long long>(1);
+  uint8_t* d_text;  // uploaded into; the index reads it as const
+  void* tmp;
+  cv.take(&d_text, len + kTextPad);
+  cv.take(&ix.blk, ix.n_blocks + 1);
+  cv.take(&ix.pre, ix.n_blocks + 1);
+  cv.take(&tmp, tmp_bytes);
+  cv.take(&ix.stray_status, 1);
   // a line start per byte and the two end entries; room for every byte a lane loads
-  const uint64_t o_pos = cv.take<uint64_t>(len + kTextPad + 2);
+  cv.take(&ix.pos, len + kTextPad + 2);
   DevBuf buf;
   MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
-  char* base = static_cast<char*>(buf.p);
-  ix.text = reinterpret_cast<const uint8_t*>(base + o_text);
-  ix.blk = reinterpret_cast<uint64_t*>(base + o_blk);
-  ix.pre = reinterpret_cast<uint64_t*>(base + o_pre);
-  ix.pos = reinterpret_cast<uint64_t*>(base + o_pos);
-  ix.stray_status = reinterpret_cast<unsigned long long*>(base + o_status);
-  if (len) MAGOT_HIP_TRY(hipMemcpyAsync(base + o_text, text, len, hipMemcpyHostToDevice, s));
+  cv.place(buf.p);
+  ix.text = d_text;
+  if (len) MAGOT_HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, s));
   MAGOT_HIP_TRY(hipMemsetAsync(ix.stray_status, 0xff, sizeof(unsigned long long), s));
-  MAGOT_HIP_TRY(launch_text_count(ix, base + o_tmp, tmp_bytes, s));
+  MAGOT_HIP_TRY(launch_text_count(ix, tmp, tmp_bytes, s));
   uint64_t total = 0;
   MAGOT_HIP_TRY(hipMemcpyAsync(&total, ix.pre + ix.n_blocks, 8, hipMemcpyDeviceToHost, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
@@ -274,24 +264,24 @@ int magot_debug_piece_copy(magot_ctx* ctx, const uint8_t* base, uint64_t base_le
     }
   hipStream_t s = ctx->stream;
   Carve cv;
-  const uint64_t o_base = cv.take<uint8_t>(((base_len + 15) & ~15ull) + kTextPad);
-  const uint64_t o_out = cv.take<uint8_t>(out_len);
-  const uint64_t o_src = cv.take<uint64_t>(n), o_dst = cv.take<uint64_t>(n);
-  const uint64_t o_len = cv.take<uint32_t>(n);
+  uint8_t *d_base, *d_out;
+  uint64_t *d_src, *d_dst;
+  uint32_t* d_len;
+  cv.take(&d_base, ((base_len + 15) & ~15ull) + kTextPad);
+  cv.take(&d_out, out_len);
+  cv.take(&d_src, n);
+  cv.take(&d_dst, n);
+  cv.take(&d_len, n);
   DevBuf buf;
   MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
-  char* mem = static_cast<char*>(buf.p);
-  MAGOT_HIP_TRY(to_device(mem + o_base, base, base_len, s));
-  MAGOT_HIP_TRY(to_device(mem + o_out, out, out_len, s));
-  MAGOT_HIP_TRY(to_device(mem + o_src, src, n * 8, s));
-  MAGOT_HIP_TRY(to_device(mem + o_dst, dst, n * 8, s));
-  MAGOT_HIP_TRY(to_device(mem + o_len, len, n * 4, s));
-  if (n)
-    MAGOT_HIP_TRY(launch_piece_copy<16>(
-        at<const uint64_t>(mem, o_src), at<const uint64_t>(mem, o_dst),
-        at<const uint32_t>(mem, o_len), n, at<const uint8_t>(mem, o_base),
-        at<uint8_t>(mem, o_out), s));
-  MAGOT_HIP_TRY(to_host(out, mem + o_out, out_len, s));
+  cv.place(buf.p);
+  MAGOT_HIP_TRY(to_device(d_base, base, base_len, s));
+  MAGOT_HIP_TRY(to_device(d_out, out, out_len, s));
+  MAGOT_HIP_TRY(to_device(d_src, src, n * 8, s));
+  MAGOT_HIP_TRY(to_device(d_dst, dst, n * 8, s));
+  MAGOT_HIP_TRY(to_device(d_len, len, n * 4, s));
+  if (n) MAGOT_HIP_TRY(launch_piece_copy<16>(d_src, d_dst, d_len, n, d_base, d_out, s));
+  MAGOT_HIP_TRY(to_host(out, d_out, out_len, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
   return MAGOT_OK;
 }
@@ -340,29 +330,31 @@ int magot_debug_text_assembly(magot_ctx* ctx, const magot_text_unit* units, uint
   hipStream_t s = ctx->stream;
   const size_t scan_bytes = text_scan_bytes(n);
   Carve cv;
-  const uint64_t o_units = cv.take<TextUnit>(n);
-  const uint64_t o_rspan = cv.take<uint64_t>(2 * n_rec);
-  const uint64_t o_text = cv.take<uint8_t>(((text_len + 15) & ~15ull) + kTextPad);
-  const uint64_t o_pay = cv.take<uint8_t>(((pay_len + 15) & ~15ull) + kTextPad);
-  const uint64_t o_len = cv.take<uint64_t>(n), o_psrc = cv.take<uint64_t>(n);
-  const uint64_t o_end = cv.take<uint64_t>(n);
-  const uint64_t o_tmp = cv.take<uint8_t>(scan_bytes);
-  const uint64_t o_out = cv.take<uint8_t>(out_len);
+  TextUnit* d_units;
+  uint64_t *d_rspan, *d_len, *d_psrc, *d_end;
+  uint8_t *d_text, *d_pay, *d_out;
+  void* tmp;
+  cv.take(&d_units, n);
+  cv.take(&d_rspan, 2 * n_rec);
+  cv.take(&d_text, ((text_len + 15) & ~15ull) + kTextPad);
+  cv.take(&d_pay, ((pay_len + 15) & ~15ull) + kTextPad);
+  cv.take(&d_len, n);
+  cv.take(&d_psrc, n);
+  cv.take(&d_end, n);
+  cv.take(&tmp, scan_bytes);
+  cv.take(&d_out, out_len);
   DevBuf buf;
   MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
-  char* mem = static_cast<char*>(buf.p);
-  MAGOT_HIP_TRY(to_device(mem + o_units, units, n * sizeof(TextUnit), s));
-  MAGOT_HIP_TRY(to_device(mem + o_rspan, rspan, 2 * n_rec * 8, s));
-  MAGOT_HIP_TRY(to_device(mem + o_text, text, text_len, s));
-  MAGOT_HIP_TRY(to_device(mem + o_pay, pay, pay_len, s));
-  MAGOT_HIP_TRY(to_device(mem + o_out, out, out_len, s));
-  launch_text_assembly(at<const TextUnit>(mem, o_units), n, at<const uint64_t>(mem, o_rspan),
-                       at<const uint8_t>(mem, o_pay), protein, at<const uint8_t>(mem, o_text),
-                       at<uint64_t>(mem, o_len), at<uint64_t>(mem, o_psrc),
-                       at<uint64_t>(mem, o_end), mem + o_tmp, scan_bytes,
-                       at<uint8_t>(mem, o_out), s);
+  cv.place(buf.p);
+  MAGOT_HIP_TRY(to_device(d_units, units, n * sizeof(TextUnit), s));
+  MAGOT_HIP_TRY(to_device(d_rspan, rspan, 2 * n_rec * 8, s));
+  MAGOT_HIP_TRY(to_device(d_text, text, text_len, s));
+  MAGOT_HIP_TRY(to_device(d_pay, pay, pay_len, s));
+  MAGOT_HIP_TRY(to_device(d_out, out, out_len, s));
+  launch_text_assembly(d_units, n, d_rspan, d_pay, protein, d_text, d_len, d_psrc, d_end, tmp,
+                       scan_bytes, d_out, s);
   MAGOT_HIP_TRY(hipGetLastError());
-  MAGOT_HIP_TRY(to_host(out, mem + o_out, out_len, s));
+  MAGOT_HIP_TRY(to_host(out, d_out, out_len, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
   *written = total;
   return MAGOT_OK;

@@ -24,23 +24,8 @@ namespace {
 
 constexpr int kFaPasses = 7;
 
-int fa_decline(uint32_t* reason, uint64_t* line, uint32_t why, uint64_t at) {
-  if (reason) *reason = why;
-  if (line) *line = at;
-  set_error("magot_fastarec_parse: input outside the device path; use the host loop");
-  return MAGOT_ERR_UNSUPPORTED;
-}
-
-template <class T>
-int fa_fetch(T* dst, const T* src, uint64_t n) {
-  if (dst && n) MAGOT_HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
-  return MAGOT_OK;
-}
-
-template <class T>
-T* at(char* base, uint64_t off) {
-  return reinterpret_cast<T*>(base + off);
-}
+constexpr char kOutside[] =
+    "magot_fastarec_parse: input outside the device path; use the host loop";
 
 // The plan of a render: the records on the device, every printed record's
 // place and pieces, the output buffer.  Replaces the handle's last one.
@@ -61,47 +46,45 @@ int fa_plan_render(magot_fastarec* p, const uint32_t* rec, uint64_t n, uint32_t 
   }
   DevBuf plan;
   Carve cv;
-  const uint64_t o_recs = cv.take<uint32_t>(n);
-  const uint64_t o_olen = cv.take<uint64_t>(n + 1), o_obase = cv.take<uint64_t>(n + 1);
-  const uint64_t o_pcnt = cv.take<uint64_t>(n + 1), o_pbase = cv.take<uint64_t>(n + 1);
+  uint32_t* d_recs;  // uploaded into; the kernels read it as const
+  void* tmp;
+  cv.take(&d_recs, n);
+  cv.take(&r.olen, n + 1);
+  cv.take(&r.obase, n + 1);
+  cv.take(&r.pcnt, n + 1);
+  cv.take(&r.pbase, n + 1);
   size_t tmp_bytes = fa_tmp_bytes(n);
-  const uint64_t o_tmp = cv.take<uint8_t>(tmp_bytes);
+  cv.take(&tmp, tmp_bytes);
   MAGOT_HIP_TRY(hipMalloc(&plan.p, cv.used + 256));
-  char* base = static_cast<char*>(plan.p);
-  MAGOT_HIP_TRY(hipMemcpyAsync(base + o_recs, rec, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  r.recs = at<uint32_t>(base, o_recs);
-  r.olen = at<uint64_t>(base, o_olen);
-  r.obase = at<uint64_t>(base, o_obase);
-  r.pcnt = at<uint64_t>(base, o_pcnt);
-  r.pbase = at<uint64_t>(base, o_pbase);
-  MAGOT_HIP_TRY(launch_fa_render_sizes(a, r, base + o_tmp, tmp_bytes, s));
+  cv.place(plan.p);
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_recs, rec, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  r.recs = d_recs;
+  MAGOT_HIP_TRY(launch_fa_render_sizes(a, r, tmp, tmp_bytes, s));
   uint64_t total = 0, pieces = 0;
   MAGOT_HIP_TRY(hipMemcpyAsync(&total, r.obase + n, 8, hipMemcpyDeviceToHost, s));
   MAGOT_HIP_TRY(hipMemcpyAsync(&pieces, r.pbase + n, 8, hipMemcpyDeviceToHost, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
   // the tables the kernels keep reading, and the text, in one allocation
   Carve co;
-  const uint64_t q_out = co.take<uint8_t>(total + 16);
-  const uint64_t q_recs = co.take<uint32_t>(n);
-  const uint64_t q_obase = co.take<uint64_t>(n + 1), q_pbase = co.take<uint64_t>(n + 1);
-  const uint64_t q_src = co.take<uint64_t>(pieces), q_dst = co.take<uint64_t>(pieces);
-  const uint64_t q_len = co.take<uint32_t>(pieces);
+  uint64_t *q_obase, *q_pbase;  // recs, obase and pbase move over from the plan
+  co.take(&r.out, total + 16);
+  co.take(&d_recs, n);
+  co.take(&q_obase, n + 1);
+  co.take(&q_pbase, n + 1);
+  co.take(&r.p_src, pieces);
+  co.take(&r.p_dst, pieces);
+  co.take(&r.p_len, pieces);
   MAGOT_HIP_TRY(hipMalloc(&p->out_mem, co.used + 256));
-  char* ob = static_cast<char*>(p->out_mem);
-  MAGOT_HIP_TRY(hipMemcpyAsync(ob + q_recs, r.recs, n * sizeof(uint32_t),
-                               hipMemcpyDeviceToDevice, s));
-  MAGOT_HIP_TRY(hipMemcpyAsync(ob + q_obase, r.obase, (n + 1) * 8, hipMemcpyDeviceToDevice, s));
-  MAGOT_HIP_TRY(hipMemcpyAsync(ob + q_pbase, r.pbase, (n + 1) * 8, hipMemcpyDeviceToDevice, s));
+  co.place(p->out_mem);
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_recs, r.recs, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(q_obase, r.obase, (n + 1) * 8, hipMemcpyDeviceToDevice, s));
+  MAGOT_HIP_TRY(hipMemcpyAsync(q_pbase, r.pbase, (n + 1) * 8, hipMemcpyDeviceToDevice, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));  // the plan's scratch goes
-  r.recs = at<uint32_t>(ob, q_recs);
+  r.recs = d_recs;
   r.olen = r.pcnt = nullptr;
-  r.obase = at<uint64_t>(ob, q_obase);
-  r.pbase = at<uint64_t>(ob, q_pbase);
+  r.obase = q_obase;
+  r.pbase = q_pbase;
   r.n_pieces = pieces;
-  r.p_src = at<uint64_t>(ob, q_src);
-  r.p_dst = at<uint64_t>(ob, q_dst);
-  r.p_len = at<uint32_t>(ob, q_len);
-  r.out = at<uint8_t>(ob, q_out);
   p->r = r;
   p->out_bytes = total;
   return MAGOT_OK;
@@ -160,46 +143,39 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
     return MAGOT_ERR_ARG;
   }
   if (int rc = resident_text_budget(&max_bytes)) return rc;
-  if (len > max_bytes) return fa_decline(reason, line, MAGOT_FASTAREC_TOO_LARGE, 0);
-  if (len && text[0] != '>') return fa_decline(reason, line, MAGOT_FASTAREC_LEADING_TEXT, 1);
+  if (len > max_bytes) return decline(kOutside, reason, line, MAGOT_FASTAREC_TOO_LARGE, 0);
+  if (len && text[0] != '>')
+    return decline(kOutside, reason, line, MAGOT_FASTAREC_LEADING_TEXT, 1);
 
-  struct Guard {
-    magot_fastarec* p;
-    ~Guard() { magot_fastarec_destroy(p); }
-  } guard{new magot_fastarec()};
+  Building<magot_fastarec, magot_fastarec_destroy> guard{new magot_fastarec()};
   magot_fastarec* p = guard.p;
   p->ctx = ctx;
   FaArgs& a = p->a;
   a.hash_bits = hash_bits;
   hipStream_t s = ctx->stream;
   if (len) {
-    if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte, sizeof(unsigned long long),
-                                    &p->rt, &a.ix))
+    Carve cv;  // the caller's slice: the status word
+    cv.take(&a.status, 1);
+    if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte, cv.used, &p->rt, &a.ix))
       return rc;
-    a.status = a.ix.stray_status = reinterpret_cast<unsigned long long*>(p->rt.extra);
+    cv.place(p->rt.extra);
+    a.ix.stray_status = a.status;
     a.ix.stray_reason = MAGOT_FASTAREC_STRAY_CR;
     MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
     a.ix.n_lines = p->rt.n_lines;
-    if (a.ix.n_lines > kFaMaxLines) return fa_decline(reason, line, MAGOT_FASTAREC_TOO_MANY_LINES, 0);
+    if (a.ix.n_lines > kFaMaxLines)
+      return decline(kOutside, reason, line, MAGOT_FASTAREC_TOO_MANY_LINES, 0);
   }
   if (a.ix.n_lines) {
     const uint64_t L = a.ix.n_lines;
     p->tmp_bytes = fa_tmp_bytes(L);  // records and keys are at most the lines
     {
       Carve cv;
-      uint64_t o[7];
-      for (uint64_t& x : o) x = cv.take<uint64_t>(L + 1);
-      const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
+      for (uint64_t** f : {&a.ix.pos, &a.hdr, &a.pay, &a.pcs, &a.rec_of, &a.pay_pre, &a.pcs_pre})
+        cv.take(f, L + 1);
+      cv.take(&p->tmp, p->tmp_bytes);
       MAGOT_HIP_TRY(hipMalloc(&p->line_mem, cv.used + 256));
-      char* base = static_cast<char*>(p->line_mem);
-      a.ix.pos = at<uint64_t>(base, o[0]);
-      a.hdr = at<uint64_t>(base, o[1]);
-      a.pay = at<uint64_t>(base, o[2]);
-      a.pcs = at<uint64_t>(base, o[3]);
-      a.rec_of = at<uint64_t>(base, o[4]);
-      a.pay_pre = at<uint64_t>(base, o[5]);
-      a.pcs_pre = at<uint64_t>(base, o[6]);
-      p->tmp = base + o_tmp;
+      cv.place(p->line_mem);
     }
     MAGOT_HIP_TRY(launch_text_fill(a.ix, kTextFillLinesCr, s));
     MAGOT_HIP_TRY(launch_fa_lines(a, p->tmp, p->tmp_bytes, s));
@@ -212,43 +188,22 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
     const uint64_t N = a.n_rec;
     {
       Carve cv;
-      uint64_t o64[14], o32[10];
-      for (uint64_t& x : o64) x = cv.take<uint64_t>(N + 1);
-      for (uint64_t& x : o32) x = cv.take<uint32_t>(N + 1);
+      for (uint64_t** f : {&a.name_off, &a.word_off, &a.hash, &a.word_hash, &a.seq_len, &a.ne,
+                           &a.ne_pos, &a.skey, &a.skey_sorted, &a.head, &a.head_pos, &a.is_first,
+                           &a.kpos, &a.k_hash})
+        cv.take(f, N + 1);
+      for (uint32_t** f : {&a.hdr_line, &a.name_len, &a.word_len, &a.no_word, &a.sval,
+                           &a.sval_sorted, &a.last_of, &a.k_first, &a.k_last, &a.k_no_word})
+        cv.take(f, N + 1);
       MAGOT_HIP_TRY(hipMalloc(&p->rec_mem, cv.used + 256));
-      char* base = static_cast<char*>(p->rec_mem);
-      a.name_off = at<uint64_t>(base, o64[0]);
-      a.word_off = at<uint64_t>(base, o64[1]);
-      a.hash = at<uint64_t>(base, o64[2]);
-      a.word_hash = at<uint64_t>(base, o64[3]);
-      a.seq_len = at<uint64_t>(base, o64[4]);
-      a.ne = at<uint64_t>(base, o64[5]);
-      a.ne_pos = at<uint64_t>(base, o64[6]);
-      a.skey = at<uint64_t>(base, o64[7]);
-      a.skey_sorted = at<uint64_t>(base, o64[8]);
-      a.head = at<uint64_t>(base, o64[9]);
-      a.head_pos = at<uint64_t>(base, o64[10]);
-      a.is_first = at<uint64_t>(base, o64[11]);
-      a.kpos = at<uint64_t>(base, o64[12]);
-      a.k_hash = at<uint64_t>(base, o64[13]);
-      a.hdr_line = at<uint32_t>(base, o32[0]);
-      a.name_len = at<uint32_t>(base, o32[1]);
-      a.word_len = at<uint32_t>(base, o32[2]);
-      a.no_word = at<uint32_t>(base, o32[3]);
-      a.sval = at<uint32_t>(base, o32[4]);
-      a.sval_sorted = at<uint32_t>(base, o32[5]);
-      a.last_of = at<uint32_t>(base, o32[6]);
-      a.k_first = at<uint32_t>(base, o32[7]);
-      a.k_last = at<uint32_t>(base, o32[8]);
-      a.k_no_word = at<uint32_t>(base, o32[9]);
+      cv.place(p->rec_mem);
     }
     MAGOT_HIP_TRY(launch_fa_names(a, p->tmp, p->tmp_bytes, s));
     unsigned long long status = 0;
     MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_ne, a.ne_pos + N, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    if (status != ~0ull)
-      return fa_decline(reason, line, (uint32_t)(status & 0xff), (status >> 8) + 1);
+    if (int rc = decline_if_offended(kOutside, reason, line, status)) return rc;
     if (a.n_ne > N) {
       set_error("magot_fastarec_parse: more records with a sequence than records");
       return MAGOT_ERR_STATE;
@@ -258,8 +213,7 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
     MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_keys, a.kpos + N, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    if (status != ~0ull)
-      return fa_decline(reason, line, (uint32_t)(status & 0xff), (status >> 8) + 1);
+    if (int rc = decline_if_offended(kOutside, reason, line, status)) return rc;
     if (a.n_keys > a.n_ne) {
       set_error("magot_fastarec_parse: more keys than records with a sequence");
       return MAGOT_ERR_STATE;
@@ -267,8 +221,7 @@ int magot_fastarec_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_
     MAGOT_HIP_TRY(launch_fa_rows(a, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
   }
-  guard.p = nullptr;
-  *out = p;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -295,15 +248,15 @@ int magot_fastarec_records(magot_ctx* ctx, magot_fastarec* p, uint32_t* line, ui
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   const FaArgs& a = p->a;
   const uint64_t n = a.n_rec;
-  if (int rc = fa_fetch(line, a.hdr_line, n)) return rc;
-  if (int rc = fa_fetch(name_off, a.name_off, n)) return rc;
-  if (int rc = fa_fetch(name_len, a.name_len, n)) return rc;
-  if (int rc = fa_fetch(seq_len, a.seq_len, n)) return rc;
-  if (int rc = fa_fetch(hash, a.hash, n)) return rc;
-  if (int rc = fa_fetch(word_off, a.word_off, n)) return rc;
-  if (int rc = fa_fetch(word_len, a.word_len, n)) return rc;
-  if (int rc = fa_fetch(word_hash, a.word_hash, n)) return rc;
-  return fa_fetch(no_word, a.no_word, n);
+  if (int rc = fetch_rows(line, a.hdr_line, n)) return rc;
+  if (int rc = fetch_rows(name_off, a.name_off, n)) return rc;
+  if (int rc = fetch_rows(name_len, a.name_len, n)) return rc;
+  if (int rc = fetch_rows(seq_len, a.seq_len, n)) return rc;
+  if (int rc = fetch_rows(hash, a.hash, n)) return rc;
+  if (int rc = fetch_rows(word_off, a.word_off, n)) return rc;
+  if (int rc = fetch_rows(word_len, a.word_len, n)) return rc;
+  if (int rc = fetch_rows(word_hash, a.word_hash, n)) return rc;
+  return fetch_rows(no_word, a.no_word, n);
 }
 
 int magot_fastarec_keys(magot_ctx* ctx, magot_fastarec* p, uint64_t* hash, uint32_t* first_record,
@@ -312,10 +265,10 @@ int magot_fastarec_keys(magot_ctx* ctx, magot_fastarec* p, uint64_t* hash, uint3
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   const FaArgs& a = p->a;
   const uint64_t n = a.n_keys;
-  if (int rc = fa_fetch(hash, a.k_hash, n)) return rc;
-  if (int rc = fa_fetch(first_record, a.k_first, n)) return rc;
-  if (int rc = fa_fetch(last_record, a.k_last, n)) return rc;
-  return fa_fetch(no_word, a.k_no_word, n);
+  if (int rc = fetch_rows(hash, a.k_hash, n)) return rc;
+  if (int rc = fetch_rows(first_record, a.k_first, n)) return rc;
+  if (int rc = fetch_rows(last_record, a.k_last, n)) return rc;
+  return fetch_rows(no_word, a.k_no_word, n);
 }
 
 int magot_fastarec_exclude(magot_ctx* ctx, magot_fastarec* p, const uint8_t* blob,
@@ -339,30 +292,29 @@ int magot_fastarec_exclude(magot_ctx* ctx, magot_fastarec* p, const uint8_t* blo
   if (!a.n_keys) return MAGOT_OK;
   hipStream_t s = ctx->stream;
   DevBuf buf;
-  Carve cv;
-  const uint64_t o_blob = cv.take<uint8_t>(blob_len + 16), o_off = cv.take<uint64_t>(m + 1);
-  const uint64_t o_k = cv.take<uint64_t>(m), o_k2 = cv.take<uint64_t>(m);
-  const uint64_t o_i = cv.take<uint32_t>(m), o_i2 = cv.take<uint32_t>(m);
-  const uint64_t o_keep = cv.take<uint8_t>(a.n_keys);
-  const size_t tmp_bytes = fa_tmp_bytes(m);
-  const uint64_t o_tmp = cv.take<uint8_t>(tmp_bytes);
-  MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
-  char* base = static_cast<char*>(buf.p);
   FaMemberArgs g{};
   g.m = m;
-  g.blob = at<const uint8_t>(base, o_blob);
-  g.off = at<const uint64_t>(base, o_off);
-  g.lkey = at<uint64_t>(base, o_k);
-  g.lkey_sorted = at<uint64_t>(base, o_k2);
-  g.lidx = at<uint32_t>(base, o_i);
-  g.lidx_sorted = at<uint32_t>(base, o_i2);
   g.first_word = first_word ? 1u : 0u;
-  g.keep = at<uint8_t>(base, o_keep);
-  if (blob_len)
-    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_blob, blob, blob_len, hipMemcpyHostToDevice, s));
-  if (m)
-    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_off, off, (m + 1) * 8, hipMemcpyHostToDevice, s));
-  MAGOT_HIP_TRY(launch_fa_member(a, g, base + o_tmp, tmp_bytes, s));
+  Carve cv;
+  uint8_t* d_blob;  // uploaded into; the kernels read them as const
+  uint64_t* d_off;
+  void* tmp;
+  cv.take(&d_blob, blob_len + 16);
+  cv.take(&d_off, m + 1);
+  cv.take(&g.lkey, m);
+  cv.take(&g.lkey_sorted, m);
+  cv.take(&g.lidx, m);
+  cv.take(&g.lidx_sorted, m);
+  cv.take(&g.keep, a.n_keys);
+  const size_t tmp_bytes = fa_tmp_bytes(m);
+  cv.take(&tmp, tmp_bytes);
+  MAGOT_HIP_TRY(hipMalloc(&buf.p, cv.used + 256));
+  cv.place(buf.p);
+  g.blob = d_blob;
+  g.off = d_off;
+  if (blob_len) MAGOT_HIP_TRY(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, s));
+  if (m) MAGOT_HIP_TRY(hipMemcpyAsync(d_off, off, (m + 1) * 8, hipMemcpyHostToDevice, s));
+  MAGOT_HIP_TRY(launch_fa_member(a, g, tmp, tmp_bytes, s));
   MAGOT_HIP_TRY(hipMemcpyAsync(keep, g.keep, a.n_keys, hipMemcpyDeviceToHost, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
   return MAGOT_OK;
@@ -426,14 +378,8 @@ int magot_fastarec_time(magot_ctx* ctx, magot_fastarec* p, int iters, double* ms
     if (reflow_bytes) *reflow_bytes = p->out_bytes;
   }
   // every pass writes what it wrote in magot_fastarec_parse: the answers stand
-  double total[kFaPasses] = {0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < kFaPasses; ++k)
-      if (int rc = time_pass(ctx, &total[k],
-                             [&]() -> hipError_t { return fa_pass(p, k, ctx->stream); }))
-        return rc;
-  for (int k = 0; k < kFaPasses; ++k) ms7[k] = total[k] / iters;
-  return MAGOT_OK;
+  return time_passes(ctx, iters, kFaPasses, ms7,
+                     [&](int k) { return fa_pass(p, k, ctx->stream); });
 }
 
 }  // extern "C"

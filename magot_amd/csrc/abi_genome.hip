@@ -137,21 +137,22 @@ int load_device_packed(magot_ctx* ctx, const ContigSource* src, uint32_t n_conti
   const uint64_t groups = (n + 31) / 32;
   const size_t scan_bytes = devpack_scan_bytes(groups);
   Carve sc;
-  const uint64_t o_raw = sc.take<uint8_t>(32 * groups + 64);
-  const uint64_t o_cnt = sc.take<uint32_t>(groups + 1);
-  const uint64_t o_slot = sc.take<uint64_t>(groups + 1);
-  const uint64_t o_tmp = sc.take<uint8_t>(scan_bytes + 1);
+  uint8_t* raw;
+  uint32_t* cnt;
+  uint64_t* slot;
+  void* tmp;
+  sc.take(&raw, 32 * groups + 64);
+  sc.take(&cnt, groups + 1);
+  sc.take(&slot, groups + 1);
+  sc.take(&tmp, scan_bytes + 1);
   DevBuf scratch;
   MAGOT_HIP_TRY(hipMalloc(&scratch.p, sc.used));
-  char* sbase = static_cast<char*>(scratch.p);
-  uint8_t* raw = reinterpret_cast<uint8_t*>(sbase + o_raw);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(sbase + o_cnt);
-  uint64_t* slot = reinterpret_cast<uint64_t*>(sbase + o_slot);
+  sc.place(scratch.p);
   // the padding past n is read by the 32-byte loads (and masked)
   MAGOT_HIP_TRY(hipMemsetAsync(raw + n, 0, 32 * groups + 64 - n, ctx->stream));
   if (int rc = upload_raw(ctx, src, hp, raw)) return rc;
   lap("upload");
-  MAGOT_HIP_TRY(launch_run_count(raw, n, cnt, slot, sbase + o_tmp, scan_bytes, ctx->stream));
+  MAGOT_HIP_TRY(launch_run_count(raw, n, cnt, slot, tmp, scan_bytes, ctx->stream));
   uint64_t n_runs = 0;
   if (groups) {
     uint64_t last_slot = 0;
@@ -201,15 +202,12 @@ int load_device_packed(magot_ctx* ctx, const ContigSource* src, uint32_t n_conti
   std::unique_ptr<magot_genome> g(new magot_genome());
   g->ctx = ctx;
   Carve cv;
-  const uint64_t o_nib = cv.take<uint32_t>(2 * hp.nib_words + 4);
-  const uint64_t o_runs = cv.take<ExcRun>(hp.runs.size());
-  const uint64_t o_dir = cv.take<uint32_t>(hp.dir.size());
+  cv.take(&g->nib, 2 * hp.nib_words + 4);
+  cv.take(&g->runs, hp.runs.size());
+  cv.take(&g->dir, hp.dir.size());
   MAGOT_HIP_TRY(hipMalloc(&g->arena, cv.used));
+  cv.place(g->arena);
   g->arena_bytes = cv.used;
-  char* base = static_cast<char*>(g->arena);
-  g->nib = reinterpret_cast<uint32_t*>(base + o_nib);
-  g->runs = reinterpret_cast<ExcRun*>(base + o_runs);
-  g->dir = reinterpret_cast<uint32_t*>(base + o_dir);
   launch_nib_pack(raw, n, g->nib, hp.nib_words, ctx->stream);
   MAGOT_HIP_TRY(hipGetLastError());
   MAGOT_HIP_TRY(hipMemsetAsync(g->nib + 2 * hp.nib_words, 0, 16, ctx->stream));
@@ -263,15 +261,12 @@ int load_packed(magot_ctx* ctx, const ContigSource* src, uint32_t n_contigs, uin
   g->ctx = ctx;
   Carve cv;
   // forward + reverse-strand planes, 4 words of slack for window over-reads
-  uint64_t o_nib = cv.take<uint32_t>(2 * hp.nib_words + 4);
-  uint64_t o_runs = cv.take<ExcRun>(hp.runs.size());
-  uint64_t o_dir = cv.take<uint32_t>(hp.dir.size());
+  cv.take(&g->nib, 2 * hp.nib_words + 4);
+  cv.take(&g->runs, hp.runs.size());
+  cv.take(&g->dir, hp.dir.size());
   MAGOT_HIP_TRY(hipMalloc(&g->arena, cv.used));
+  cv.place(g->arena);
   g->arena_bytes = cv.used;
-  char* base = static_cast<char*>(g->arena);
-  g->nib = reinterpret_cast<uint32_t*>(base + o_nib);
-  g->runs = reinterpret_cast<ExcRun*>(base + o_runs);
-  g->dir = reinterpret_cast<uint32_t*>(base + o_dir);
   MAGOT_HIP_TRY(hipMemcpy(g->nib, hp.nib.get(), hp.nib_words * 4, hipMemcpyHostToDevice));
   MAGOT_HIP_TRY(hipMemset(g->nib + 2 * hp.nib_words, 0, 16));
   launch_mirror_planes(g->nib, hp.span, ctx->stream);
@@ -535,15 +530,16 @@ int magot_genome_wire_export(const magot_genome* g, void* wire_dev, uint64_t cap
   const uint64_t groups = g->span / 32;
   const size_t scan_bytes = wire_scan_bytes(groups);
   Carve sc;
-  const uint64_t o_cnt = sc.take<uint32_t>(groups + 1);
-  const uint64_t o_slot = sc.take<uint64_t>(groups + 1);
-  const uint64_t o_tmp = sc.take<uint8_t>(scan_bytes + 1);
+  uint32_t* cnt;
+  uint64_t* slot;
+  void* tmp;
+  sc.take(&cnt, groups + 1);
+  sc.take(&slot, groups + 1);
+  sc.take(&tmp, scan_bytes + 1);
   DevBuf scratch;
   MAGOT_HIP_TRY(hipMalloc(&scratch.p, sc.used));
-  char* sb = static_cast<char*>(scratch.p);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(sb + o_cnt);
-  uint64_t* slot = reinterpret_cast<uint64_t*>(sb + o_slot);
-  MAGOT_HIP_TRY(launch_wire_count(g->nib, g->span, cnt, slot, sb + o_tmp, scan_bytes, st));
+  sc.place(scratch.p);
+  MAGOT_HIP_TRY(launch_wire_count(g->nib, g->span, cnt, slot, tmp, scan_bytes, st));
   uint64_t n_mask = 0;
   if (groups) {
     uint64_t last_slot = 0;

@@ -89,17 +89,6 @@ struct magot_orf6 {
 
 namespace magot {
 
-// Sub-allocate 256-byte aligned slices of one device allocation.
-struct Carve {
-  uint64_t used = 0;
-  template <class T>
-  uint64_t take(uint64_t count) {
-    uint64_t at = used;
-    used += (count * sizeof(T) + 255) & ~255ull;
-    return at;
-  }
-};
-
 inline int bind(magot_ctx* ctx) {
   if (!ctx) {
     set_error("null context");
@@ -190,23 +179,19 @@ int resident_text_open(magot_ctx* ctx, const char* text, uint64_t len, uint32_t 
   ix->byte2 = byte2;
   rt->tmp_bytes = exclusive_sum_bytes<uint64_t>(ix->n_blocks + 1);
   Carve cv;
-  const uint64_t o_text = cv.take<uint8_t>(len + kTextPad);
-  uint64_t o_blk[4] = {0, 0, 0, 0};  // blk, pre, blk2, pre2
-  for (int k = 0; k < (second ? 4 : 2); ++k) o_blk[k] = cv.take<uint64_t>(ix->n_blocks + 1);
-  const uint64_t o_tmp = cv.take<uint8_t>(rt->tmp_bytes);
-  const uint64_t o_extra = cv.take<uint8_t>(extra_bytes);
+  uint8_t* d_text;  // uploaded into; the index reads it as const
+  cv.take(&d_text, len + kTextPad);
+  uint64_t** const blk[4] = {&ix->blk, &ix->pre, &ix->blk2, &ix->pre2};
+  ix->blk2 = ix->pre2 = nullptr;
+  for (int k = 0; k < (second ? 4 : 2); ++k) cv.take(blk[k], ix->n_blocks + 1);
+  cv.take(&rt->tmp, rt->tmp_bytes);
+  cv.take(&rt->extra, extra_bytes);
   MAGOT_HIP_TRY(hipMalloc(&rt->mem, cv.used + 256));
-  char* base = static_cast<char*>(rt->mem);
-  ix->text = reinterpret_cast<const uint8_t*>(base + o_text);
-  ix->blk = reinterpret_cast<uint64_t*>(base + o_blk[0]);
-  ix->pre = reinterpret_cast<uint64_t*>(base + o_blk[1]);
-  ix->blk2 = second ? reinterpret_cast<uint64_t*>(base + o_blk[2]) : nullptr;
-  ix->pre2 = second ? reinterpret_cast<uint64_t*>(base + o_blk[3]) : nullptr;
-  rt->tmp = base + o_tmp;
-  rt->extra = base + o_extra;
+  cv.place(rt->mem);
+  ix->text = d_text;
   MAGOT_HIP_TRY(hipEventRecord(ctx->ev0, s));
   if (len)
-    if (int rc = upload_text(ctx, text, len, reinterpret_cast<uint8_t*>(base + o_text))) return rc;
+    if (int rc = upload_text(ctx, text, len, d_text)) return rc;
   MAGOT_HIP_TRY(hipEventRecord(ctx->ev1, s));
   if (int rc = before_count(rt->extra)) return rc;
   MAGOT_HIP_TRY(launch_text_count(*ix, rt->tmp, rt->tmp_bytes, s));
@@ -282,6 +267,71 @@ int time_pass(magot_ctx* ctx, double* total_ms, F launch) {
   MAGOT_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   *total_ms += ms;
   return MAGOT_OK;
+}
+
+// The loop of the *_time entry points: `iters` rounds of the passes 0..n-1,
+// pass(k) (it returns a hipError_t) timed by time_pass; ms[k] is pass k's mean.
+// A pass that skip(k) names is not launched and reports exactly 0.
+template <class F, class S>
+int time_passes(magot_ctx* ctx, int iters, int n, double* ms, F pass, S skip) {
+  for (int k = 0; k < n; ++k) ms[k] = 0;
+  for (int i = 0; i < iters; ++i)
+    for (int k = 0; k < n; ++k)
+      if (!skip(k))
+        if (int rc = time_pass(ctx, &ms[k], [&]() -> hipError_t { return pass(k); })) return rc;
+  for (int k = 0; k < n; ++k) ms[k] /= iters;
+  return MAGOT_OK;
+}
+
+template <class F>
+int time_passes(magot_ctx* ctx, int iters, int n, double* ms, F pass) {
+  return time_passes(ctx, iters, n, ms, pass, [](int) { return false; });
+}
+
+// A handle under construction: destroyed unless released.
+template <class H, void (*Destroy)(H*)>
+struct Building {
+  H* p;
+  ~Building() { Destroy(p); }
+  H* release() {
+    H* done = p;
+    p = nullptr;
+    return done;
+  }
+};
+
+// n rows of a device table to the host; a null dst or no rows: nothing.
+template <class T>
+int fetch_rows(T* dst, const T* src, uint64_t n) {
+  if (dst && n) MAGOT_HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+  return MAGOT_OK;
+}
+
+// An input the device path does not take: `who` is the entry point's whole
+// message, *reason and *line (1-based, 0: none; either may be null) say why.
+inline int decline(const char* who, uint32_t* reason, uint64_t* line, uint32_t why, uint64_t at) {
+  if (reason) *reason = why;
+  if (line) *line = at;
+  set_error(who);
+  return MAGOT_ERR_UNSUPPORTED;
+}
+
+// The kernels' status word of the first offending line: all ones while none
+// offends, else its 0-based line << 8 | the reason.
+inline bool first_offence(unsigned long long status, uint32_t* why, uint64_t* line0) {
+  if (status == ~0ull) return false;
+  *why = (uint32_t)(status & 0xff);
+  *line0 = status >> 8;
+  return true;
+}
+
+// MAGOT_OK, or the decline that a status word names.
+inline int decline_if_offended(const char* who, uint32_t* reason, uint64_t* line,
+                               unsigned long long status) {
+  uint32_t why = 0;
+  uint64_t line0 = 0;
+  if (!first_offence(status, &why, &line0)) return MAGOT_OK;
+  return decline(who, reason, line, why, line0 + 1);
 }
 
 // Text parsed on the device in chunks (abi_text.hip): chunk k is staged in

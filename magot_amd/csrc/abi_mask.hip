@@ -72,11 +72,8 @@ int magot_mask_create(magot_ctx* ctx, const magot_plan* p, const magot_maskplan*
       set_error("magot_mask_create: an interval outside its contig");
       return MAGOT_ERR_RANGE;
     }
-  struct Guard {
-    magot_mask* m;
-    ~Guard() { magot_mask_destroy(m); }
-  } guard{new magot_mask()};
-  magot_mask* m = guard.m;
+  Building<magot_mask, magot_mask_destroy> guard{new magot_mask()};
+  magot_mask* m = guard.p;
   m->ctx = ctx;
   m->plan = p;
   MaskArgs& a = m->a;
@@ -87,17 +84,18 @@ int magot_mask_create(magot_ctx* ctx, const magot_plan* p, const magot_maskplan*
   a.cov_words = (src_bytes + 31) / 32;
   a.n_rec = n;
   a.text_bytes = at;
-  Carve cv;
-  const uint64_t o_rows = cv.take<magot_mask_interval>(a.n_rows);
-  const uint64_t o_csrc = cv.take<uint64_t>(nc);
-  const uint64_t o_tstart = cv.take<uint64_t>(n + 1);
-  const uint64_t o_rsrc = cv.take<uint64_t>(n);
-  const uint64_t o_hlen = cv.take<uint32_t>(n);
-  const uint64_t o_hoff = cv.take<uint64_t>(n);
-  const uint64_t o_hdr = cv.take<uint8_t>(hdr.size());
-  const uint64_t o_cov = cv.take<uint32_t>(a.cov_words + 1);
-  const uint64_t o_out = cv.take<uint8_t>(a.text_bytes);
+  Carve cv;  // the uploads go to the arena + offset: the kernels' fields are const
+  const uint64_t o_rows = cv.take(&a.rows, a.n_rows);
+  const uint64_t o_csrc = cv.take(&a.contig_src, nc);
+  const uint64_t o_tstart = cv.take(&a.tstart, n + 1);
+  const uint64_t o_rsrc = cv.take(&a.rsrc, n);
+  const uint64_t o_hlen = cv.take(&a.hlen, n);
+  const uint64_t o_hoff = cv.take(&a.hoff, n);
+  const uint64_t o_hdr = cv.take(&a.hdr, hdr.size());
+  cv.take(&a.cov, a.cov_words + 1);
+  cv.take(&a.out, a.text_bytes);
   MAGOT_HIP_TRY(hipMalloc(&m->arena, cv.used + 256));
+  cv.place(m->arena);
   char* base = static_cast<char*>(m->arena);
   auto up = [&](uint64_t off, const void* src, uint64_t bytes) {
     return bytes ? hipMemcpy(base + off, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
@@ -109,18 +107,8 @@ int magot_mask_create(magot_ctx* ctx, const magot_plan* p, const magot_maskplan*
   MAGOT_HIP_TRY(up(o_hlen, hlen.data(), n * 4));
   MAGOT_HIP_TRY(up(o_hoff, hoff.data(), n * 8));
   MAGOT_HIP_TRY(up(o_hdr, hdr.data(), hdr.size()));
-  a.rows = reinterpret_cast<const magot_mask_interval*>(base + o_rows);
-  a.contig_src = reinterpret_cast<const uint64_t*>(base + o_csrc);
-  a.tstart = reinterpret_cast<const uint64_t*>(base + o_tstart);
-  a.rsrc = reinterpret_cast<const uint64_t*>(base + o_rsrc);
-  a.hlen = reinterpret_cast<const uint32_t*>(base + o_hlen);
-  a.hoff = reinterpret_cast<const uint64_t*>(base + o_hoff);
-  a.hdr = reinterpret_cast<const uint8_t*>(base + o_hdr);
-  a.cov = reinterpret_cast<uint32_t*>(base + o_cov);
-  a.out = reinterpret_cast<uint8_t*>(base + o_out);
   if (text_bytes) *text_bytes = a.text_bytes;
-  guard.m = nullptr;
-  *out = m;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -180,15 +168,13 @@ int magot_mask_time(magot_ctx* ctx, magot_mask* m, int iters, double* paint_ms, 
     set_error("magot_mask_time: execute the extraction plan first");
     return MAGOT_ERR_STATE;
   }
-  double total[2] = {0, 0};
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < 2; ++k)
-      if (int rc = time_pass(ctx, &total[k], [&] {
-            return k ? launch_mask_text(m->a, ctx->stream) : launch_mask_paint(m->a, ctx->stream);
-          }))
-        return rc;
-  if (paint_ms) *paint_ms = total[0] / iters;
-  if (text_ms) *text_ms = total[1] / iters;
+  double ms[2];
+  if (int rc = time_passes(ctx, iters, 2, ms, [&](int k) {
+        return k ? launch_mask_text(m->a, ctx->stream) : launch_mask_paint(m->a, ctx->stream);
+      }))
+    return rc;
+  if (paint_ms) *paint_ms = ms[0];
+  if (text_ms) *text_ms = ms[1];
   return MAGOT_OK;
 }
 

@@ -131,28 +131,29 @@ int magot_plan_orf6(magot_ctx* ctx, magot_plan* p, const uint8_t* lut64, magot_o
   if (lut64) std::memcpy(lut, lut64, 64);
   else standard_lut(lut);
   orf6_tables(lut, tables);
-  Carve cv;
-  const uint64_t o_off = cv.take<uint64_t>(o->n_rec + 1);
-  const uint64_t o_boff = cv.take<uint64_t>(o->n_rec + 1);
-  const uint64_t o_out = cv.take<uint8_t>(o->total + 64);
-  const uint64_t o_rows = cv.take<uint64_t>(2 * (ne_k + 1));
-  const uint64_t o_t0 = cv.take<uint64_t>(n_tiles + 1);
-  const uint64_t o_r0 = cv.take<uint32_t>(n_tiles);
-  const uint64_t o_e0 = cv.take<uint32_t>(n_tiles);
-  const uint64_t o_m = cv.take<uint32_t>(n_tiles);
-  const uint64_t o_lut = cv.take<uint8_t>(256);
+  Orf6Args& a = o->args;
+  Carve cv;  // the uploads go to the arena + offset: the kernel's fields are const
+  const uint64_t o_off = cv.take(&a.noff, o->n_rec + 1);
+  const uint64_t o_boff = cv.take(&a.boff, o->n_rec + 1);
+  cv.take(&o->out, o->total + 64);
+  const uint64_t o_rows = cv.take(&a.rows, 2 * (ne_k + 1));
+  const uint64_t o_t0 = cv.take(&a.tile_t0, n_tiles + 1);
+  const uint64_t o_r0 = cv.take(&a.tile_r0, n_tiles);
+  const uint64_t o_e0 = cv.take(&a.tile_e0, n_tiles);
+  const uint64_t o_m = cv.take(&a.tile_m, n_tiles);
+  const uint64_t o_lut = cv.take(&a.tables, 256);
   const uint64_t nib_words = p->args.span / 4;  // forward + reverse planes, 8 bases per word
   const uint64_t code2_words = nib_words / 2;
-  const uint64_t o_code2 = cv.take<uint32_t>(code2_words + 4);
+  uint32_t *code2, *exc1;  // written here; the kernel reads them as const
+  cv.take(&code2, code2_words + 4);
   const uint64_t exc1_words = nib_words / 4;
-  const uint64_t o_exc1 = cv.take<uint32_t>(exc1_words + 4);
+  cv.take(&exc1, exc1_words + 4);
   MAGOT_HIP_TRY(hipMalloc(&o->arena, cv.used));
+  cv.place(o->arena);
   char* base = static_cast<char*>(o->arena);
   auto up = [&](uint64_t off, const void* src, uint64_t bytes) {
     return bytes ? hipMemcpy(base + off, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
   };
-  uint32_t* code2 = reinterpret_cast<uint32_t*>(base + o_code2);
-  uint32_t* exc1 = reinterpret_cast<uint32_t*>(base + o_exc1);
   launch_code2(p->args.nib, nib_words, code2, ctx->stream);
   launch_exc1(p->args.nib, nib_words, exc1, ctx->stream);
   MAGOT_HIP_TRY(hipGetLastError());
@@ -167,26 +168,16 @@ int magot_plan_orf6(magot_ctx* ctx, magot_plan* p, const uint8_t* lut64, magot_o
   MAGOT_HIP_TRY(up(o_e0, tiles.e0.data(), n_tiles * 4));
   MAGOT_HIP_TRY(up(o_m, tiles.m.data(), n_tiles * 4));
   MAGOT_HIP_TRY(up(o_lut, tables, 256));
-  o->out = reinterpret_cast<uint8_t*>(base + o_out);
-  Orf6Args& a = o->args;
   a.nib = p->args.nib;
   a.nib_words = nib_words;
   a.code2 = code2;
   a.code2_words = code2_words;
   a.exc1 = exc1;
   a.exc1_words = exc1_words;
-  a.rows = reinterpret_cast<const uint64_t*>(base + o_rows);
   a.n_rows = ne_k;
-  a.noff = reinterpret_cast<const uint64_t*>(base + o_off);
   a.n_rec = o->n_rec;
   a.total = total_nuc;
-  a.boff = reinterpret_cast<const uint64_t*>(base + o_boff);
-  a.tile_t0 = reinterpret_cast<const uint64_t*>(base + o_t0);
-  a.tile_r0 = reinterpret_cast<const uint32_t*>(base + o_r0);
-  a.tile_e0 = reinterpret_cast<const uint32_t*>(base + o_e0);
-  a.tile_m = reinterpret_cast<const uint32_t*>(base + o_m);
   a.n_tiles = n_tiles;
-  a.tables = reinterpret_cast<const uint8_t*>(base + o_lut);
   a.out = o->out;
   if (total_res) *total_res = o->total;
   *out = o.release();
@@ -241,12 +232,10 @@ int magot_orf6_time(magot_ctx* ctx, magot_orf6* o, int iters, double* avg_ms) {
     set_error("magot_orf6_time: bad argument");
     return MAGOT_ERR_ARG;
   }
-  double total = 0;
-  for (int i = 0; i < iters; ++i)
-    if (int rc = time_pass(ctx, &total, [&] { return o->launch(ctx->stream), hipSuccess; }))
-      return rc;
+  if (int rc = time_passes(ctx, iters, 1, avg_ms,
+                           [&](int) { return o->launch(ctx->stream), hipSuccess; }))
+    return rc;
   o->executed = true;
-  *avg_ms = total / iters;
   return MAGOT_OK;
 }
 
@@ -368,11 +357,8 @@ int magot_orfcall_create(magot_ctx* ctx, magot_orf6* o, uint32_t flags, magot_or
     set_error("magot_orfcall_create: too many records (stream indices are 32-bit)");
     return MAGOT_ERR_ARG;
   }
-  struct Guard {
-    magot_orfcall* c;
-    ~Guard() { magot_orfcall_destroy(c); }
-  } guard{new magot_orfcall()};
-  magot_orfcall* c = guard.c;
+  Building<magot_orfcall, magot_orfcall_destroy> guard{new magot_orfcall()};
+  magot_orfcall* c = guard.p;
   c->ctx = ctx;
   c->o6 = o;
   OrfCallArgs& a = c->a;
@@ -435,8 +421,7 @@ int magot_orfcall_create(magot_ctx* ctx, magot_orf6* o, uint32_t flags, magot_or
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
   if (n_orfs) *n_orfs = c->rows();
   if (payload_bytes) *payload_bytes = c->longest() ? c->sel_bytes : c->payload_bytes;
-  guard.c = nullptr;
-  *out = c;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -554,16 +539,11 @@ int magot_orfcall_time(magot_ctx* ctx, magot_orfcall* c, int text, int iters, do
     set_error("magot_orfcall_time: call magot_orfcall_text first");
     return MAGOT_ERR_STATE;
   }
-  double total = 0;
-  for (int i = 0; i < iters; ++i)
-    if (int rc = time_pass(ctx, &total, [&] {
-          if (!text) return orf_run(c, ctx->stream);
-          if (hipError_t e = launch_orftext_sizes(c->t, ctx->stream)) return e;
-          return launch_orftext_copy(c->t, ctx->stream);
-        }))
-      return rc;
-  *avg_ms = total / iters;
-  return MAGOT_OK;
+  return time_passes(ctx, iters, 1, avg_ms, [&](int) {
+    if (!text) return orf_run(c, ctx->stream);
+    if (hipError_t e = launch_orftext_sizes(c->t, ctx->stream)) return e;
+    return launch_orftext_copy(c->t, ctx->stream);
+  });
 }
 
 }  // extern "C"

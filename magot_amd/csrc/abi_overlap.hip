@@ -60,20 +60,16 @@ int upload_query(magot_ctx* ctx, magot_overlap* h, const char* who, const uint32
     h->q = OvQuery{};
     const uint64_t cap = std::max<uint64_t>(n, 1);
     Carve cv;
-    const uint64_t o_seq = cv.take<uint32_t>(cap), o_c0 = cv.take<int64_t>(cap);
-    const uint64_t o_c1 = cv.take<int64_t>(cap), o_drop = cv.take<uint8_t>(cap);
-    const uint64_t o_counts = cv.take<int64_t>(cap), o_list = cv.take<uint32_t>(cap);
-    const uint64_t o_n = cv.take<unsigned long long>(1);
+    cv.take(&h->q.seq, cap);
+    cv.take(&h->q.c0, cap);
+    cv.take(&h->q.c1, cap);
+    cv.take(&h->drop, cap);
+    cv.take(&h->counts, cap);
+    cv.take(&h->long_list, cap);
+    cv.take(&h->n_long, 1);
     MAGOT_HIP_TRY(hipMalloc(&h->qmem, cv.used));
-    char* base = static_cast<char*>(h->qmem);
+    cv.place(h->qmem);
     h->qcap = cap;
-    h->q.seq = reinterpret_cast<const uint32_t*>(base + o_seq);
-    h->q.c0 = reinterpret_cast<const int64_t*>(base + o_c0);
-    h->q.c1 = reinterpret_cast<const int64_t*>(base + o_c1);
-    h->drop = reinterpret_cast<uint8_t*>(base + o_drop);
-    h->counts = reinterpret_cast<int64_t*>(base + o_counts);
-    h->long_list = reinterpret_cast<uint32_t*>(base + o_list);
-    h->n_long = reinterpret_cast<unsigned long long*>(base + o_n);
   }
   h->q.n = n;
   if (n) {
@@ -125,53 +121,46 @@ int magot_overlap_create(magot_ctx* ctx, const uint32_t* seq, const int64_t* p0,
     set_error("magot_overlap_create: a coordinate outside [-2^39, 2^39)");
     return MAGOT_ERR_RANGE;
   }
-  struct Guard {
-    magot_overlap* h;
-    ~Guard() { magot_overlap_destroy(h); }
-  } guard{new magot_overlap()};
-  magot_overlap* h = guard.h;
+  Building<magot_overlap, magot_overlap_destroy> guard{new magot_overlap()};
+  magot_overlap* h = guard.p;
   h->ctx = ctx;
   h->sort_bytes = ov_sort_bytes(n);
   const uint64_t segs = (uint64_t)n_seq + 1;
-  Carve cv;
-  const uint64_t o_seq = cv.take<uint32_t>(n), o_p0 = cv.take<int64_t>(n);
-  const uint64_t o_p1 = cv.take<int64_t>(n);
-  const uint64_t o_raw = cv.take<uint64_t>(5 * n), o_raw_v = cv.take<int64_t>(n);
-  const uint64_t o_tab = cv.take<uint64_t>(5 * n), o_cl_v = cv.take<int64_t>(n);
-  const uint64_t o_seg = cv.take<uint64_t>(3 * segs);
-  const uint64_t o_tmp = cv.take<uint8_t>(h->sort_bytes);
-  MAGOT_HIP_TRY(hipMalloc(&h->arena, cv.used + 256));
-  char* base = static_cast<char*>(h->arena);
-  if (n) {
-    MAGOT_HIP_TRY(hipMemcpy(base + o_seq, seq, n * 4, hipMemcpyHostToDevice));
-    MAGOT_HIP_TRY(hipMemcpy(base + o_p0, p0, n * 8, hipMemcpyHostToDevice));
-    MAGOT_HIP_TRY(hipMemcpy(base + o_p1, p1, n * 8, hipMemcpyHostToDevice));
-  }
   OvBuildArgs& b = h->b;
   b.n = n;
   b.n_seq = n_seq;
-  b.seq = reinterpret_cast<const uint32_t*>(base + o_seq);
-  b.p0 = reinterpret_cast<const int64_t*>(base + o_p0);
-  b.p1 = reinterpret_cast<const int64_t*>(base + o_p1);
-  b.raw = reinterpret_cast<uint64_t*>(base + o_raw);
-  b.raw_v = reinterpret_cast<int64_t*>(base + o_raw_v);
-  uint64_t* tab = reinterpret_cast<uint64_t*>(base + o_tab);
-  b.in_s = tab;
-  b.in_e = tab + n;
-  b.all_s = tab + 2 * n;
-  b.cl_s = tab + 3 * n;
-  b.cl_e = tab + 4 * n;
-  b.cl_v = reinterpret_cast<int64_t*>(base + o_cl_v);
-  uint64_t* seg = reinterpret_cast<uint64_t*>(base + o_seg);
-  b.seg_in = seg;
-  b.seg_all = seg + segs;
-  b.seg_cl = seg + 2 * segs;
-  h->sort_tmp = base + o_tmp;
+  Carve cv;
+  uint32_t* d_seq;  // uploaded into; the kernels read them as const
+  int64_t *d_p0, *d_p1;
+  cv.take(&d_seq, n);
+  cv.take(&d_p0, n);
+  cv.take(&d_p1, n);
+  cv.take(&b.raw, 5 * n);
+  cv.take(&b.raw_v, n);
+  cv.take(&b.in_s, 5 * n);  // and in_e, all_s, cl_s, cl_e
+  cv.take(&b.cl_v, n);
+  cv.take(&b.seg_in, 3 * segs);  // and seg_all, seg_cl
+  cv.take(&h->sort_tmp, h->sort_bytes);
+  MAGOT_HIP_TRY(hipMalloc(&h->arena, cv.used + 256));
+  cv.place(h->arena);
+  if (n) {
+    MAGOT_HIP_TRY(hipMemcpy(d_seq, seq, n * 4, hipMemcpyHostToDevice));
+    MAGOT_HIP_TRY(hipMemcpy(d_p0, p0, n * 8, hipMemcpyHostToDevice));
+    MAGOT_HIP_TRY(hipMemcpy(d_p1, p1, n * 8, hipMemcpyHostToDevice));
+  }
+  b.seq = d_seq;
+  b.p0 = d_p0;
+  b.p1 = d_p1;
+  b.in_e = b.in_s + n;
+  b.all_s = b.in_s + 2 * n;
+  b.cl_s = b.in_s + 3 * n;
+  b.cl_e = b.in_s + 4 * n;
+  b.seg_all = b.seg_in + segs;
+  b.seg_cl = b.seg_in + 2 * segs;
   h->ix = OvIndex{n, n_seq, b.in_s, b.in_e, b.all_s, b.cl_s, b.cl_e, b.cl_v,
                   b.seg_in, b.seg_all, b.seg_cl};
   MAGOT_HIP_TRY(build(h, ctx->stream));
-  guard.h = nullptr;
-  *out = h;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -215,32 +204,26 @@ int magot_overlap_time(magot_ctx* ctx, magot_overlap* h, int iters, double* ms,
   // the unsorted keys (the keys pass writes them again)
   const uint64_t bytes = h->b.n * 8 * 5;
   if (copy_bytes) *copy_bytes = bytes + h->b.n * 8;
-  double total[6] = {0, 0, 0, 0, 0, 0};
   hipStream_t s = ctx->stream;
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < 6; ++k) {
-      if (k >= 3 && k <= 4 && !h->q.n) continue;  // no query set was given yet
-      if (int rc = time_pass(ctx, &total[k], [&]() -> hipError_t {
-            switch (k) {
-              case 0: return launch_ov_keys(h->b, s);
-              case 1: return launch_ov_sort(h->b, h->sort_tmp, h->sort_bytes, s);
-              case 2: return launch_ov_segments(h->b, s);
-              case 3: return launch_ov_purge(h->ix, h->q, h->drop, s);
-              case 4:
-                return launch_ov_overlap(h->ix, h->q, h->counts, h->long_list, h->n_long,
-                                         ctx->n_cu, s);
-              default:
-                if (!bytes) return hipSuccess;
-                if (hipError_t e = hipMemcpyAsync(h->b.raw, h->b.in_s, bytes,
-                                                  hipMemcpyDeviceToDevice, s))
-                  return e;
-                return hipMemcpyAsync(h->b.raw_v, h->b.cl_v, h->b.n * 8, hipMemcpyDeviceToDevice, s);
-            }
-          }))
-        return rc;
-    }
-  for (int k = 0; k < 6; ++k) ms[k] = total[k] / iters;
-  return MAGOT_OK;
+  return time_passes(
+      ctx, iters, 6, ms,
+      [&](int k) -> hipError_t {
+        switch (k) {
+          case 0: return launch_ov_keys(h->b, s);
+          case 1: return launch_ov_sort(h->b, h->sort_tmp, h->sort_bytes, s);
+          case 2: return launch_ov_segments(h->b, s);
+          case 3: return launch_ov_purge(h->ix, h->q, h->drop, s);
+          case 4:
+            return launch_ov_overlap(h->ix, h->q, h->counts, h->long_list, h->n_long, ctx->n_cu,
+                                     s);
+          default:
+            if (!bytes) return hipSuccess;
+            if (hipError_t e = hipMemcpyAsync(h->b.raw, h->b.in_s, bytes, hipMemcpyDeviceToDevice, s))
+              return e;
+            return hipMemcpyAsync(h->b.raw_v, h->b.cl_v, h->b.n * 8, hipMemcpyDeviceToDevice, s);
+        }
+      },
+      [&](int k) { return k >= 3 && k <= 4 && !h->q.n; });  // no query set was given yet
 }
 
 }  // extern "C"

@@ -164,9 +164,9 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   Carve cv;
   // The device holds the tiles' packed blocks and their overflow rows, not
   // the u64 tables they are packed from.
-  const uint64_t o_blocks = cv.take<uint8_t>((uint64_t)n_tiles * geo.stride);
-  const uint64_t o_ovf_ex = cv.take<uint64_t>(pl.n_ovf_ex + 1);
-  const uint64_t o_ovf_tx = cv.take<TxRow>(pl.n_ovf_tx + 1);
+  const uint64_t o_blocks = cv.take(&p->args.blocks, (uint64_t)n_tiles * geo.stride);
+  const uint64_t o_ovf_ex = cv.take(&p->args.ovf_ex, pl.n_ovf_ex + 1);
+  const uint64_t o_ovf_tx = cv.take(&p->args.ovf_tx, pl.n_ovf_tx + 1);
   // genome order: {layout place, record-order offsets} per output, for the
   // reassembly copies (magot_plan_fetch / copy_outputs)
   const uint64_t lay_rows = by_genome ? T : 0;
@@ -175,6 +175,7 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   const uint64_t o_lay_pep = cv.take<uint64_t>(lay_rows);
   const uint64_t o_rec_pep = cv.take<uint64_t>(by_genome ? T + 1 : 0);
   MAGOT_HIP_TRY(hipMalloc(&p->arena, cv.used));
+  cv.place(p->arena);
   p->arena_bytes = cv.used;
   const hipError_t out_err = out_alloc.take(&p->out_arena);
   MAGOT_HIP_TRY(out_err);
@@ -231,10 +232,7 @@ int magot_plan_create(magot_ctx* ctx, const magot_genome* g, const magot_exon* e
   a.span = g->span;
   a.runs = g->runs;
   a.dir = g->dir;
-  a.blocks = reinterpret_cast<const uint8_t*>(base + o_blocks);
   a.blk = geo;
-  a.ovf_ex = reinterpret_cast<const uint64_t*>(base + o_ovf_ex);
-  a.ovf_tx = reinterpret_cast<const TxRow*>(base + o_ovf_tx);
   a.nuc = static_cast<uint8_t*>(p->out_arena);
   a.pep = static_cast<uint8_t*>(p->out_arena) + ((out_nuc + 255) & ~255ull);
   a.total_nuc = B;
@@ -342,15 +340,12 @@ int magot_plan_time(magot_ctx* ctx, magot_plan* p, int iters, double* avg_ms) {
     set_error("magot_plan_time: bad argument");
     return MAGOT_ERR_ARG;
   }
-  double total = 0.0;
-  for (int i = 0; i < iters; ++i)
-    if (int rc = time_pass(ctx, &total, [&] {
-          launch_extract(p->args, ctx->stream);
-          return hipGetLastError();
-        }))
-      return rc;
+  if (int rc = time_passes(ctx, iters, 1, avg_ms, [&](int) {
+        launch_extract(p->args, ctx->stream);
+        return hipGetLastError();
+      }))
+    return rc;
   p->executed = true;
-  *avg_ms = total / iters;
   return MAGOT_OK;
 }
 
@@ -506,24 +501,18 @@ int magot_fasta_text_create(magot_ctx* ctx, const magot_gffplan* gp, const magot
   o->cap = text->size() + (roff.empty() ? 0 : roff.back());
   o->scan_bytes = text_scan_bytes(o->n_units);
   Carve cv;
-  const uint64_t o_units = cv.take<TextUnit>(o->n_units);
-  const uint64_t o_roff = cv.take<uint64_t>(span.size());
-  const uint64_t o_text = cv.take<uint8_t>(text->size());
-  const uint64_t o_len = cv.take<uint64_t>(o->n_units);
-  const uint64_t o_psrc = cv.take<uint64_t>(o->n_units);
-  const uint64_t o_end = cv.take<uint64_t>(o->n_units);
-  const uint64_t o_tmp = cv.take<uint8_t>(o->scan_bytes);
-  const uint64_t o_out = cv.take<uint8_t>(o->cap);
+  // the uploads go to the arena + offset: the kernels' fields are const
+  const uint64_t o_units = cv.take(&o->units, o->n_units);
+  const uint64_t o_roff = cv.take(&o->roff, span.size());
+  const uint64_t o_text = cv.take(&o->text, text->size());
+  cv.take(&o->len, o->n_units);
+  cv.take(&o->psrc, o->n_units);
+  cv.take(&o->end, o->n_units);
+  cv.take(&o->scan_tmp, o->scan_bytes);
+  cv.take(&o->out, o->cap);
   MAGOT_HIP_TRY(hipMalloc(&o->arena, cv.used));
+  cv.place(o->arena);
   char* base = static_cast<char*>(o->arena);
-  o->units = reinterpret_cast<const TextUnit*>(base + o_units);
-  o->roff = reinterpret_cast<const uint64_t*>(base + o_roff);
-  o->text = reinterpret_cast<const uint8_t*>(base + o_text);
-  o->len = reinterpret_cast<uint64_t*>(base + o_len);
-  o->psrc = reinterpret_cast<uint64_t*>(base + o_psrc);
-  o->end = reinterpret_cast<uint64_t*>(base + o_end);
-  o->scan_tmp = base + o_tmp;
-  o->out = reinterpret_cast<uint8_t*>(base + o_out);
   if (!units.empty())
     MAGOT_HIP_TRY(hipMemcpy(base + o_units, units.data(), units.size() * sizeof(TextUnit),
                             hipMemcpyHostToDevice));
@@ -578,12 +567,8 @@ int magot_fasta_text_time(magot_ctx* ctx, magot_fasta_text* o, int iters, double
     set_error("magot_fasta_text_time: bad argument");
     return MAGOT_ERR_ARG;
   }
-  double total = 0;
-  for (int i = 0; i < iters; ++i)
-    if (int rc = time_pass(ctx, &total, [&] { return o->launch(ctx->stream), hipSuccess; }))
-      return rc;
-  *avg_ms = total / iters;
-  return MAGOT_OK;
+  return time_passes(ctx, iters, 1, avg_ms,
+                     [&](int) { return o->launch(ctx->stream), hipSuccess; });
 }
 
 void magot_fasta_text_destroy(magot_fasta_text* o) {

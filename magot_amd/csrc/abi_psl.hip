@@ -38,18 +38,7 @@ hipError_t psl_pass(const magot_psl* p, int k, hipStream_t s) {
   }
 }
 
-int psl_decline(uint32_t* reason, uint64_t* line, uint32_t why, uint64_t at) {
-  if (reason) *reason = why;
-  if (line) *line = at;
-  set_error("magot_psl_parse: input outside the device path; use the line loop");
-  return MAGOT_ERR_UNSUPPORTED;
-}
-
-template <class T>
-int psl_fetch(T* dst, const T* src, uint64_t n) {
-  if (dst && n) MAGOT_HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
-  return MAGOT_OK;
-}
+constexpr char kOutside[] = "magot_psl_parse: input outside the device path; use the line loop";
 
 }  // namespace
 
@@ -79,73 +68,58 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     return MAGOT_ERR_ARG;
   }
   if (int rc = resident_text_budget(&max_bytes)) return rc;
-  if (len > max_bytes) return psl_decline(reason, line, MAGOT_PSL_TOO_LARGE, 0);
+  if (len > max_bytes) return decline(kOutside, reason, line, MAGOT_PSL_TOO_LARGE, 0);
 
-  struct Guard {
-    magot_psl* p;
-    ~Guard() { magot_psl_destroy(p); }
-  } guard{new magot_psl()};
+  Building<magot_psl, magot_psl_destroy> guard{new magot_psl()};
   magot_psl* p = guard.p;
   p->ctx = ctx;
   PslArgs& a = p->a;
   a.hash_bits = hash_bits;
   hipStream_t s = ctx->stream;
   if (len) {
-    if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte,
-                                    2 * sizeof(unsigned long long), &p->rt, &a.ix))
+    Carve cv;  // the caller's slice: the status word, then the count of keys
+    cv.take(&a.status, 2);
+    if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte, cv.used, &p->rt, &a.ix))
       return rc;
-    a.status = reinterpret_cast<unsigned long long*>(p->rt.extra);
+    cv.place(p->rt.extra);
     a.n_uniq = a.status + 1;
     MAGOT_HIP_TRY(hipMemsetAsync(a.status, 0xff, sizeof(unsigned long long), s));
     a.ix.n_lines = p->rt.n_lines;
-    if (a.ix.n_lines > kPslLineMask) return psl_decline(reason, line, MAGOT_PSL_TOO_MANY_LINES, 0);
+    if (a.ix.n_lines > kPslLineMask)
+      return decline(kOutside, reason, line, MAGOT_PSL_TOO_MANY_LINES, 0);
   }
   if (a.ix.n_lines) {
     const uint64_t L = a.ix.n_lines;
     p->tmp_bytes = psl_tmp_bytes(L);
     Carve cv;
-    const uint64_t o_start = cv.take<uint64_t>(L + 1), o_hash = cv.take<uint64_t>(L);
-    const uint64_t o_koff = cv.take<uint64_t>(L), o_klen = cv.take<uint32_t>(L);
-    const uint64_t o_rank = cv.take<uint64_t>(L), o_kind = cv.take<uint32_t>(L + 1);
-    const uint64_t o_dpos = cv.take<uint32_t>(L + 1);
-    const uint64_t o_skey = cv.take<uint64_t>(L), o_sval = cv.take<uint64_t>(L);
-    const uint64_t o_skey2 = cv.take<uint64_t>(L), o_sval2 = cv.take<uint64_t>(L);
-    const uint64_t o_poff = cv.take<uint64_t>(L), o_plen = cv.take<uint64_t>(L);
-    const uint64_t o_uniq = cv.take<uint64_t>(L), o_agg = cv.take<PslAgg>(L);
-    const uint64_t o_seg = cv.take<uint32_t>(4 * L);
-    const uint64_t o_g64 = cv.take<uint64_t>(4 * L), o_g32 = cv.take<uint32_t>(2 * L);
-    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
+    cv.take(&a.ix.pos, L + 1);
+    cv.take(&a.hash, L);
+    cv.take(&a.key_off, L);
+    cv.take(&a.key_len, L);
+    cv.take(&a.rank, L);
+    cv.take(&a.kind, L + 1);
+    cv.take(&a.dpos, L + 1);
+    cv.take(&a.skey, L);
+    cv.take(&a.sval, L);
+    cv.take(&a.skey_sorted, L);
+    cv.take(&a.sval_sorted, L);
+    cv.take(&a.pass_off, L);
+    cv.take(&a.pass_len, L);
+    cv.take(&a.uniq, L);
+    cv.take(&a.agg, L);
+    cv.take(&a.seg_first, 4 * L);  // and seg_id and their sorted copies
+    cv.take(&a.g_hash, 4 * L);     // and g_off, g_len, g_score
+    cv.take(&a.g_first, 2 * L);    // and g_best
+    cv.take(&p->tmp, p->tmp_bytes);
     MAGOT_HIP_TRY(hipMalloc(&p->mem, cv.used + 256));
-    char* base = static_cast<char*>(p->mem);
-    a.ix.pos = reinterpret_cast<uint64_t*>(base + o_start);
-    a.hash = reinterpret_cast<uint64_t*>(base + o_hash);
-    a.key_off = reinterpret_cast<uint64_t*>(base + o_koff);
-    a.key_len = reinterpret_cast<uint32_t*>(base + o_klen);
-    a.rank = reinterpret_cast<uint64_t*>(base + o_rank);
-    a.kind = reinterpret_cast<uint32_t*>(base + o_kind);
-    a.dpos = reinterpret_cast<uint32_t*>(base + o_dpos);
-    a.skey = reinterpret_cast<uint64_t*>(base + o_skey);
-    a.sval = reinterpret_cast<uint64_t*>(base + o_sval);
-    a.skey_sorted = reinterpret_cast<uint64_t*>(base + o_skey2);
-    a.sval_sorted = reinterpret_cast<uint64_t*>(base + o_sval2);
-    a.pass_off = reinterpret_cast<uint64_t*>(base + o_poff);
-    a.pass_len = reinterpret_cast<uint64_t*>(base + o_plen);
-    a.uniq = reinterpret_cast<uint64_t*>(base + o_uniq);
-    a.agg = reinterpret_cast<PslAgg*>(base + o_agg);
-    uint32_t* seg = reinterpret_cast<uint32_t*>(base + o_seg);
-    a.seg_first = seg;
-    a.seg_id = seg + L;
-    a.seg_first_sorted = seg + 2 * L;
-    a.seg_id_sorted = seg + 3 * L;
-    uint64_t* g64 = reinterpret_cast<uint64_t*>(base + o_g64);
-    a.g_hash = g64;
-    a.g_off = g64 + L;
-    a.g_len = g64 + 2 * L;
-    a.g_score = reinterpret_cast<int64_t*>(g64 + 3 * L);
-    uint32_t* g32 = reinterpret_cast<uint32_t*>(base + o_g32);
-    a.g_first = g32;
-    a.g_best = g32 + L;
-    p->tmp = base + o_tmp;
+    cv.place(p->mem);
+    a.seg_id = a.seg_first + L;
+    a.seg_first_sorted = a.seg_first + 2 * L;
+    a.seg_id_sorted = a.seg_first + 3 * L;
+    a.g_off = a.g_hash + L;
+    a.g_len = a.g_hash + 2 * L;
+    a.g_score = reinterpret_cast<int64_t*>(a.g_hash + 3 * L);
+    a.g_best = a.g_first + L;
 
     MAGOT_HIP_TRY(launch_text_fill(a.ix, kTextFillLines, s));
     MAGOT_HIP_TRY(launch_psl_parse(a, s));
@@ -155,8 +129,7 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipMemcpyAsync(&n_data, a.dpos + L, 4, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    if (status != ~0ull)
-      return psl_decline(reason, line, (uint32_t)(status & 0xff), (status >> 8) + 1);
+    if (int rc = decline_if_offended(kOutside, reason, line, status)) return rc;
     a.n_data = n_data;
     MAGOT_HIP_TRY(launch_psl_scatter(a, s));
     MAGOT_HIP_TRY(launch_psl_sort(a, p->tmp, p->tmp_bytes, s));
@@ -166,8 +139,7 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     MAGOT_HIP_TRY(hipMemcpyAsync(&status, a.status, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipMemcpyAsync(&n_uniq, a.n_uniq, 8, hipMemcpyDeviceToHost, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
-    if (status != ~0ull)
-      return psl_decline(reason, line, (uint32_t)(status & 0xff), (status >> 8) + 1);
+    if (int rc = decline_if_offended(kOutside, reason, line, status)) return rc;
     if (n_uniq > a.n_data) {
       set_error("magot_psl_parse: more keys than data lines");
       return MAGOT_ERR_STATE;
@@ -176,8 +148,7 @@ int magot_psl_parse(magot_ctx* ctx, const char* text, uint64_t len, uint32_t has
     MAGOT_HIP_TRY(launch_psl_order(a, p->tmp, p->tmp_bytes, s));
     MAGOT_HIP_TRY(hipStreamSynchronize(s));
   }
-  guard.p = nullptr;
-  *out = p;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -200,8 +171,8 @@ int magot_psl_pass_lines(magot_ctx* ctx, magot_psl* p, uint64_t* off, uint64_t* 
   if (int rc = handle_of(ctx, p, "magot_psl_pass_lines", "handle")) return rc;
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   const uint64_t n = p->a.ix.n_lines - p->a.n_data;
-  if (int rc = psl_fetch(off, p->a.pass_off, n)) return rc;
-  return psl_fetch(len, p->a.pass_len, n);
+  if (int rc = fetch_rows(off, p->a.pass_off, n)) return rc;
+  return fetch_rows(len, p->a.pass_len, n);
 }
 
 int magot_psl_groups(magot_ctx* ctx, magot_psl* p, uint64_t* hash, uint32_t* first_line,
@@ -210,12 +181,12 @@ int magot_psl_groups(magot_ctx* ctx, magot_psl* p, uint64_t* hash, uint32_t* fir
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   const PslArgs& a = p->a;
   const uint64_t n = a.n_groups;
-  if (int rc = psl_fetch(hash, a.g_hash, n)) return rc;
-  if (int rc = psl_fetch(first_line, a.g_first, n)) return rc;
-  if (int rc = psl_fetch(best_line, a.g_best, n)) return rc;
-  if (int rc = psl_fetch(score, a.g_score, n)) return rc;
-  if (int rc = psl_fetch(off, a.g_off, n)) return rc;
-  return psl_fetch(len, a.g_len, n);
+  if (int rc = fetch_rows(hash, a.g_hash, n)) return rc;
+  if (int rc = fetch_rows(first_line, a.g_first, n)) return rc;
+  if (int rc = fetch_rows(best_line, a.g_best, n)) return rc;
+  if (int rc = fetch_rows(score, a.g_score, n)) return rc;
+  if (int rc = fetch_rows(off, a.g_off, n)) return rc;
+  return fetch_rows(len, a.g_len, n);
 }
 
 int magot_psl_time(magot_ctx* ctx, magot_psl* p, int iters, double* ms8, uint64_t* text_bytes) {
@@ -229,14 +200,8 @@ int magot_psl_time(magot_ctx* ctx, magot_psl* p, int iters, double* ms8, uint64_
   if (!p->a.ix.n_lines) return MAGOT_OK;  // an empty text: nothing was launched
   if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.ix.n + 256));
   // every pass writes what it wrote in magot_psl_parse: the answers stand
-  double total[kPslPasses] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < kPslPasses; ++k)
-      if (int rc = time_pass(ctx, &total[k],
-                             [&]() -> hipError_t { return psl_pass(p, k, ctx->stream); }))
-        return rc;
-  for (int k = 0; k < kPslPasses; ++k) ms8[k] = total[k] / iters;
-  return MAGOT_OK;
+  return time_passes(ctx, iters, kPslPasses, ms8,
+                     [&](int k) { return psl_pass(p, k, ctx->stream); });
 }
 
 }  // extern "C"

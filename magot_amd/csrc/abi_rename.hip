@@ -23,16 +23,8 @@ namespace {
 
 constexpr int kRnPasses = 6;
 
-int rn_decline(uint32_t* reason, uint32_t why) {
-  if (reason) *reason = why;
-  set_error("magot_rename_parse: input outside the device path; use the host loop");
-  return MAGOT_ERR_UNSUPPORTED;
-}
-
-template <class T>
-T* at(char* base, uint64_t off) {
-  return reinterpret_cast<T*>(base + off);
-}
+constexpr char kOutside[] =
+    "magot_rename_parse: input outside the device path; use the host loop";
 
 // The buffers of a render: the output and one row per piece.  Replaces the
 // handle's last ones.
@@ -43,15 +35,12 @@ int rn_plan_render(magot_rename* p) {
   RnRenderArgs& r = p->r;
   if (!r.n_pieces) return MAGOT_OK;
   Carve co;
-  const uint64_t q_out = co.take<uint8_t>(r.out_bytes + 16);
-  const uint64_t q_src = co.take<uint64_t>(r.n_pieces), q_dst = co.take<uint64_t>(r.n_pieces);
-  const uint64_t q_len = co.take<uint32_t>(r.n_pieces);
+  co.take(&r.out, r.out_bytes + 16);
+  co.take(&r.p_src, r.n_pieces);
+  co.take(&r.p_dst, r.n_pieces);
+  co.take(&r.p_len, r.n_pieces);
   MAGOT_HIP_TRY(hipMalloc(&p->out_mem, co.used + 256));
-  char* ob = static_cast<char*>(p->out_mem);
-  r.out = at<uint8_t>(ob, q_out);
-  r.p_src = at<uint64_t>(ob, q_src);
-  r.p_dst = at<uint64_t>(ob, q_dst);
-  r.p_len = at<uint32_t>(ob, q_len);
+  co.place(p->out_mem);
   return MAGOT_OK;
 }
 
@@ -108,19 +97,17 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
     set_error("magot_rename_parse: the delimiter is one byte other than LF");
     return MAGOT_ERR_ARG;
   }
-  if (n_keys >= kRnMaxKeys) return rn_decline(reason, MAGOT_RENAME_TABLE_TOO_LARGE);
+  if (n_keys >= kRnMaxKeys)
+    return decline(kOutside, reason, nullptr, MAGOT_RENAME_TABLE_TOO_LARGE, 0);
   const uint64_t names_len = n_keys ? name_off[n_keys] : 0, vals_len = n_keys ? val_off[n_keys] : 0;
   if (names_len >= kRnMaxBlob || vals_len >= kRnMaxBlob)
-    return rn_decline(reason, MAGOT_RENAME_TABLE_TOO_LARGE);
+    return decline(kOutside, reason, nullptr, MAGOT_RENAME_TABLE_TOO_LARGE, 0);
   if (vals_len && !values) {
     set_error("magot_rename_parse: null argument");
     return MAGOT_ERR_ARG;
   }
 
-  struct Guard {
-    magot_rename* p;
-    ~Guard() { magot_rename_destroy(p); }
-  } guard{new magot_rename()};
+  Building<magot_rename, magot_rename_destroy> guard{new magot_rename()};
   magot_rename* p = guard.p;
   p->ctx = ctx;
   RnArgs& a = p->a;
@@ -148,7 +135,7 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
     a.max_len = std::max(a.max_len, l);
   }
   if (int rc = resident_text_budget(&max_bytes)) return rc;
-  if (len > max_bytes) return rn_decline(reason, MAGOT_RENAME_TOO_LARGE);
+  if (len > max_bytes) return decline(kOutside, reason, nullptr, MAGOT_RENAME_TOO_LARGE, 0);
 
   a.hash_bits = hash_bits;
   a.n_keys = n_keys;
@@ -161,28 +148,23 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
   hipStream_t s = ctx->stream;
   {
     Carve cv;  // the caller's slices: the values (pieces are copied from them), the table, the status
+    // the uploads go to base + offset: the kernels' fields are const
     const uint64_t o_vals = cv.take<uint8_t>(vals_len + kTextPad);
-    const uint64_t o_names = cv.take<uint8_t>(names_len + 1);
-    const uint64_t o_noff = cv.take<uint64_t>(n_keys + 1), o_voff = cv.take<uint64_t>(n_keys + 1);
-    const uint64_t o_rank = cv.take<uint32_t>(n_keys + 1);
-    const uint64_t o_hash = cv.take<uint64_t>(n_keys + 1);
-    const uint64_t o_claim = cv.take<uint32_t>(a.cap);
-    const uint64_t o_slots = cv.take<RnSlot>(a.cap);
-    const uint64_t o_status = cv.take<unsigned long long>(1);
+    const uint64_t o_names = cv.take(&a.names, names_len + 1);
+    const uint64_t o_noff = cv.take(&a.name_off, n_keys + 1);
+    const uint64_t o_voff = cv.take(&a.val_off, n_keys + 1);
+    const uint64_t o_rank = cv.take(&a.rank, n_keys + 1);
+    cv.take(&a.key_hash, n_keys + 1);
+    cv.take(&a.claim, a.cap);
+    cv.take(&a.slots, a.cap);
+    cv.take(&a.status, 1);
     // between the text's upload and the count: the table's upload, its lookup structure and
     // the status word's way back, which resident_text_open's synchronisation completes.
     // a.ix.text is set by then: the values' offset is counted from it.
     unsigned long long status = 0;
     auto table = [&](char* base) -> int {
+      cv.place(base);
       a.val_base = (uint64_t)(base + o_vals - reinterpret_cast<const char*>(a.ix.text));
-      a.names = at<const uint8_t>(base, o_names);
-      a.name_off = at<const uint64_t>(base, o_noff);
-      a.val_off = at<const uint64_t>(base, o_voff);
-      a.rank = at<const uint32_t>(base, o_rank);
-      a.key_hash = at<uint64_t>(base, o_hash);
-      a.claim = at<uint32_t>(base, o_claim);
-      a.slots = at<RnSlot>(base, o_slots);
-      a.status = at<unsigned long long>(base, o_status);
       if (n_keys) {
         MAGOT_HIP_TRY(hipMemcpyAsync(base + o_names, names, names_len, hipMemcpyHostToDevice, s));
         if (vals_len)
@@ -200,7 +182,7 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
     };
     if (int rc = resident_text_open(ctx, text, len, delim, '\n', cv.used, table, &p->rt, &a.ix))
       return rc;
-    if (status != ~0ull) return rn_decline(reason, (uint32_t)status);
+    if (status != ~0ull) return decline(kOutside, reason, nullptr, (uint32_t)status, 0);
     a.n_fields = p->rt.total;
     if (a.n_fields > len) {
       set_error("magot_rename_parse: more delimiters than bytes");
@@ -211,20 +193,17 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
     const uint64_t F = a.n_fields;
     p->tmp_bytes = exclusive_sum_bytes<uint64_t>(F + 2);  // the hits are at most the fields
     Carve cv;
-    const uint64_t o_pos = cv.take<uint64_t>(F + 1);
-    const uint64_t o_hit = cv.take<uint64_t>(F + 1), o_hpos = cv.take<uint64_t>(F + 1);
-    const uint64_t o_key = cv.take<uint32_t>(F + 1);
-    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
+    cv.take(&a.ix.pos, F + 1);
+    cv.take(&a.f_hit, F + 1);
+    cv.take(&a.f_hpos, F + 1);
+    cv.take(&a.f_key, F + 1);
+    cv.take(&p->tmp, p->tmp_bytes);
     size_t free_b = 0, total_b = 0;
     MAGOT_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (cv.used > free_b / 2) return rn_decline(reason, MAGOT_RENAME_TOO_LARGE);
+    if (cv.used > free_b / 2)
+      return decline(kOutside, reason, nullptr, MAGOT_RENAME_TOO_LARGE, 0);
     MAGOT_HIP_TRY(hipMalloc(&p->field_mem, cv.used + 256));
-    char* base = static_cast<char*>(p->field_mem);
-    a.ix.pos = at<uint64_t>(base, o_pos);
-    a.f_hit = at<uint64_t>(base, o_hit);
-    a.f_hpos = at<uint64_t>(base, o_hpos);
-    a.f_key = at<uint32_t>(base, o_key);
-    p->tmp = base + o_tmp;
+    cv.place(p->field_mem);
     MAGOT_HIP_TRY(launch_text_fill(a.ix, kTextFillPlain, s));
     MAGOT_HIP_TRY(launch_rn_match(a, p->tmp, p->tmp_bytes, s));
     MAGOT_HIP_TRY(hipMemcpyAsync(&a.n_hits, a.f_hpos + F, 8, hipMemcpyDeviceToHost, s));
@@ -237,18 +216,14 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
   {
     const uint64_t H = a.n_hits;
     Carve cv;
-    const uint64_t o_end = cv.take<uint64_t>(H + 1);
-    const uint64_t o_delta = cv.take<uint64_t>(H + 1), o_dsum = cv.take<uint64_t>(H + 1);
-    const uint64_t o_pcnt = cv.take<uint64_t>(H + 2), o_pbase = cv.take<uint64_t>(H + 2);
-    const uint64_t o_key = cv.take<uint32_t>(H + 1);
+    cv.take(&a.h_end, H + 1);
+    cv.take(&a.h_delta, H + 1);
+    cv.take(&a.h_dsum, H + 1);
+    cv.take(&a.h_pcnt, H + 2);
+    cv.take(&a.h_pbase, H + 2);
+    cv.take(&a.h_key, H + 1);
     MAGOT_HIP_TRY(hipMalloc(&p->hit_mem, cv.used + 256));
-    char* base = static_cast<char*>(p->hit_mem);
-    a.h_end = at<uint64_t>(base, o_end);
-    a.h_delta = at<uint64_t>(base, o_delta);
-    a.h_dsum = at<uint64_t>(base, o_dsum);
-    a.h_pcnt = at<uint64_t>(base, o_pcnt);
-    a.h_pbase = at<uint64_t>(base, o_pbase);
-    a.h_key = at<uint32_t>(base, o_key);
+    cv.place(p->hit_mem);
     uint64_t shift = 0;
     if (len) {  // an empty text has no run and no piece
       MAGOT_HIP_TRY(launch_rn_layout(a, p->tmp, p->tmp_bytes, s));
@@ -263,8 +238,7 @@ int magot_rename_parse(magot_ctx* ctx, const char* text, uint64_t len, const uin
       return MAGOT_ERR_STATE;
     }
   }
-  guard.p = nullptr;
-  *out = p;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -337,14 +311,8 @@ int magot_rename_time(magot_ctx* ctx, magot_rename* p, int iters, double* ms6,
   if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.ix.n + 256));
   if (int rc = rn_plan_render(p)) return rc;
   // every pass writes what it wrote in magot_rename_parse: the answers stand
-  double total[kRnPasses] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < kRnPasses; ++k)
-      if (int rc = time_pass(ctx, &total[k],
-                             [&]() -> hipError_t { return rn_pass(p, k, ctx->stream); }))
-        return rc;
-  for (int k = 0; k < kRnPasses; ++k) ms6[k] = total[k] / iters;
-  return MAGOT_OK;
+  return time_passes(ctx, iters, kRnPasses, ms6,
+                     [&](int k) { return rn_pass(p, k, ctx->stream); });
 }
 
 }  // extern "C"

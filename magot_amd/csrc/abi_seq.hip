@@ -311,16 +311,18 @@ int magot_orf6_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_of
   Orf6Tiles tiles;
   orf6_plan_tiles(seq_off, n, nullptr, 0, &tiles);
   const uint64_t n_tiles = tiles.r0.size();
-  Carve cv;
-  const uint64_t o_in = cv.take<uint8_t>(total + 64);
-  const uint64_t o_out = cv.take<uint8_t>(total_res + 64);
-  const uint64_t o_off = cv.take<uint64_t>(n + 1);
-  const uint64_t o_boff = cv.take<uint64_t>(n + 1);
-  const uint64_t o_t0 = cv.take<uint64_t>(n_tiles + 1);
-  const uint64_t o_r0 = cv.take<uint32_t>(n_tiles);
-  const uint64_t o_lut = cv.take<uint8_t>(256);
+  Orf6Args a{};
+  Carve cv;  // the uploads go to base + offset: the kernel's fields are const
+  const uint64_t o_in = cv.take(&a.nuc, total + 64);
+  cv.take(&a.out, total_res + 64);
+  const uint64_t o_off = cv.take(&a.noff, n + 1);
+  const uint64_t o_boff = cv.take(&a.boff, n + 1);
+  const uint64_t o_t0 = cv.take(&a.tile_t0, n_tiles + 1);
+  const uint64_t o_r0 = cv.take(&a.tile_r0, n_tiles);
+  const uint64_t o_lut = cv.take(&a.tables, 256);
   void* d = nullptr;
   MAGOT_HIP_TRY(hipMalloc(&d, cv.used));
+  cv.place(d);
   char* base = static_cast<char*>(d);
   hipError_t e = hipMemcpyAsync(base + o_in, seqs, total, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess)
@@ -340,21 +342,13 @@ int magot_orf6_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_of
     e = hipMemcpyAsync(base + o_r0, tiles.r0.data(), n_tiles * 4, hipMemcpyHostToDevice,
                        ctx->stream);
   if (e == hipSuccess) {
-    Orf6Args a{};
-    a.nuc = reinterpret_cast<const uint8_t*>(base + o_in);
-    a.noff = reinterpret_cast<const uint64_t*>(base + o_off);
     a.n_rec = n;
     a.total = total;
-    a.boff = reinterpret_cast<const uint64_t*>(base + o_boff);
-    a.tile_t0 = reinterpret_cast<const uint64_t*>(base + o_t0);
-    a.tile_r0 = reinterpret_cast<const uint32_t*>(base + o_r0);
     a.n_tiles = n_tiles;
-    a.tables = reinterpret_cast<const uint8_t*>(base + o_lut);
-    a.out = reinterpret_cast<uint8_t*>(base + o_out);
     launch_orf6(a, false, ctx->stream);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, base + o_out, total_res, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, a.out, total_res, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   int rc = MAGOT_OK;
   if (e != hipSuccess) {

@@ -68,31 +68,27 @@ int magot_site_create(magot_ctx* ctx, const magot_genome* g, const uint32_t* con
     set_error("magot_site_create: more workgroups than a grid holds");
     return MAGOT_ERR_ARG;
   }
-  struct Guard {
-    magot_site* p;
-    ~Guard() { magot_site_destroy(p); }
-  } guard{new magot_site()};
+  Building<magot_site, magot_site_destroy> guard{new magot_site()};
   magot_site* p = guard.p;
   p->ctx = ctx;
   p->g = g;
+  SiteArgs& a = p->a;
   Carve cv;
-  const uint64_t o_start = cv.take<uint64_t>(n_rows);
-  const uint64_t o_counts = cv.take<uint32_t>(n_sites * 4);
+  uint64_t* d_start;  // uploaded into; the kernel reads it as const
+  cv.take(&d_start, n_rows);
+  cv.take(&a.counts, n_sites * 4);
   MAGOT_HIP_TRY(hipMalloc(&p->mem, cv.used + 256));
-  char* base = static_cast<char*>(p->mem);
-  MAGOT_HIP_TRY(hipMemcpyAsync(base + o_start, start.data(), n_rows * sizeof(uint64_t),
+  cv.place(p->mem);
+  MAGOT_HIP_TRY(hipMemcpyAsync(d_start, start.data(), n_rows * sizeof(uint64_t),
                                hipMemcpyHostToDevice, ctx->stream));
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `start` goes out of scope
-  SiteArgs& a = p->a;
   a.nib = g->nib;
-  a.row_start = reinterpret_cast<const uint64_t*>(base + o_start);
+  a.row_start = d_start;
   a.n_rows = n_rows;
   a.n_sites = n_sites;
-  a.counts = reinterpret_cast<uint32_t*>(base + o_counts);
   a.n_tiles = (uint32_t)n_tiles;
   a.n_strips = (uint32_t)n_strips;
-  guard.p = nullptr;
-  *out = p;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -125,13 +121,10 @@ int magot_site_time(magot_ctx* ctx, magot_site* p, int iters, double* ms) {
     set_error("magot_site_time: bad argument");
     return MAGOT_ERR_ARG;
   }
-  double total = 0;
-  for (int i = 0; i < iters; ++i)
-    if (int rc = time_pass(ctx, &total,
-                           [&]() -> hipError_t { return launch_site_count(p->a, ctx->stream); }))
-      return rc;
+  if (int rc = time_passes(ctx, iters, 1, ms,
+                           [&](int) { return launch_site_count(p->a, ctx->stream); }))
+    return rc;
   p->executed = true;  // every run writes the same counts
-  *ms = total / iters;
   return MAGOT_OK;
 }
 

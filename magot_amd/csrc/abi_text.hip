@@ -79,11 +79,8 @@ int magot_depth_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t c
   *line = 0;
   if (n_lines) *n_lines = 0;
   if (n_runs) *n_runs = 0;
-  struct Guard {
-    magot_depth* t;
-    ~Guard() { magot_depth_destroy(t); }
-  } guard{new magot_depth()};
-  magot_depth* t = guard.t;
+  Building<magot_depth, magot_depth_destroy> guard{new magot_depth()};
+  magot_depth* t = guard.p;
   t->ctx = ctx;
   const uint64_t chunk = text_chunk_bytes(chunk_bytes, len);
   // a line of the grammar has at least 6 bytes ("a 1 0" and its LF)
@@ -92,25 +89,19 @@ int magot_depth_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t c
   const uint64_t text_blocks = depth_text_blocks(chunk);
   t->scan_bytes = depth_scan_bytes(std::max(text_blocks, depth_blocks(t->arena_cap)) + 1);
   Carve cv;
-  const uint64_t o_arena = cv.take<int32_t>(t->arena_cap);
-  const uint64_t o_sum = cv.take<int64_t>(depth_blocks(t->arena_cap) + 1);
-  const uint64_t o_dir = cv.take<int64_t>(depth_blocks(t->arena_cap) + 1);
-  const uint64_t o_count = cv.take<uint32_t>(text_blocks + 1);
-  const uint64_t o_first = cv.take<uint32_t>(text_blocks + 1);
-  const uint64_t o_tmp = cv.take<uint8_t>(t->scan_bytes);
-  const uint64_t o_heads = cv.take<DepthHead>(t->heads_cap);
-  const uint64_t o_small = cv.take<uint8_t>(3 * sizeof(DepthCarry) + 64);
+  uint8_t* small;  // three carries, two status words, two head counters
+  cv.take(&t->arena, t->arena_cap);
+  cv.take(&t->block_sum, depth_blocks(t->arena_cap) + 1);
+  cv.take(&t->dir, depth_blocks(t->arena_cap) + 1);
+  cv.take(&t->blk_count, text_blocks + 1);
+  cv.take(&t->blk_first, text_blocks + 1);
+  cv.take(&t->scan_tmp, t->scan_bytes);
+  cv.take(&t->heads, t->heads_cap);
+  cv.take(&small, 3 * sizeof(DepthCarry) + 64);
   MAGOT_HIP_TRY(hipMalloc(&t->arena_mem, cv.used + 256));
-  char* base = static_cast<char*>(t->arena_mem);
-  t->arena = reinterpret_cast<int32_t*>(base + o_arena);
-  t->block_sum = reinterpret_cast<int64_t*>(base + o_sum);
-  t->dir = reinterpret_cast<int64_t*>(base + o_dir);
-  t->blk_count = reinterpret_cast<uint32_t*>(base + o_count);
-  t->blk_first = reinterpret_cast<uint32_t*>(base + o_first);
-  t->scan_tmp = base + o_tmp;
-  t->heads = reinterpret_cast<DepthHead*>(base + o_heads);
-  t->carry = reinterpret_cast<DepthCarry*>(base + o_small);
-  t->status = reinterpret_cast<unsigned long long*>(base + o_small + 3 * sizeof(DepthCarry));
+  cv.place(t->arena_mem);
+  t->carry = reinterpret_cast<DepthCarry*>(small);
+  t->status = reinterpret_cast<unsigned long long*>(small + 3 * sizeof(DepthCarry));
   t->n_heads = reinterpret_cast<uint32_t*>(t->status + 2);
   // the carries and the head counters zero, the status words all ones
   MAGOT_HIP_TRY(hipMemsetAsync(t->carry, 0, 3 * sizeof(DepthCarry) + 64, ctx->stream));
@@ -155,10 +146,7 @@ int magot_depth_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t c
   // the first offending line, whichever check finds it
   uint64_t bad_line = ~0ull;
   uint32_t bad = 0;
-  if (status != ~0ull) {
-    bad_line = (uint64_t)(status >> 8);
-    bad = (uint32_t)(status & 0xff);
-  }
+  first_offence(status, &bad, &bad_line);
   if (line_long && last.lines < bad_line) {
     bad_line = last.lines;
     bad = MAGOT_DEPTH_LINE_LONG;
@@ -202,8 +190,7 @@ int magot_depth_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t c
                                        t->scan_bytes, ctx->stream));
   if (n_lines) *n_lines = t->n_lines;
   if (n_runs) *n_runs = t->runs.size();
-  guard.t = nullptr;
-  *out = t;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -259,35 +246,29 @@ int magot_depth_sums(magot_ctx* ctx, magot_depth* t, const int64_t* start, const
     }
   if (!n_rows && !n_groups) return MAGOT_OK;
   Carve cv;
-  const uint64_t o_start = cv.take<int64_t>(n_rows);
-  const uint64_t o_len = cv.take<int64_t>(n_rows);
-  const uint64_t o_sums = cv.take<int64_t>(n_rows);
-  const uint64_t o_off = cv.take<uint64_t>(n_groups + 1);
-  const uint64_t o_group = cv.take<int64_t>(n_groups);
+  int64_t *d_start, *d_len, *d_sums, *d_group;
+  uint64_t* d_off;
+  cv.take(&d_start, n_rows);
+  cv.take(&d_len, n_rows);
+  cv.take(&d_sums, n_rows);
+  cv.take(&d_off, n_groups + 1);
+  cv.take(&d_group, n_groups);
   DevBuf d;
   MAGOT_HIP_TRY(hipMalloc(&d.p, cv.used + 256));
-  char* base = static_cast<char*>(d.p);
-  int64_t* d_sums = reinterpret_cast<int64_t*>(base + o_sums);
+  cv.place(d.p);
   if (n_rows) {
-    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_start, start, n_rows * 8, hipMemcpyHostToDevice,
-                                 ctx->stream));
-    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_len, length, n_rows * 8, hipMemcpyHostToDevice,
-                                 ctx->stream));
+    MAGOT_HIP_TRY(hipMemcpyAsync(d_start, start, n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    MAGOT_HIP_TRY(hipMemcpyAsync(d_len, length, n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
   }
   if (n_groups)
-    MAGOT_HIP_TRY(hipMemcpyAsync(base + o_off, group_offsets, (n_groups + 1) * 8,
-                                 hipMemcpyHostToDevice, ctx->stream));
-  MAGOT_HIP_TRY(launch_depth_sums(t->arena, t->dir, t->n_lines,
-                                  reinterpret_cast<const int64_t*>(base + o_start),
-                                  reinterpret_cast<const int64_t*>(base + o_len), n_rows, d_sums,
+    MAGOT_HIP_TRY(hipMemcpyAsync(d_off, group_offsets, (n_groups + 1) * 8, hipMemcpyHostToDevice,
+                                 ctx->stream));
+  MAGOT_HIP_TRY(launch_depth_sums(t->arena, t->dir, t->n_lines, d_start, d_len, n_rows, d_sums,
                                   ctx->stream));
-  MAGOT_HIP_TRY(launch_depth_groups(d_sums, reinterpret_cast<const uint64_t*>(base + o_off),
-                                    n_groups, reinterpret_cast<int64_t*>(base + o_group),
-                                    ctx->stream));
+  MAGOT_HIP_TRY(launch_depth_groups(d_sums, d_off, n_groups, d_group, ctx->stream));
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (n_rows && sums) MAGOT_HIP_TRY(hipMemcpy(sums, d_sums, n_rows * 8, hipMemcpyDeviceToHost));
-  if (n_groups)
-    MAGOT_HIP_TRY(hipMemcpy(group_sums, base + o_group, n_groups * 8, hipMemcpyDeviceToHost));
+  if (n_groups) MAGOT_HIP_TRY(hipMemcpy(group_sums, d_group, n_groups * 8, hipMemcpyDeviceToHost));
   return MAGOT_OK;
 }
 
@@ -313,31 +294,25 @@ int magot_depth_time(magot_ctx* ctx, magot_depth* t, int iters, double* ms4,
     MAGOT_HIP_TRY(hipMemcpy(d.p, rows.data(), 2 * nr * 8, hipMemcpyHostToDevice));
   }
   int64_t* dr = static_cast<int64_t*>(d.p);
-  double total[4] = {0, 0, 0, 0};
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < 4; ++k) {
-      if (k < 2 && !ts.last_len) continue;
-      if (int rc = time_pass(ctx, &total[k], [&] {
-            switch (k) {
-              case 0:
-                return launch_depth_line_index(ts.dev[ts.last_slot], ts.last_len, t->blk_count,
-                                               t->blk_first, t->scan_tmp, t->scan_bytes,
-                                               ctx->stream);
-              case 1:  // the same depths into the same lines; heads, status and carry into scratch
-                return launch_depth_parse(depth_args(t, ts.last_slot, ts.last_len, ts.last_off,
-                                                     ts.last_in, 2, true), ctx->stream);
-              case 2:
-                return launch_depth_directory(t->arena, t->n_lines, t->block_sum, t->dir,
-                                              t->scan_tmp, t->scan_bytes, ctx->stream);
-              default:
-                return launch_depth_sums(t->arena, t->dir, t->n_lines, dr, dr + nr, nr,
-                                         dr + 2 * nr, ctx->stream);
-            }
-          }))
-        return rc;
-    }
-  for (int k = 0; k < 4; ++k) ms4[k] = total[k] / iters;
-  return MAGOT_OK;
+  return time_passes(
+      ctx, iters, 4, ms4,
+      [&](int k) {
+        switch (k) {
+          case 0:
+            return launch_depth_line_index(ts.dev[ts.last_slot], ts.last_len, t->blk_count,
+                                           t->blk_first, t->scan_tmp, t->scan_bytes, ctx->stream);
+          case 1:  // the same depths into the same lines; heads, status and carry into scratch
+            return launch_depth_parse(depth_args(t, ts.last_slot, ts.last_len, ts.last_off,
+                                                 ts.last_in, 2, true), ctx->stream);
+          case 2:
+            return launch_depth_directory(t->arena, t->n_lines, t->block_sum, t->dir,
+                                          t->scan_tmp, t->scan_bytes, ctx->stream);
+          default:
+            return launch_depth_sums(t->arena, t->dir, t->n_lines, dr, dr + nr, nr, dr + 2 * nr,
+                                     ctx->stream);
+        }
+      },
+      [&](int k) { return k < 2 && !ts.last_len; });  // an empty text left no chunk
 }
 
 }  // extern "C"
@@ -409,11 +384,8 @@ int magot_fq_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t chun
     return MAGOT_ERR_ARG;
   }
   *out = nullptr;
-  struct Guard {
-    magot_fq* t;
-    ~Guard() { magot_fq_destroy(t); }
-  } guard{new magot_fq()};
-  magot_fq* t = guard.t;
+  Building<magot_fq, magot_fq_destroy> guard{new magot_fq()};
+  magot_fq* t = guard.p;
   t->ctx = ctx;
   t->file_bytes = len;
   const uint64_t chunk = text_chunk_bytes(chunk_bytes, len);
@@ -422,27 +394,21 @@ int magot_fq_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t chun
   t->scan_bytes = fq_scan_bytes(text_blocks + 1, t->longs_cap + kFqDense);
   t->sort_bytes = fq_sort_bytes(t->longs_cap);
   Carve cv;
-  const uint64_t o_hist = cv.take<unsigned long long>(kFqDense);
-  const uint64_t o_longs = cv.take<int64_t>(2 * t->longs_cap);
-  const uint64_t o_blk = cv.take<FqBlock>(text_blocks + 1);
-  const uint64_t o_pre = cv.take<FqBlock>(text_blocks + 1);
-  const uint64_t o_cum = cv.take<FqItem>(t->longs_cap + kFqDense);
-  const uint64_t o_scan = cv.take<uint8_t>(t->scan_bytes);
-  const uint64_t o_sort = cv.take<uint8_t>(t->sort_bytes);
-  const uint64_t o_small = cv.take<uint8_t>(256);
+  uint8_t* small_block;
+  cv.take(&t->hist, kFqDense);
+  cv.take(&t->longs, 2 * t->longs_cap);
+  cv.take(&t->blk, text_blocks + 1);
+  cv.take(&t->pre, text_blocks + 1);
+  cv.take(&t->cum, t->longs_cap + kFqDense);
+  cv.take(&t->scan_tmp, t->scan_bytes);
+  cv.take(&t->sort_tmp, t->sort_bytes);
+  cv.take(&small_block, 256);
   MAGOT_HIP_TRY(hipMalloc(&t->mem, cv.used + 256));
-  char* base = static_cast<char*>(t->mem);
-  t->hist = reinterpret_cast<unsigned long long*>(base + o_hist);
-  t->longs = reinterpret_cast<int64_t*>(base + o_longs);
-  t->blk = reinterpret_cast<FqBlock*>(base + o_blk);
-  t->pre = reinterpret_cast<FqBlock*>(base + o_pre);
-  t->cum = reinterpret_cast<FqItem*>(base + o_cum);
-  t->scan_tmp = base + o_scan;
-  t->sort_tmp = base + o_sort;
+  cv.place(t->mem);
   // 256 bytes: three carries, the list's cursor, the nine result words twice
   static_assert(3 * sizeof(FqCarry) + 8 + 18 * 8 <= 256, "the small block");
-  t->carry = reinterpret_cast<FqCarry*>(base + o_small);
-  t->cursor = reinterpret_cast<unsigned long long*>(base + o_small + 3 * sizeof(FqCarry));
+  t->carry = reinterpret_cast<FqCarry*>(small_block);
+  t->cursor = reinterpret_cast<unsigned long long*>(small_block + 3 * sizeof(FqCarry));
   t->out = reinterpret_cast<uint64_t*>(t->cursor + 1);
   struct {
     FqCarry carry[3];
@@ -491,8 +457,7 @@ int magot_fq_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t chun
   MAGOT_HIP_TRY(launch_fq_reduce(r, t->scan_tmp, t->scan_bytes, ctx->stream));
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   MAGOT_HIP_TRY(hipMemcpy(t->stats, t->out, sizeof(t->stats), hipMemcpyDeviceToHost));
-  guard.t = nullptr;
-  *out = t;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -557,19 +522,17 @@ int magot_fq_time(magot_ctx* ctx, magot_fq* t, int iters, double* ms4, uint64_t*
   if (chunk_len) *chunk_len = ts.last_len;
   // a histogram, a list and a cursor of their own for the timed length pass,
   // and the copy's target
+  FqChunkArgs a = fq_args(t, ts.last_slot, ts.last_len, ts.last_off, ts.last_in, 2);
   Carve cv;
-  const uint64_t o_hist = cv.take<unsigned long long>(kFqDense);
-  const uint64_t o_longs = cv.take<int64_t>(t->longs_cap);
-  const uint64_t o_cursor = cv.take<unsigned long long>(1);
-  const uint64_t o_copy = cv.take<uint8_t>(ts.last_len);
+  uint8_t* copy;
+  cv.take(&a.hist, kFqDense);
+  cv.take(&a.longs, t->longs_cap);
+  cv.take(&a.n_longs, 1);
+  const uint64_t o_copy = cv.take(&copy, ts.last_len);
   DevBuf d;
   MAGOT_HIP_TRY(hipMalloc(&d.p, cv.used + 256));
-  char* base = static_cast<char*>(d.p);
-  MAGOT_HIP_TRY(hipMemsetAsync(base, 0, o_copy, ctx->stream));
-  FqChunkArgs a = fq_args(t, ts.last_slot, ts.last_len, ts.last_off, ts.last_in, 2);
-  a.hist = reinterpret_cast<unsigned long long*>(base + o_hist);
-  a.longs = reinterpret_cast<int64_t*>(base + o_longs);
-  a.n_longs = reinterpret_cast<unsigned long long*>(base + o_cursor);
+  cv.place(d.p);
+  MAGOT_HIP_TRY(hipMemsetAsync(d.p, 0, o_copy, ctx->stream));  // all but the copy's target
   FqReduceArgs r{};
   r.hist = t->hist;
   r.longs = t->longs + t->longs_cap;
@@ -593,7 +556,7 @@ int magot_fq_time(magot_ctx* ctx, magot_fq* t, int iters, double* ms4, uint64_t*
                   return e;
                 return launch_fq_reduce(r, t->scan_tmp, t->scan_bytes, ctx->stream);
               default:
-                return hipMemcpyAsync(base + o_copy, ts.dev[ts.last_slot], ts.last_len,
+                return hipMemcpyAsync(copy, ts.dev[ts.last_slot], ts.last_len,
                                       hipMemcpyDeviceToDevice, ctx->stream);
             }
           }))

@@ -105,11 +105,8 @@ int magot_track_create(magot_ctx* ctx, const magot_genome* g, magot_track** out,
     return MAGOT_ERR_ARG;
   }
   *out = nullptr;
-  struct Guard {
-    magot_track* t;
-    ~Guard() { magot_track_destroy(t); }
-  } guard{new magot_track()};
-  magot_track* t = guard.t;
+  Building<magot_track, magot_track_destroy> guard{new magot_track()};
+  magot_track* t = guard.p;
   t->ctx = ctx;
   t->g = g;
   t->n_words = g->span / 32;
@@ -118,28 +115,21 @@ int magot_track_create(magot_ctx* ctx, const magot_genome* g, magot_track** out,
   t->scan_bytes = track_scan_bytes(t->n_blocks + 1);
   const uint64_t nc = g->contig_base.size();
   Carve cv;
-  const uint64_t o_words = cv.take<uint32_t>(t->plane_words);
-  const uint64_t o_scratch = cv.take<uint32_t>(t->plane_words);
-  const uint64_t o_base = cv.take<uint64_t>(nc + 1);
-  const uint64_t o_count = cv.take<uint32_t>(t->n_blocks + 1);
-  const uint64_t o_rank = cv.take<uint32_t>(t->n_blocks + 1);
-  const uint64_t o_tmp = cv.take<uint8_t>(t->scan_bytes);
+  cv.take(&t->words, t->plane_words);
+  cv.take(&t->scratch, t->plane_words);
+  cv.take(&t->contig_base, nc + 1);
+  cv.take(&t->blk_count, t->n_blocks + 1);
+  cv.take(&t->blk_rank, t->n_blocks + 1);
+  cv.take(&t->scan_tmp, t->scan_bytes);
   MAGOT_HIP_TRY(hipMalloc(&t->arena, cv.used + 256));
-  char* base = static_cast<char*>(t->arena);
-  t->words = reinterpret_cast<uint32_t*>(base + o_words);
-  t->scratch = reinterpret_cast<uint32_t*>(base + o_scratch);
-  t->contig_base = reinterpret_cast<uint64_t*>(base + o_base);
-  t->blk_count = reinterpret_cast<uint32_t*>(base + o_count);
-  t->blk_rank = reinterpret_cast<uint32_t*>(base + o_rank);
-  t->scan_tmp = base + o_tmp;
+  cv.place(t->arena);
   // both planes zeroed whole: no pass writes a word at or past n_words
   MAGOT_HIP_TRY(hipMemsetAsync(t->words, 0, 2 * ((t->plane_words * 4 + 255) & ~255ull),
                                ctx->stream));
   if (nc)
     MAGOT_HIP_TRY(hipMemcpy(t->contig_base, g->contig_base.data(), nc * 8, hipMemcpyHostToDevice));
   if (n_words) *n_words = t->n_words;
-  guard.t = nullptr;
-  *out = t;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -267,43 +257,36 @@ int magot_track_windows_create(magot_ctx* ctx, magot_track* t, uint64_t window, 
     if (len > window && !(skip && skip[c])) total += (len - window) / jump;
   }
   tab[nc] = total;
-  struct Guard {
-    magot_track_windows* w;
-    ~Guard() { magot_track_windows_destroy(w); }
-  } guard{new magot_track_windows()};
-  magot_track_windows* w = guard.w;
+  Building<magot_track_windows, magot_track_windows_destroy> guard{new magot_track_windows()};
+  magot_track_windows* w = guard.p;
   w->ctx = ctx;
   w->t = t;
   const uint64_t groups = track_flip_groups(total);
   w->scan_bytes = track_scan_bytes(groups + 1);
-  Carve cv;
-  const uint64_t o_first = cv.take<uint64_t>(nc + 1);
-  const uint64_t o_sums = cv.take<uint32_t>(total);
-  const uint64_t o_fc = cv.take<uint32_t>(groups + 1);
-  const uint64_t o_fs = cv.take<uint64_t>(groups + 1);
-  const uint64_t o_tmp = cv.take<uint8_t>(w->scan_bytes);
-  MAGOT_HIP_TRY(hipMalloc(&w->arena, cv.used + 256));
-  char* base = static_cast<char*>(w->arena);
-  MAGOT_HIP_TRY(hipMemcpy(base + o_first, tab.data(), (nc + 1) * 8, hipMemcpyHostToDevice));
   TrackWindowArgs& a = w->a;
+  Carve cv;
+  uint64_t* d_first;  // uploaded into; the kernels read it as const
+  cv.take(&d_first, nc + 1);
+  cv.take(&a.sums, total);
+  cv.take(&a.flip_count, groups + 1);
+  cv.take(&a.flip_slot, groups + 1);
+  cv.take(&w->scan_tmp, w->scan_bytes);
+  MAGOT_HIP_TRY(hipMalloc(&w->arena, cv.used + 256));
+  cv.place(w->arena);
+  MAGOT_HIP_TRY(hipMemcpy(d_first, tab.data(), (nc + 1) * 8, hipMemcpyHostToDevice));
   a.track = t->words;
   a.rank = t->blk_rank;
   a.contig_base = t->contig_base;
-  a.first = reinterpret_cast<const uint64_t*>(base + o_first);
+  a.first = d_first;
   a.n_contigs = nc;
   a.n_windows = total;
   a.W = window;
   a.jump = jump;
-  a.sums = reinterpret_cast<uint32_t*>(base + o_sums);
-  a.flip_count = reinterpret_cast<uint32_t*>(base + o_fc);
-  a.flip_slot = reinterpret_cast<uint64_t*>(base + o_fs);
-  w->scan_tmp = base + o_tmp;
   if (int rc = track_rank_ready(ctx, t)) return rc;
   MAGOT_HIP_TRY(launch_track_windows(a, ctx->stream));
   if (n_windows) *n_windows = total;
   if (first) memcpy(first, tab.data(), (nc + 1) * 8);
-  guard.w = nullptr;
-  *out = w;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -420,35 +403,30 @@ int magot_track_time(magot_ctx* ctx, magot_track* t, magot_track_windows* w, uin
   if (w) {  // sizes the index list for this s_min
     if (int rc = magot_track_transitions(ctx, w, s_min, &cap)) return rc;
   }
-  double total[5] = {0, 0, 0, 0, 0};
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < 5; ++k) {
-      if (k >= 2 && k <= 3 && !w) continue;
-      if (int rc = time_pass(ctx, &total[k], [&] {
-            switch (k) {
-              case 0:  // into the scratch plane: the track keeps its bits
-                return launch_track_class(t->g->nib, t->n_words, kOrigin, t->g->extent, false,
-                                          true, t->scratch, ctx->stream);
-              case 1:
-                return launch_track_rank(t->words, t->n_blocks, t->blk_count, t->blk_rank,
-                                         t->scan_tmp, t->scan_bytes, ctx->stream);
-              case 2:
-                return launch_track_windows(w->a, ctx->stream);
-              case 3:
-                if (hipError_t e = launch_track_flip_count(w->a, s_min, w->scan_tmp,
-                                                           w->scan_bytes, ctx->stream))
-                  return e;
-                return launch_track_flip_write(w->a, s_min, cap, ctx->stream);
-              default:
-                return launch_track_count(static_cast<const magot_mask_interval*>(d.p),
-                                          rows.size(), t->contig_base, t->words, t->blk_rank,
-                                          t->g->span, static_cast<uint32_t*>(o.p), ctx->stream);
-            }
-          }))
-        return rc;
-    }
-  for (int k = 0; k < 5; ++k) ms5[k] = total[k] / iters;
-  return MAGOT_OK;
+  return time_passes(
+      ctx, iters, 5, ms5,
+      [&](int k) {
+        switch (k) {
+          case 0:  // into the scratch plane: the track keeps its bits
+            return launch_track_class(t->g->nib, t->n_words, kOrigin, t->g->extent, false, true,
+                                      t->scratch, ctx->stream);
+          case 1:
+            return launch_track_rank(t->words, t->n_blocks, t->blk_count, t->blk_rank,
+                                     t->scan_tmp, t->scan_bytes, ctx->stream);
+          case 2:
+            return launch_track_windows(w->a, ctx->stream);
+          case 3:
+            if (hipError_t e = launch_track_flip_count(w->a, s_min, w->scan_tmp, w->scan_bytes,
+                                                       ctx->stream))
+              return e;
+            return launch_track_flip_write(w->a, s_min, cap, ctx->stream);
+          default:
+            return launch_track_count(static_cast<const magot_mask_interval*>(d.p), rows.size(),
+                                      t->contig_base, t->words, t->blk_rank, t->g->span,
+                                      static_cast<uint32_t*>(o.p), ctx->stream);
+        }
+      },
+      [&](int k) { return k >= 2 && k <= 3 && !w; });  // no window set was given
 }
 
 }  // extern "C"

@@ -27,18 +27,8 @@ namespace {
 
 constexpr int kVcfPasses = 8;
 
-int vcf_decline(uint32_t* reason, uint64_t* line, uint32_t why, uint64_t at) {
-  if (reason) *reason = why;
-  if (line) *line = at;
-  set_error("magot_vcf_parse: input outside the device path; use the host functions");
-  return MAGOT_ERR_UNSUPPORTED;
-}
-
-template <class T>
-int vcf_fetch(T* dst, const T* src, uint64_t n) {
-  if (dst && n) MAGOT_HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
-  return MAGOT_OK;
-}
+constexpr char kOutside[] =
+    "magot_vcf_parse: input outside the device path; use the host functions";
 
 // the span of 0-based line k without its LF
 int vcf_line_span(const magot_vcf* p, const char* host_text, uint64_t k, uint64_t* off,
@@ -108,13 +98,10 @@ int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max
   if (!max_samples || max_samples > kVcfMaxSamples) max_samples = kVcfMaxSamples;
   if (!max_runs || max_runs > kVcfMaxRuns) max_runs = kVcfMaxRuns;
   if (int rc = resident_text_budget(&max_bytes)) return rc;
-  if (len > max_bytes) return vcf_decline(reason, line, MAGOT_VCF_TOO_LARGE, 0);
-  if (!len) return vcf_decline(reason, line, MAGOT_VCF_NO_HEADER, 0);
+  if (len > max_bytes) return decline(kOutside, reason, line, MAGOT_VCF_TOO_LARGE, 0);
+  if (!len) return decline(kOutside, reason, line, MAGOT_VCF_NO_HEADER, 0);
 
-  struct Guard {
-    magot_vcf* p;
-    ~Guard() { magot_vcf_destroy(p); }
-  } guard{new magot_vcf()};
+  Building<magot_vcf, magot_vcf_destroy> guard{new magot_vcf()};
   magot_vcf* p = guard.p;
   p->ctx = ctx;
   TextIndexArgs& ix = p->ix;
@@ -122,31 +109,29 @@ int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max
   hipStream_t s = ctx->stream;
   {
     Carve cv;  // the caller's slices: eight status words and last_line
-    const uint64_t o_status = cv.take<unsigned long long>(8);
-    const uint64_t o_last = cv.take<uint32_t>(1);
+    cv.take(&a.status, 8);
+    cv.take(&p->last_line, 1);
     if (int rc = resident_text_open(ctx, text, len, '\n', kTextNoByte, cv.used, &p->rt, &ix))
       return rc;
+    cv.place(p->rt.extra);
     a.text = ix.text;
     a.n = len;
-    a.status = reinterpret_cast<unsigned long long*>(p->rt.extra + o_status);
-    p->last_line = reinterpret_cast<uint32_t*>(p->rt.extra + o_last);
     ix.n_lines = p->rt.n_lines;
-    if (ix.n_lines > kPslLineMask) return vcf_decline(reason, line, MAGOT_VCF_TOO_MANY_LINES, 0);
+    if (ix.n_lines > kPslLineMask)
+      return decline(kOutside, reason, line, MAGOT_VCF_TOO_MANY_LINES, 0);
   }
   const uint64_t L = a.n_lines = ix.n_lines;  // at least 1
   a.final_lf = text[len - 1] == '\n' ? 1 : 0;
   {
     p->tmp_bytes = vcf_tmp_bytes(L);
     Carve cv;
-    const uint64_t o_start = cv.take<uint64_t>(L + 1);
-    const uint64_t o_kind = cv.take<uint64_t>(L + 1), o_kpos = cv.take<uint64_t>(L + 1);
-    const uint64_t o_tmp = cv.take<uint8_t>(p->tmp_bytes);
+    cv.take(&ix.pos, L + 1);
+    cv.take(&a.kind, L + 1);
+    cv.take(&a.kpos, L + 1);
+    cv.take(&p->tmp, p->tmp_bytes);
     MAGOT_HIP_TRY(hipMalloc(&p->mem, cv.used + 256));
-    char* base = static_cast<char*>(p->mem);
-    a.line_start = ix.pos = reinterpret_cast<uint64_t*>(base + o_start);
-    a.kind = reinterpret_cast<uint64_t*>(base + o_kind);
-    a.kpos = reinterpret_cast<uint64_t*>(base + o_kpos);
-    p->tmp = base + o_tmp;
+    cv.place(p->mem);
+    a.line_start = ix.pos;
   }
   MAGOT_HIP_TRY(launch_text_fill(ix, kTextFillLines, s));
   MAGOT_HIP_TRY(launch_vcf_classify(a, p->tmp, p->tmp_bytes, s));
@@ -157,55 +142,45 @@ int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
   a.n_data = totals & 0xffffffffull;
   a.n_hdr = totals >> 32;
-  if (st[4]) return vcf_decline(reason, line, MAGOT_VCF_CARRIAGE_RETURN, 0);
-  if (st[1] == 0) return vcf_decline(reason, line, MAGOT_VCF_NO_HEADER, 0);
-  if (st[1] > 1) return vcf_decline(reason, line, MAGOT_VCF_MANY_HEADERS, 0);
-  if (!a.n_data) return vcf_decline(reason, line, MAGOT_VCF_NO_DATA, 0);
-  if (st[3] < st[2]) return vcf_decline(reason, line, MAGOT_VCF_HEADER_AFTER_DATA, st[3] + 1);
+  if (st[4]) return decline(kOutside, reason, line, MAGOT_VCF_CARRIAGE_RETURN, 0);
+  if (st[1] == 0) return decline(kOutside, reason, line, MAGOT_VCF_NO_HEADER, 0);
+  if (st[1] > 1) return decline(kOutside, reason, line, MAGOT_VCF_MANY_HEADERS, 0);
+  if (!a.n_data) return decline(kOutside, reason, line, MAGOT_VCF_NO_DATA, 0);
+  if (st[3] < st[2])
+    return decline(kOutside, reason, line, MAGOT_VCF_HEADER_AFTER_DATA, st[3] + 1);
   // S from the '#' line: the fields of the text behind '#', less nine
   if (int rc = vcf_line_span(p, text, st[2], &p->head_off, &p->head_len)) return rc;
   uint64_t fields = 1;
   for (uint64_t i = 1; i < p->head_len; ++i) fields += text[p->head_off + i] == '\t';
-  if (fields < 10) return vcf_decline(reason, line, MAGOT_VCF_NO_SAMPLES, st[2] + 1);
-  if (fields - 9 > max_samples) return vcf_decline(reason, line, MAGOT_VCF_TOO_MANY_SAMPLES, st[2] + 1);
+  if (fields < 10) return decline(kOutside, reason, line, MAGOT_VCF_NO_SAMPLES, st[2] + 1);
+  if (fields - 9 > max_samples)
+    return decline(kOutside, reason, line, MAGOT_VCF_TOO_MANY_SAMPLES, st[2] + 1);
   a.n_samples = (uint32_t)(fields - 9);
   a.words = (a.n_samples + 31) / 32;
   {
     const uint64_t D = a.n_data;
     Carve cv;
-    const uint64_t o_dl = cv.take<uint32_t>(D), o_ho = cv.take<uint64_t>(a.n_hdr + 1);
-    const uint64_t o_hn = cv.take<uint64_t>(a.n_hdr + 1);
-    const uint64_t o_pos = cv.take<int32_t>(D), o_hash = cv.take<uint64_t>(D);
-    const uint64_t o_cl = cv.take<uint32_t>(D);
-    const uint64_t o_head = cv.take<uint32_t>(D + 1), o_run = cv.take<uint32_t>(D + 1);
-    const uint64_t o_bits = cv.take<uint32_t>(D * a.words);
-    const uint64_t o_roff = cv.take<uint64_t>(max_runs), o_rlen = cv.take<uint64_t>(max_runs);
-    const uint64_t o_cor = cv.take<uint32_t>(max_runs);
-    const uint64_t o_key = cv.take<uint64_t>(D), o_key2 = cv.take<uint64_t>(D);
-    const uint64_t o_val = cv.take<uint32_t>(D), o_val2 = cv.take<uint32_t>(D);
-    const uint64_t o_ks = cv.take<uint8_t>(D), o_kept = cv.take<uint8_t>(D);
-    const uint64_t o_first = cv.take<uint8_t>(D);
+    cv.take(&a.data_line, D);
+    cv.take(&a.hdr_off, a.n_hdr + 1);
+    cv.take(&a.hdr_len, a.n_hdr + 1);
+    cv.take(&a.pos, D);
+    cv.take(&a.hash, D);
+    cv.take(&a.chrom_len, D);
+    cv.take(&a.head, D + 1);
+    cv.take(&a.run, D + 1);
+    cv.take(&a.bits, D * a.words);
+    cv.take(&a.run_off, max_runs);
+    cv.take(&a.run_len, max_runs);
+    cv.take(&a.contig_of_run, max_runs);
+    cv.take(&a.key, D);
+    cv.take(&a.key_sorted, D);
+    cv.take(&a.val, D);
+    cv.take(&a.val_sorted, D);
+    cv.take(&a.kept_sorted, D);
+    cv.take(&a.kept, D);
+    cv.take(&a.first, D);
     MAGOT_HIP_TRY(hipMalloc(&p->data_mem, cv.used + 256));
-    char* base = static_cast<char*>(p->data_mem);
-    a.data_line = reinterpret_cast<uint32_t*>(base + o_dl);
-    a.hdr_off = reinterpret_cast<uint64_t*>(base + o_ho);
-    a.hdr_len = reinterpret_cast<uint64_t*>(base + o_hn);
-    a.pos = reinterpret_cast<int32_t*>(base + o_pos);
-    a.hash = reinterpret_cast<uint64_t*>(base + o_hash);
-    a.chrom_len = reinterpret_cast<uint32_t*>(base + o_cl);
-    a.head = reinterpret_cast<uint32_t*>(base + o_head);
-    a.run = reinterpret_cast<uint32_t*>(base + o_run);
-    a.bits = reinterpret_cast<uint32_t*>(base + o_bits);
-    a.run_off = reinterpret_cast<uint64_t*>(base + o_roff);
-    a.run_len = reinterpret_cast<uint64_t*>(base + o_rlen);
-    a.contig_of_run = reinterpret_cast<const uint32_t*>(base + o_cor);
-    a.key = reinterpret_cast<uint64_t*>(base + o_key);
-    a.key_sorted = reinterpret_cast<uint64_t*>(base + o_key2);
-    a.val = reinterpret_cast<uint32_t*>(base + o_val);
-    a.val_sorted = reinterpret_cast<uint32_t*>(base + o_val2);
-    a.kept_sorted = reinterpret_cast<uint8_t*>(base + o_ks);
-    a.kept = reinterpret_cast<uint8_t*>(base + o_kept);
-    a.first = reinterpret_cast<uint8_t*>(base + o_first);
+    cv.place(p->data_mem);
     MAGOT_HIP_TRY(hipMemsetAsync(a.kept, 0, D, s));
     MAGOT_HIP_TRY(hipMemsetAsync(a.first, 0, D, s));
   }
@@ -216,14 +191,12 @@ int magot_vcf_parse(magot_ctx* ctx, const char* text, uint64_t len, uint64_t max
   MAGOT_HIP_TRY(hipMemcpyAsync(st, a.status, 8, hipMemcpyDeviceToHost, s));
   MAGOT_HIP_TRY(hipMemcpyAsync(&n_runs, a.run + a.n_data, 4, hipMemcpyDeviceToHost, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
-  if (st[0] != ~0ull)
-    return vcf_decline(reason, line, (uint32_t)(st[0] & 0xff), (st[0] >> 8) + 1);
-  if (n_runs > max_runs) return vcf_decline(reason, line, MAGOT_VCF_TOO_MANY_RUNS, 0);
+  if (int rc = decline_if_offended(kOutside, reason, line, st[0])) return rc;
+  if (n_runs > max_runs) return decline(kOutside, reason, line, MAGOT_VCF_TOO_MANY_RUNS, 0);
   a.n_runs = n_runs;  // the run tables hold max_runs
   MAGOT_HIP_TRY(launch_vcf_runs(a, s));
   MAGOT_HIP_TRY(hipStreamSynchronize(s));
-  guard.p = nullptr;
-  *out = p;
+  *out = guard.release();
   return MAGOT_OK;
 }
 
@@ -250,15 +223,15 @@ double magot_vcf_upload_ms(const magot_vcf* p) { return p ? (double)p->rt.upload
 int magot_vcf_header_lines(magot_ctx* ctx, magot_vcf* p, uint64_t* off, uint64_t* len) {
   if (int rc = handle_of(ctx, p, "magot_vcf_header_lines", "handle")) return rc;
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (int rc = vcf_fetch(off, p->a.hdr_off, p->a.n_hdr)) return rc;
-  return vcf_fetch(len, p->a.hdr_len, p->a.n_hdr);
+  if (int rc = fetch_rows(off, p->a.hdr_off, p->a.n_hdr)) return rc;
+  return fetch_rows(len, p->a.hdr_len, p->a.n_hdr);
 }
 
 int magot_vcf_runs(magot_ctx* ctx, magot_vcf* p, uint64_t* off, uint64_t* len) {
   if (int rc = handle_of(ctx, p, "magot_vcf_runs", "handle")) return rc;
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (int rc = vcf_fetch(off, p->a.run_off, p->a.n_runs)) return rc;
-  return vcf_fetch(len, p->a.run_len, p->a.n_runs);
+  if (int rc = fetch_rows(off, p->a.run_off, p->a.n_runs)) return rc;
+  return fetch_rows(len, p->a.run_len, p->a.n_runs);
 }
 
 int magot_vcf_resolve(magot_ctx* ctx, magot_vcf* p, const uint32_t* contig, uint64_t n_runs) {
@@ -289,12 +262,12 @@ int magot_vcf_tables(magot_ctx* ctx, magot_vcf* p, uint32_t* line, int32_t* pos,
   MAGOT_HIP_TRY(hipStreamSynchronize(ctx->stream));
   const VcfArgs& a = p->a;
   const uint64_t n = a.n_data;
-  if (int rc = vcf_fetch(line, a.data_line, n)) return rc;
-  if (int rc = vcf_fetch(pos, a.pos, n)) return rc;
-  if (int rc = vcf_fetch(hash, a.hash, n)) return rc;
-  if (int rc = vcf_fetch(kept, a.kept, n)) return rc;
-  if (int rc = vcf_fetch(first, a.first, n)) return rc;
-  return vcf_fetch(bits, a.bits, n * a.words);
+  if (int rc = fetch_rows(line, a.data_line, n)) return rc;
+  if (int rc = fetch_rows(pos, a.pos, n)) return rc;
+  if (int rc = fetch_rows(hash, a.hash, n)) return rc;
+  if (int rc = fetch_rows(kept, a.kept, n)) return rc;
+  if (int rc = fetch_rows(first, a.first, n)) return rc;
+  return fetch_rows(bits, a.bits, n * a.words);
 }
 
 int magot_vcf_last_of(magot_ctx* ctx, magot_vcf* p, uint64_t d, uint64_t* line, uint64_t* off,
@@ -343,30 +316,24 @@ int magot_vcf_count(magot_ctx* ctx, magot_vcf* p, const uint32_t* contig, const 
   c.n_loci = n_loci;
   p->ctmp_bytes = vcf_count_tmp_bytes(n_loci);
   Carve cv;
-  const uint64_t o_c = cv.take<uint32_t>(n_loci), o_lo = cv.take<uint32_t>(n_loci);
-  const uint64_t o_hi = cv.take<uint32_t>(n_loci);
-  const uint64_t o_b = cv.take<uint64_t>(n_loci), o_e = cv.take<uint64_t>(n_loci);
-  const uint64_t o_pc = cv.take<uint64_t>(n_loci + 1), o_po = cv.take<uint64_t>(n_loci + 1);
-  const uint64_t o_al = cv.take<uint32_t>(a.words), o_fg = cv.take<uint32_t>(1);
-  const uint64_t o_cnt = cv.take<uint32_t>(n_loci * a.n_samples);
-  const uint64_t o_tmp = cv.take<uint8_t>(p->ctmp_bytes);
+  uint32_t *d_c, *d_lo, *d_hi, *d_al;  // uploaded into; the kernels read them as const
+  cv.take(&d_c, n_loci);
+  cv.take(&d_lo, n_loci);
+  cv.take(&d_hi, n_loci);
+  cv.take(&c.rng_b, n_loci);
+  cv.take(&c.rng_e, n_loci);
+  cv.take(&c.pieces, n_loci + 1);
+  cv.take(&c.piece_off, n_loci + 1);
+  cv.take(&d_al, a.words);
+  cv.take(&c.foreign, 1);
+  cv.take(&c.counts, n_loci * a.n_samples);
+  cv.take(&p->ctmp, p->ctmp_bytes);
   MAGOT_HIP_TRY(hipMalloc(&p->loci_mem, cv.used + 256));
-  char* base = static_cast<char*>(p->loci_mem);
-  uint32_t* d_c = reinterpret_cast<uint32_t*>(base + o_c);
-  uint32_t* d_lo = reinterpret_cast<uint32_t*>(base + o_lo);
-  uint32_t* d_hi = reinterpret_cast<uint32_t*>(base + o_hi);
-  uint32_t* d_al = reinterpret_cast<uint32_t*>(base + o_al);
+  cv.place(p->loci_mem);
   c.contig = d_c;
   c.lo = d_lo;
   c.hi = d_hi;
   c.allowed = d_al;
-  c.rng_b = reinterpret_cast<uint64_t*>(base + o_b);
-  c.rng_e = reinterpret_cast<uint64_t*>(base + o_e);
-  c.pieces = reinterpret_cast<uint64_t*>(base + o_pc);
-  c.piece_off = reinterpret_cast<uint64_t*>(base + o_po);
-  c.foreign = reinterpret_cast<uint32_t*>(base + o_fg);
-  c.counts = reinterpret_cast<uint32_t*>(base + o_cnt);
-  p->ctmp = base + o_tmp;
   hipStream_t s = ctx->stream;
   MAGOT_HIP_TRY(hipMemcpyAsync(d_c, contig, n_loci * 4, hipMemcpyHostToDevice, s));
   MAGOT_HIP_TRY(hipMemcpyAsync(d_lo, lo, n_loci * 4, hipMemcpyHostToDevice, s));
@@ -397,14 +364,8 @@ int magot_vcf_time(magot_ctx* ctx, magot_vcf* p, int iters, double* ms8, uint64_
   if (text_bytes) *text_bytes = p->a.n;
   if (!p->copy_mem) MAGOT_HIP_TRY(hipMalloc(&p->copy_mem, p->a.n + 256));
   // every pass writes what it wrote before: the answers stand
-  double total[kVcfPasses] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < iters; ++i)
-    for (int k = 0; k < kVcfPasses; ++k)
-      if (int rc = time_pass(ctx, &total[k],
-                             [&]() -> hipError_t { return vcf_pass(p, k, ctx->stream); }))
-        return rc;
-  for (int k = 0; k < kVcfPasses; ++k) ms8[k] = total[k] / iters;
-  return MAGOT_OK;
+  return time_passes(ctx, iters, kVcfPasses, ms8,
+                     [&](int k) { return vcf_pass(p, k, ctx->stream); });
 }
 
 }  // extern "C"

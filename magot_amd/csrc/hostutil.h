@@ -1,6 +1,6 @@
 // Host-side helpers shared by the translation units that plan on the CPU
 // (the abi*.hip units, tileplan.cpp): lap timing, the thread count,
-// range-parallel loops and uninitialised arrays.  No HIP here.
+// range-parallel loops, the slice carve and uninitialised arrays.  No HIP here.
 #pragma once
 
 #include <algorithm>
@@ -71,6 +71,44 @@ inline int py2_float_str(double v, char* out) {
   }
   return n;
 }
+
+// Sub-allocate 256-byte aligned slices of one allocation.  take<T>(count) gives
+// a slice's offset, for the sites whose offsets are themselves the product;
+// take(&field, count) sizes the slice from the field's own type and records the
+// field, and place(base) sets every recorded field to base + its offset and
+// forgets them.  A recorded field must not move between the two.
+struct Carve {
+  uint64_t used = 0;
+  template <class T>
+  uint64_t take(uint64_t count) {
+    uint64_t at = used;
+    used += (count * sizeof(T) + 255) & ~255ull;
+    return at;
+  }
+  template <class T>
+  uint64_t take(T** field, uint64_t count) {
+    const uint64_t at = take<T>(count);
+    slots.push_back({field, at, [](void* f, char* p) { *static_cast<T**>(f) = reinterpret_cast<T*>(p); }});
+    return at;
+  }
+  uint64_t take(void** field, uint64_t bytes) {  // untyped scratch: a slice of bytes
+    const uint64_t at = take<uint8_t>(bytes);
+    slots.push_back({field, at, [](void* f, char* p) { *static_cast<void**>(f) = p; }});
+    return at;
+  }
+  void place(void* base) {
+    for (const Slot& s : slots) s.set(s.field, static_cast<char*>(base) + s.at);
+    slots.clear();
+  }
+
+ private:
+  struct Slot {
+    void* field;
+    uint64_t at;
+    void (*set)(void*, char*);  // writes the field through its own type
+  };
+  std::vector<Slot> slots;
+};
 
 // A host array left uninitialised (POD rows the planner writes itself, in
 // parallel: no sequential zero fill, and its pages fault in on the writing threads).
