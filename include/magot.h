@@ -608,6 +608,7 @@ void magot_orfcall_destroy(magot_orfcall* c);
 #define MAGOT_GFF_LONGEST 4u
 #define MAGOT_GFF_GENOMIC 8u
 #define MAGOT_GFF_FROM_EXONS 16u
+#define MAGOT_GFF_FOR_WRITE 32u
 typedef struct magot_gffplan magot_gffplan;
 int magot_gff_plan(const char* gff, uint64_t gff_len, const char* const* seqids,
                    const uint64_t* contig_lens, uint32_t n_contigs, const char* feature,
@@ -621,7 +622,9 @@ int magot_gff_plan(const char* gff, uint64_t gff_len, const char* const* seqids,
  * per plan, else MAGOT_ERR_STATE).  `gff` must stay valid until
  * magot_gff_lower returns.  Either returns MAGOT_ERR_UNSUPPORTED for a
  * diagnostic path; the plan handle from magot_gff_read is then still the
- * caller's to destroy.
+ * caller's to destroy.  MAGOT_GFF_FOR_WRITE (not with MAGOT_GFF_FROM_EXONS:
+ * MAGOT_ERR_ARG) makes magot_gff_read keep, per feature, what
+ * magot_gff_lower_write needs; without it the model is what it always was.
  */
 int magot_gff_read(const char* gff, uint64_t gff_len, uint32_t flags, magot_gffplan** out);
 int magot_gff_lower(magot_gffplan* p, const char* const* seqids, const uint64_t* contig_lens,
@@ -1345,6 +1348,96 @@ int magot_rename_time(magot_ctx* ctx, magot_rename* p, int iters, double* ms6,
                       uint64_t* text_bytes, uint64_t* out_bytes);
 void magot_rename_params(uint32_t* max_name, uint32_t* text_block, uint32_t* piece);
 void magot_rename_destroy(magot_rename* p);
+
+/*
+ * write_gff (genome.py:228-238, 616-645, 733-778) as a table of output lines:
+ * the annotation lowered on the host, its text rendered on the device.
+ *
+ * One magot_gffrow stands for one output line.  `line_off` is the start of a
+ * line of the GFF text with at least eight tabs: its columns 1, 2, 3, 6, 7 and
+ * 8 are copied or classified from there.  A reference (offset, length) below
+ * the text's length points into the text, one at or above it into the blob
+ * (offset - text length).  By kind:
+ *   MAGOT_GFFROW_LINE         c1 c2 c3 lo hi score c7 phase ID=<id>[;Parent=<parent>]
+ *   MAGOT_GFFROW_EXON_TWIN    c1 c2 exon lo hi score c7 phase ID=ExonOf<id>[;Parent=<parent>]
+ *   MAGOT_GFFROW_GTF          c1 c2 c3 lo hi score c7 phase transcript_id <id>;gene_id <parent>
+ *   MAGOT_GFFROW_MADE_PARENT  c1 . <type> lo hi . c7 . ID=<id>[;Parent=<parent>]
+ * joined by tabs and ended by LF; ";Parent=" only with MAGOT_GFFROW_HAS_PARENT.
+ * lo and hi print as decimal integers.  score is column 6 as Python 2 prints
+ * float(column 6): "." when the column has no ASCII digit and no ASCII letter;
+ * the normalised literal (leading zeros dropped, one kept; trailing fraction
+ * zeros dropped, ".0" when none remains; the sign kept) when it is -?D+,
+ * -?D+.D* or -?.D+ with at most 12 digits from its first to its last non-zero
+ * digit, at most 12 integer digits after the leading zeros and, its integer
+ * part being zero, at most 3 zeros before the fraction's first non-zero digit;
+ * any other column declines the table.  phase is column 8 when it is exactly 0, 1 or 2, else ".".
+ *
+ *   magot_gff_lower_write  walks a plan read with MAGOT_GFF_FOR_WRITE in
+ *       write_gff's order (flags: MAGOT_GFF_ORDER_PY2) for `format`
+ *       (MAGOT_GFFFMT_*), any number of times; the rows replace the plan's last
+ *       ones, the blob is the reader's (made-up names, then every table's name)
+ *       and the same for every lowering.  MAGOT_ERR_UNSUPPORTED where the reference raises or
+ *       where a row cannot say what it prints: a parent without children, a gtf
+ *       line without parent or grandparent, an attribute that shadows a name
+ *       get_gff reads, a CR in the first eight columns, an exon twin whose
+ *       whole-line replaces would touch more than the type and the leading
+ *       "ID=".
+ *   magot_gffplan_write_views  the rows and the blob of the last lowering (the
+ *       plan's memory).
+ *   magot_gffwrite_open  text, blob and rows (any caller's) made resident, every
+ *       row sized and the output laid out.  MAGOT_ERR_RANGE before any launch: a
+ *       line_off beyond the text, a reference that leaves text and blob, a kind
+ *       that is none of the four; MAGOT_ERR_ARG: a reference of 2^28 bytes or
+ *       more.  Declined with MAGOT_ERR_UNSUPPORTED, *out = NULL, *reason a
+ *       MAGOT_GFFWRITE_* code and *row the first offending row (1-based).
+ *   magot_gffwrite_sizes  the rows and the output's bytes.
+ *   magot_gffwrite_render  the text into a device buffer of the handle.
+ *   magot_gffwrite_render_fetch  that text to the host (cap >= its length).
+ *   magot_gffwrite_time  mean device ms over `iters` runs of: the sizes, the
+ *       scan, the render (*out_bytes) and a device copy of as many bytes, in
+ *       ms4[0..3].
+ *   magot_gffwrite_params  the rows one wave renders, the threads of a
+ *       workgroup, and the bytes within which a line's eighth tab must lie.
+ */
+typedef struct magot_gffrow {
+  uint64_t line_off;   /* the source line's first byte */
+  int64_t lo, hi;
+  uint64_t id_off;     /* ID; under gtf the parent (transcript_id) */
+  uint64_t parent_off; /* parent; under gtf the grandparent (gene_id) */
+  uint64_t type_off;   /* MAGOT_GFFROW_MADE_PARENT: the type's name */
+  uint32_t id_len, parent_len;
+  uint32_t type_len;
+  uint32_t kind;       /* MAGOT_GFFROW_* | MAGOT_GFFROW_HAS_PARENT */
+} magot_gffrow;
+enum {
+  MAGOT_GFFROW_LINE = 0,
+  MAGOT_GFFROW_EXON_TWIN = 1,
+  MAGOT_GFFROW_GTF = 2,
+  MAGOT_GFFROW_MADE_PARENT = 3
+};
+#define MAGOT_GFFROW_HAS_PARENT 0x100u
+enum { MAGOT_GFFFMT_GFF3 = 0, MAGOT_GFFFMT_GTF = 1, MAGOT_GFFFMT_EXON_ADDED = 2 };
+enum {
+  MAGOT_GFFWRITE_TOO_LARGE = 1, /* text, blob and rows against max_bytes */
+  MAGOT_GFFWRITE_SCORE = 2,     /* a score outside the two classes */
+  MAGOT_GFFWRITE_COLUMNS = 3    /* no eighth tab within the line's first max_head bytes */
+};
+int magot_gff_lower_write(magot_gffplan* p, uint32_t format, uint32_t flags, uint64_t* n_rows,
+                          uint64_t* blob_len);
+int magot_gffplan_write_views(const magot_gffplan* p, const magot_gffrow** rows, uint64_t* n_rows,
+                              const uint8_t** blob, uint64_t* blob_len);
+typedef struct magot_gffwrite magot_gffwrite;
+int magot_gffwrite_open(magot_ctx* ctx, const char* text, uint64_t len, const uint8_t* blob,
+                        uint64_t blob_len, const magot_gffrow* rows, uint64_t n_rows,
+                        uint64_t max_bytes, magot_gffwrite** out, uint32_t* reason, uint64_t* row);
+int magot_gffwrite_sizes(const magot_gffwrite* p, uint64_t* n_rows, uint64_t* out_bytes);
+double magot_gffwrite_upload_ms(const magot_gffwrite* p);
+int magot_gffwrite_render(magot_ctx* ctx, magot_gffwrite* p, uint64_t* bytes);
+int magot_gffwrite_render_fetch(magot_ctx* ctx, magot_gffwrite* p, uint8_t* out, uint64_t cap);
+int magot_gffwrite_time(magot_ctx* ctx, magot_gffwrite* p, int iters, double* ms4,
+                        uint64_t* text_bytes, uint64_t* out_bytes);
+void magot_gffwrite_params(uint32_t* rows_per_group, uint32_t* threads, uint32_t* max_head);
+void magot_gffwrite_destroy(magot_gffwrite* p);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,10 @@ EXPORTS = (
     'magot_rename_parse', 'magot_rename_sizes', 'magot_rename_upload_ms', 'magot_rename_hits',
     'magot_rename_render', 'magot_rename_render_fetch', 'magot_rename_time',
     'magot_rename_params', 'magot_rename_destroy',
+    'magot_gff_lower_write', 'magot_gffplan_write_views',
+    'magot_gffwrite_open', 'magot_gffwrite_sizes', 'magot_gffwrite_upload_ms',
+    'magot_gffwrite_render', 'magot_gffwrite_render_fetch', 'magot_gffwrite_time',
+    'magot_gffwrite_params', 'magot_gffwrite_destroy',
 )
 
 ERR_ARG = -1
@@ -96,6 +100,10 @@ GFF_ORDER_PY2 = 2
 GFF_LONGEST = 4
 GFF_GENOMIC = 8
 GFF_FROM_EXONS = 16
+GFF_FOR_WRITE = 32
+GFF_FORMATS = {'simple gff3': 0, 'gtf': 1, 'exon added gff3': 2}
+GFFROW_LINE, GFFROW_EXON_TWIN, GFFROW_GTF, GFFROW_MADE_PARENT = 0, 1, 2, 3
+GFFROW_HAS_PARENT = 0x100
 PACK_HOST = 1
 ORF_FROM_ATG = 1
 ORF_LONGEST = 2
@@ -129,6 +137,12 @@ FASTAREC_REASONS = (None, 'leading_text', 'stray_cr', 'long_name', 'hash_collisi
 FASTAREC_STYLES = {'fasta': 0, 'tab': 1}
 # magot_rename_parse's reasons (MAGOT_RENAME_*), by code
 RENAME_REASONS = (None, 'too_large', 'hash_collision', 'table_too_large')
+# magot_gffwrite_open's reasons (MAGOT_GFFWRITE_*), by code
+GFFWRITE_REASONS = (None, 'too_large', 'score', 'columns')
+# magot_gffrow (include/magot.h)
+GFFROW_DTYPE = np.dtype([('line_off', '<u8'), ('lo', '<i8'), ('hi', '<i8'), ('id_off', '<u8'),
+                         ('parent_off', '<u8'), ('type_off', '<u8'), ('id_len', '<u4'),
+                         ('parent_len', '<u4'), ('type_len', '<u4'), ('kind', '<u4')])
 MASK_INTERVAL_DTYPE = np.dtype([('contig', '<u4'), ('start', '<u4'), ('len', '<u4')])
 
 
@@ -419,6 +433,21 @@ def _declare(lib):
         'magot_rename_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p, _u64p]),
         'magot_rename_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3),
         'magot_rename_destroy': (None, [_vp]),
+        'magot_gff_lower_write': (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p,
+                                                 _u64p]),
+        'magot_gffplan_write_views': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _u64p,
+                                                     ctypes.POINTER(_vp), _u64p]),
+        'magot_gffwrite_open': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64,
+                                               _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.POINTER(_vp),
+                                               ctypes.POINTER(ctypes.c_uint32), _u64p]),
+        'magot_gffwrite_sizes': (ctypes.c_int, [_vp, _u64p, _u64p]),
+        'magot_gffwrite_upload_ms': (ctypes.c_double, [_vp]),
+        'magot_gffwrite_render': (ctypes.c_int, [_vp, _vp, _u64p]),
+        'magot_gffwrite_render_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_gffwrite_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p, _u64p]),
+        'magot_gffwrite_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3),
+        'magot_gffwrite_destroy': (None, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

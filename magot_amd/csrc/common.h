@@ -1114,6 +1114,42 @@ hipError_t launch_rn_match(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStre
 hipError_t launch_rn_layout(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_rn_render(const RnArgs& a, const RnRenderArgs& r, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// write_gff's text from a table of rows (gffwrite.hip; magot.h: magot_gffrow).
+// Pass 1, one lane per row: the eight tabs of the row's source line, its score
+// and phase classified, the output line's exact length.  A scan of the lengths.
+// Pass 3, one wave per kGwGroup consecutive rows: every row's segments staged
+// in LDS (a segment is a run of the text or blob, or a few bytes made up in
+// LDS: the integers, the score, the literals), then the lanes dealt over the
+// 16-byte chunks of the group's contiguous output range.
+// ---------------------------------------------------------------------------
+constexpr int kGwGroup = 32;      // rows per wave
+constexpr int kGwThreads = 256;   // threads of a workgroup (4 waves)
+constexpr uint32_t kGwMaxHead = 1u << 20;  // a line's eighth tab lies within so many bytes
+constexpr uint32_t kGwMaxRef = 1u << 28;   // bytes of a referenced name
+struct GwAux {            // per row, from pass 1
+  uint32_t tab[8];        // the tabs of the source line, counted from line_off
+  uint32_t int_off, int_len;    // score: integer digits without leading zeros, from line_off
+  uint32_t frac_off, frac_len;  // score: fraction digits without trailing zeros
+  uint32_t flags;         // kGwScoreNum, kGwScoreNeg, kGwPhase
+  uint32_t pad[3];
+};
+constexpr uint32_t kGwScoreNum = 1, kGwScoreNeg = 2, kGwPhase = 4;
+struct GwArgs {
+  const uint8_t* text;  // n bytes
+  uint64_t n;
+  const uint8_t* blob;  // blob_len bytes: reference n + k is its byte k
+  uint64_t blob_len;
+  const magot_gffrow* rows;
+  uint64_t n_rows;
+  GwAux* aux;           // n_rows
+  uint64_t* len;        // n_rows + 1: bytes of each output line, the last entry 0
+  uint64_t* off;        // n_rows + 1: their exclusive scan
+  unsigned long long* status;  // min of (row << 8 | MAGOT_GFFWRITE_* reason), ~0 when clean
+};
+hipError_t launch_gw_size(const GwArgs& a, hipStream_t s);
+hipError_t launch_gw_render(const GwArgs& a, uint8_t* out, hipStream_t s);
+
 // Standard genetic code (genome.py:795-802) as a 64-byte table indexed
 // c0 + 4*c1 + 16*c2 with A=0, C=1, G=2, T=3.
 void standard_lut(uint8_t out[64]);

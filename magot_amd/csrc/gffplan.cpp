@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -51,6 +52,44 @@ struct Table {
 };
 
 struct Unsupported {};  // a diagnostic path of the reference: use the object path
+
+// What magot_gff_read keeps beside the model under MAGOT_GFF_FOR_WRITE, for
+// magot_gff_lower_write: per feature the line that made it, its parent and
+// what its line forbids; per ID where its bytes lie (in the GFF text, or in
+// the blob behind it: offset text_len + place).
+constexpr uint8_t kWMade = 1;    // a parent made by a GTF hierarchy
+constexpr uint8_t kWShadow = 2;  // an attribute key shadows a name get_gff reads
+constexpr uint8_t kWCr = 4;      // a CR in the line's first eight columns
+constexpr uint8_t kWTrap = 8;    // an exon twin's replaces would touch more than type and ID=
+struct WriteInfo {
+  const char* text = nullptr;
+  uint64_t text_len = 0;
+  std::vector<uint64_t> line_off;
+  std::vector<uint32_t> parent;  // the parent's ID, ~0u: None
+  std::vector<uint8_t> flags;
+  std::vector<uint64_t> name_off;
+  std::vector<uint32_t> name_len;
+  std::vector<uint64_t> type_off;  // per table: its name, appended to the blob once the read is through
+  std::string blob;
+  // the bytes of ID k, noted when the ID is first interned
+  void note(uint32_t k, std::string_view s) {
+    if (k < name_off.size()) return;
+    name_off.resize(k + 1, 0);
+    name_len.resize(k + 1, 0);
+    name_len[k] = (uint32_t)s.size();
+    if (s.data() >= text && s.data() + s.size() <= text + text_len) {
+      name_off[k] = (uint64_t)(s.data() - text);
+    } else {
+      name_off[k] = text_len + blob.size();
+      blob.append(s.data(), s.size());
+    }
+  }
+  void feature(uint64_t off, uint32_t par, uint8_t fl) {
+    line_off.push_back(off);
+    parent.push_back(par);
+    flags.push_back(fl);
+  }
+};
 
 // The first exception a worker thread caught, rethrown by the caller.
 struct FirstError {
@@ -192,6 +231,7 @@ struct Model {
   // parents); children() walks a chain.
   std::vector<uint32_t> kid_head, kid_tail;     // per list
   std::vector<uint32_t> link_child, link_next;  // per appended child
+  std::unique_ptr<WriteInfo> w;  // MAGOT_GFF_FOR_WRITE only
 
   Model() {
     // AnnotationSet.__init__ (genome.py:528-533) creates these dicts
@@ -431,6 +471,12 @@ struct GffHier {
 
 // Chunk-local string codes (seqid, type, strand) so that the ordered pass
 // maps a few codes per chunk to the model's instead of comparing text.
+// Beside a line under MAGOT_GFF_FOR_WRITE: where it starts, and its kW* flags.
+struct GffW {
+  uint64_t off;
+  uint8_t flags;
+};
+
 struct LocalIntern {
   std::vector<sv> strs;
   std::unordered_map<sv, uint32_t> map;
@@ -529,9 +575,11 @@ struct LineParser {
   uint32_t prev_run = 0;
   std::string dup;
   std::vector<uint64_t> type_lines;  // accepted lines per local type code
+  const char* base = nullptr;        // the text's first byte (GffW::off counts from it)
 
   // false: the line is skipped; throws Unsupported on a diagnostic path
-  bool parse(const char* raw, uint64_t rl, GffLine& L, GffHier& H) {
+  bool parse(const char* raw, uint64_t rl, GffLine& L, GffHier& H, GffW* W = nullptr) {
+    const char* const raw0 = raw;
     if (F.from_exons && sv(raw, rl).find("\texon\t") != sv::npos) {
       // line.replace("\texon\t", "\tCDS\t") (genome.py:285-286): left to right,
       // non-overlapping; the tab count (checked before, :283) is unchanged
@@ -625,7 +673,33 @@ struct LineParser {
           L.hv_mask |= (uint8_t)(1u << level);
         }
     }
+    if (W) note_write(raw0, rl, cols, L, *W);
     return true;
+  }
+
+  // Names get_gff reads from the object (genome.py:618, 626-628, 640), which an
+  // attribute of column 9 overwrites (:595-598, :660-661).
+  static bool shadows(sv key, bool have_id_field) {
+    for (sv name : {sv("seqid"), sv("source"), sv("feature_type"), sv("score"), sv("strand"),
+                    sv("phase"), sv("parent"), sv("child_list"), sv("annotation_set"),
+                    sv("coords"), sv("get_coords"), sv("get_gff")})
+      if (key == name) return true;
+    return key == "ID" && !have_id_field;  // the ID field itself is not set as an attribute
+  }
+  void note_write(const char* raw0, uint64_t rl, const sv cols[9], const GffLine& L, GffW& W) {
+    W.off = (uint64_t)(raw0 - base);
+    W.flags = 0;
+    for (const auto& p : tags.kv)
+      if (shadows(p.first, F.have_id_field)) W.flags |= kWShadow;
+    int tabs = 0;
+    for (uint64_t i = 0; i < rl && tabs < 8; ++i) {
+      tabs += raw0[i] == '\t';
+      if (raw0[i] == '\r') W.flags |= kWCr;
+    }
+    auto has_id = [](sv s) { return s.find("ID=") != sv::npos; };
+    for (int c : {0, 1, 6})
+      if (cols[c] == "CDS" || has_id(cols[c])) W.flags |= kWTrap;
+    if (has_id(L.id) || (L.has_parent && has_id(L.parent))) W.flags |= kWTrap;
   }
 };
 
@@ -668,7 +742,7 @@ struct Prefault {
 // parallel over newline-aligned chunks of the text, then the model updates
 // (de-duplication, tables, parents) in file order.  Any diagnostic path
 // anywhere declines the whole input, so chunks may find them out of order.
-void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
+void read_gff(Model& M, const char* text, uint64_t n, bool from_exons, bool for_write = false) {
   const auto t_start = std::chrono::steady_clock::now();
   GffFormat F;
   F.from_exons = from_exons;
@@ -702,6 +776,7 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
   }
   std::vector<std::vector<GffLine>> lines(n_chunks);
   std::vector<std::vector<GffHier>> hiers(n_chunks);  // GTF only
+  std::vector<std::vector<GffW>> wlines(for_write ? n_chunks : 0);
   const bool hier = !F.hierarchy.empty();
   std::vector<std::unique_ptr<LineParser>> parsers(n_chunks);
   FirstError failed;
@@ -711,6 +786,7 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
     for (uint64_t c; (c = next.fetch_add(1)) < n_chunks && !unsupported.load();) {
       parsers[c].reset(new LineParser{F, {}, {}, {}});
       LineParser& P = *parsers[c];
+      P.base = text;
       std::vector<GffLine>& out = lines[c];
       std::vector<GffHier>& hout = hiers[c];
       out.reserve((cut[c + 1] - cut[c]) / 96 + 16);
@@ -718,13 +794,15 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
       try {
         GffLine L;
         GffHier H;
+        GffW W;
         for (uint64_t pos = cut[c]; pos < cut[c + 1];) {
           const char* nl =
               static_cast<const char*>(memchr(text + pos, '\n', cut[c + 1] - pos));
           const uint64_t end = nl ? (uint64_t)(nl - text) + 1 : cut[c + 1];
-          if (P.parse(text + pos, end - pos, L, H)) {
+          if (P.parse(text + pos, end - pos, L, H, for_write ? &W : nullptr)) {
             out.push_back(L);
             if (hier) hout.push_back(H);
+            if (for_write) wlines[c].push_back(W);
           }
           pos = end;
         }
@@ -800,6 +878,14 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
               std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(),
               pf.bytes() >> 20);
   }
+  WriteInfo* const WI = M.w.get();
+  if (WI) {
+    WI->text = text;
+    WI->text_len = n;
+    WI->line_off.reserve(total + 16);
+    WI->parent.reserve(total + 16);
+    WI->flags.reserve(total + 16);
+  }
   std::string nid;
   std::vector<uint32_t> sq_of, st_of, ty_of;  // chunk code -> model index
   std::vector<uint8_t> ty_base;
@@ -839,9 +925,11 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
           r = r ? r + 1 : 2;
           dup_name(L.id, r - 1, nid);
           idk = L.dup_run == r - 1 ? M.id(nid, L.h_dup) : M.id(nid);
+          if (WI) WI->note(idk, nid);
         } else {
           idk = M.id(L.id, L.h_id);
           k0 = idk;
+          if (WI) WI->note(idk, L.id);
         }
         last_id = L.id;
         last_k0 = k0;
@@ -856,6 +944,7 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
           if (!((L.hv_mask >> level) & 1)) continue;
           const uint32_t t = hier_table[level];
           const uint32_t pk = M.id(HV[li].hv[level], HV[li].h_hv[level]);
+          if (WI) WI->note(pk, HV[li].hv[level]);
           const int64_t have = M.slot(t, pk);
           if (have >= 0) {
             Feature& hf = M.feats[(size_t)have];
@@ -869,6 +958,15 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
             M.add_child(f, child);
             M.feats.push_back(std::move(f));
             M.put(t, pk, (uint32_t)M.feats.size() - 1);
+            if (WI) {  // its parent: the last later level the line names (genome.py:376-380)
+              uint32_t grand = ~0u;
+              for (size_t up = level + 1; up < F.hierarchy.size(); ++up)
+                if ((L.hv_mask >> up) & 1) {
+                  grand = M.id(HV[li].hv[up], HV[li].h_hv[up]);
+                  WI->note(grand, HV[li].hv[up]);
+                }
+              WI->feature(wlines[c][li].off, grand, (uint8_t)(wlines[c][li].flags | kWMade));
+            }
           }
           child = pk;
         }
@@ -900,8 +998,15 @@ void read_gff(Model& M, const char* text, uint64_t n, bool from_exons) {
       const uint32_t ty = f.type;
       M.feats.push_back(std::move(f));
       M.put(ty, idk, (uint32_t)M.feats.size() - 1);
+      if (WI) WI->feature(wlines[c][li].off, L.has_parent ? (uint32_t)last_pk : ~0u,
+                          wlines[c][li].flags);
     }
   }
+  if (WI)  // a made parent's type is its table's name: a referenced name like any other
+    for (const Table& t : M.tables) {
+      WI->type_off.push_back(n + WI->blob.size());
+      WI->blob += t.name;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -989,6 +1094,8 @@ struct magot_gffplan : magot::Lowered {
   magot::Model model;
   bool protein = false;
   int stage = 0;  // 1: read (magot_gff_read), 2: lowered (magot_gff_lower)
+  // magot_gff_lower_write's last result (the blob is the reader's: model.w->blob)
+  std::vector<magot_gffrow> w_rows;
 };
 
 namespace magot {
@@ -1332,7 +1439,13 @@ int magot_gff_read(const char* gff, uint64_t gff_len, uint32_t flags, magot_gffp
   std::unique_ptr<magot_gffplan> P(new magot_gffplan());
   GffLap lap;
   try {
-    magot::read_gff(P->model, gff, gff_len, (flags & MAGOT_GFF_FROM_EXONS) != 0);
+    const bool for_write = (flags & MAGOT_GFF_FOR_WRITE) != 0;
+    if (for_write && (flags & MAGOT_GFF_FROM_EXONS)) {
+      magot::set_error("magot_gff_read: MAGOT_GFF_FOR_WRITE with MAGOT_GFF_FROM_EXONS");
+      return MAGOT_ERR_ARG;
+    }
+    if (for_write) P->model.w.reset(new magot::WriteInfo());
+    magot::read_gff(P->model, gff, gff_len, (flags & MAGOT_GFF_FROM_EXONS) != 0, for_write);
     lap("read_gff");
   } catch (const Unsupported&) {
     magot::set_error("magot_gff_read: input takes a diagnostic path; use the object path");
@@ -1824,5 +1937,276 @@ int magot_gffplan_selections(const magot_gffplan* p, uint64_t* n_groups) {
 }
 
 void magot_gffplan_destroy(magot_gffplan* p) { delete p; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// write_gff lowering (genome.py:228-238, 616-645, 733-778): one row per output
+// line, in output order; the device renders the text (gffwrite.hip)
+// ---------------------------------------------------------------------------
+
+namespace magot {
+namespace {
+
+constexpr uint32_t kRowCdsLine = 0x200u;  // scratch bit: the line's type is CDS (exon-added order)
+
+// Iteration order of an empty Python 2 dict after dict.update(other), `keys`
+// being other's iteration order (PyDict_Merge: one presize, raw inserts).
+std::vector<uint32_t> py2_merge_order(const std::vector<uint32_t>& keys,
+                                      const std::vector<uint64_t>& hash) {
+  uint64_t size = 8;
+  if (keys.size() * 3 >= size * 2)
+    while (size <= 2 * keys.size()) size <<= 1;
+  std::vector<int64_t> slots(size, -1);
+  const uint64_t mask = size - 1;
+  for (uint32_t k : keys) {
+    uint64_t i = hash[k] & mask, perturb = hash[k];
+    while (slots[i & mask] >= 0) {
+      i = i * 5 + perturb + 1;
+      perturb >>= 5;
+    }
+    slots[i & mask] = k;
+  }
+  std::vector<uint32_t> out;
+  for (int64_t k : slots)
+    if (k >= 0) out.push_back((uint32_t)k);
+  return out;
+}
+
+struct WriteLowering {
+  const Model& M;
+  const WriteInfo& W;
+  const uint32_t format;
+  std::vector<uint32_t> id_of_feat;
+  std::vector<int64_t> span_lo, span_hi;
+  std::vector<uint8_t> span_state;  // 0: unknown, 1: known, 2: being computed
+  using Rows = std::vector<magot_gffrow>;
+  using Key = std::pair<int64_t, int64_t>;
+
+  WriteLowering(const Model& m, const WriteInfo& w, uint32_t fmt) : M(m), W(w), format(fmt) {
+    id_of_feat.assign(M.feats.size(), 0);
+    for (uint32_t t = 0; t < M.tables.size(); ++t)
+      for (uint32_t k : M.tables[t].keys) id_of_feat[(size_t)M.slot(t, k)] = k;
+    span_lo.assign(M.feats.size(), 0);
+    span_hi.assign(M.feats.size(), 0);
+    span_state.assign(M.feats.size(), 0);
+  }
+
+  uint32_t feature_of(uint32_t idk) const {  // annotation_set[ID]; KeyError declines
+    const int64_t o = M.lookup(idk);
+    if (o < 0) throw Unsupported();
+    return (uint32_t)o;
+  }
+  // ParentAnnotation.get_coords (genome.py:663-675); None (no children) is a
+  // TypeError wherever get_gff subscripts it
+  void span(uint32_t fi) {
+    if (span_state[fi] == 1) return;
+    if (span_state[fi] == 2) throw Unsupported();  // a feature above itself: RuntimeError
+    const Feature& F = M.feats[fi];
+    if (M.children(F).empty()) throw Unsupported();
+    span_state[fi] = 2;
+    bool any = false;
+    int64_t lo = 0, hi = 0;
+    for (uint32_t c : M.children(F)) {
+      const uint32_t o = feature_of(c);
+      const Key k = coords(o);
+      lo = any ? std::min(lo, k.first) : k.first;
+      hi = any ? std::max(hi, k.second) : k.second;
+      any = true;
+    }
+    span_lo[fi] = lo;
+    span_hi[fi] = hi;
+    span_state[fi] = 1;
+  }
+  Key coords(uint32_t fi) {
+    const Feature& F = M.feats[fi];
+    if (F.base) return Key(F.lo, F.hi);
+    span(fi);
+    return Key(span_lo[fi], span_hi[fi]);
+  }
+  void name(uint32_t idk, uint64_t* off, uint32_t* len) const {
+    if (idk >= W.name_off.size()) throw Unsupported();
+    *off = W.name_off[idk];
+    *len = W.name_len[idk];
+  }
+
+  void emit(uint32_t fi, Rows& out) {
+    const Feature& F = M.feats[fi];
+    const uint8_t fl = W.flags[fi];
+    if (fl & (kWShadow | kWCr)) throw Unsupported();
+    magot_gffrow r{};
+    r.line_off = W.line_off[fi];
+    const uint32_t par = W.parent[fi];
+    if (F.base) {
+      r.lo = F.lo;
+      r.hi = F.hi;
+      if (format == MAGOT_GFFFMT_GTF) {
+        if (par == ~0u) throw Unsupported();  // 'transcript_id ' + None: TypeError
+        const uint32_t grand = W.parent[feature_of(par)];
+        if (grand == ~0u) throw Unsupported();  // ... + None: TypeError
+        name(par, &r.id_off, &r.id_len);
+        name(grand, &r.parent_off, &r.parent_len);
+        r.kind = MAGOT_GFFROW_GTF | MAGOT_GFFROW_HAS_PARENT;
+        out.push_back(r);
+        return;
+      }
+      name(id_of_feat[fi], &r.id_off, &r.id_len);
+      r.kind = MAGOT_GFFROW_LINE;
+      if (par != ~0u) {
+        name(par, &r.parent_off, &r.parent_len);
+        r.kind |= MAGOT_GFFROW_HAS_PARENT;
+      }
+      if (format == MAGOT_GFFFMT_EXON_ADDED && M.tables[F.type].name == "CDS") {
+        if (fl & kWTrap) throw Unsupported();
+        magot_gffrow twin = r;
+        twin.kind = (r.kind & MAGOT_GFFROW_HAS_PARENT) | MAGOT_GFFROW_EXON_TWIN;
+        out.push_back(twin);
+        r.kind |= kRowCdsLine;
+      }
+      out.push_back(r);
+      return;
+    }
+    span(fi);  // the columns are read before the format is looked at
+    if (format != MAGOT_GFFFMT_GTF) {
+      r.lo = span_lo[fi];
+      r.hi = span_hi[fi];
+      name(id_of_feat[fi], &r.id_off, &r.id_len);
+      r.kind = (fl & kWMade) ? MAGOT_GFFROW_MADE_PARENT : MAGOT_GFFROW_LINE;
+      if (par != ~0u) {
+        name(par, &r.parent_off, &r.parent_len);
+        r.kind |= MAGOT_GFFROW_HAS_PARENT;
+      }
+      if (fl & kWMade) {
+        r.type_off = W.type_off[F.type];
+        r.type_len = (uint32_t)M.tables[F.type].name.size();
+      }
+      out.push_back(r);
+    }
+    // child_dict (genome.py:761-771): keyed by coords; a child whose coords are
+    // taken goes under (c0, c1 + len(child_dict)), replacing what is there.
+    // The children's rows lie one behind the other in `sub`; the dict holds
+    // each entry's range of it and gives them back in key order.
+    Rows sub;
+    std::map<Key, std::pair<size_t, size_t>> kids;
+    for (uint32_t c : M.children(F)) {
+      const uint32_t o = feature_of(c);
+      Key k = coords(o);
+      const size_t begin = sub.size();
+      emit(o, sub);
+      if (kids.count(k)) k.second += (int64_t)kids.size();
+      kids[k] = {begin, sub.size()};
+    }
+    for (const auto& e : kids)
+      out.insert(out.end(), sub.begin() + (ptrdiff_t)e.second.first,
+                 sub.begin() + (ptrdiff_t)e.second.second);
+  }
+
+  // One entry of a top-level table.  Under "exon added gff3" every parent level
+  // moves its CDS lines behind the others, first equal line first
+  // (genome.py:772-777): over the whole entry that is one stable partition.
+  void top(uint32_t fi, Rows& all) {
+    Rows out;
+    emit(fi, out);
+    if (format == MAGOT_GFFFMT_EXON_ADDED && !M.feats[fi].base)
+      std::stable_partition(out.begin(), out.end(),
+                            [](const magot_gffrow& r) { return !(r.kind & kRowCdsLine); });
+    for (magot_gffrow& r : out) r.kind &= ~kRowCdsLine;
+    all.insert(all.end(), out.begin(), out.end());
+  }
+};
+
+}  // namespace
+}  // namespace magot
+
+extern "C" {
+
+int magot_gff_lower_write(magot_gffplan* P, uint32_t format, uint32_t flags, uint64_t* n_rows,
+                          uint64_t* blob_len) {
+  if (!P || format > MAGOT_GFFFMT_EXON_ADDED) {
+    magot::set_error("magot_gff_lower_write: null plan or unknown format");
+    return MAGOT_ERR_ARG;
+  }
+  if (P->stage != 1 || !P->model.w) {
+    magot::set_error("magot_gff_lower_write: plan not read with MAGOT_GFF_FOR_WRITE");
+    return MAGOT_ERR_STATE;
+  }
+  P->w_rows.clear();
+  GffLap lap;
+  try {
+    const magot::Model& M = P->model;
+    const bool py2 = (flags & MAGOT_GFF_ORDER_PY2) != 0;
+    // the set's attribute names: the four of __init__, `genome`, then the others
+    std::vector<std::string> names;
+    std::vector<int64_t> table_of;
+    for (uint32_t t = 0; t < M.tables.size(); ++t) {
+      names.push_back(M.tables[t].name);
+      table_of.push_back(t);
+      if (t == 3) {  // AnnotationSet.__init__ sets it behind its four dicts
+        names.push_back("genome");
+        table_of.push_back(-1);
+      }
+    }
+    std::vector<uint32_t> order(names.size());
+    for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
+    if (py2) {  // as built, as deep-copied, as merged into the copy's __dict__
+      std::vector<uint64_t> hash(names.size());
+      for (size_t i = 0; i < names.size(); ++i) hash[i] = magot::py2_hash(names[i]);
+      order = magot::py2_dict_order(order, hash);
+      order = magot::py2_dict_order(order, hash);
+      order = magot::py2_merge_order(order, hash);
+    }
+    magot::WriteLowering L(M, *P->model.w, format);
+    for (uint32_t q : order) {
+      if (table_of[q] < 0) continue;
+      const uint32_t t = (uint32_t)table_of[q];
+      std::vector<uint32_t> keys = M.tables[t].keys;
+      if (keys.empty()) continue;
+      if (py2) {
+        std::vector<uint64_t> hash(keys.size());
+        std::vector<uint32_t> pos(keys.size());
+        for (size_t i = 0; i < keys.size(); ++i) {
+          hash[i] = magot::py2_hash(M.ids.strs[keys[i]]);
+          pos[i] = (uint32_t)i;
+        }
+        pos = magot::py2_dict_order(pos, hash);
+        pos = magot::py2_dict_order(pos, hash);
+        std::vector<uint32_t> ordered(pos.size());
+        for (size_t i = 0; i < pos.size(); ++i) ordered[i] = keys[pos[i]];
+        keys.swap(ordered);
+      }
+      const uint32_t first = (uint32_t)M.slot(t, keys[0]);
+      if (P->model.w->flags[first] & magot::kWShadow) throw Unsupported();
+      if (P->model.w->parent[first] != ~0u) continue;
+      for (uint32_t k : keys) L.top((uint32_t)M.slot(t, k), P->w_rows);
+    }
+    lap("lower_write");
+  } catch (const Unsupported&) {
+    P->w_rows.clear();
+    magot::set_error("magot_gff_lower_write: input takes a diagnostic path; use the object path");
+    return MAGOT_ERR_UNSUPPORTED;
+  } catch (const std::exception& e) {
+    P->w_rows.clear();
+    magot::set_error(std::string("magot_gff_lower_write: ") + e.what());
+    return MAGOT_ERR_ARG;
+  }
+  if (n_rows) *n_rows = P->w_rows.size();
+  if (blob_len) *blob_len = P->model.w->blob.size();
+  return MAGOT_OK;
+}
+
+int magot_gffplan_write_views(const magot_gffplan* p, const magot_gffrow** rows, uint64_t* n_rows,
+                              const uint8_t** blob, uint64_t* blob_len) {
+  if (!p) {
+    magot::set_error("magot_gffplan_write_views: null plan");
+    return MAGOT_ERR_ARG;
+  }
+  if (rows) *rows = p->w_rows.data();
+  if (n_rows) *n_rows = p->w_rows.size();
+  const std::string empty;
+  const std::string& b = p->model.w ? p->model.w->blob : empty;
+  if (blob) *blob = reinterpret_cast<const uint8_t*>(p->model.w ? b.data() : nullptr);
+  if (blob_len) *blob_len = b.size();
+  return MAGOT_OK;
+}
 
 }  // extern "C"

@@ -665,12 +665,13 @@ class GffRead(object):
         self.from_exons = from_exons
 
     @classmethod
-    def read(cls, gff, from_exons=False):
+    def read(cls, gff, from_exons=False, for_write=False):
+        """``for_write``: keep what ``lower_write`` needs (MAGOT_GFF_FOR_WRITE)."""
         L = _lib.lib()
         text = _text_view(gff)
         h = ctypes.c_void_p()
-        rc = L.magot_gff_read(_text_ptr(text), len(text),
-                              GffPlan.flags(from_exons=from_exons), ctypes.byref(h))
+        flags = GffPlan.flags(from_exons=from_exons) | (_lib.GFF_FOR_WRITE if for_write else 0)
+        rc = L.magot_gff_read(_text_ptr(text), len(text), flags, ctypes.byref(h))
         if rc == _lib.ERR_UNSUPPORTED:
             if h.value:
                 L.magot_gffplan_destroy(h)
@@ -705,11 +706,149 @@ class GffRead(object):
             if h is not None:
                 L.magot_gffplan_destroy(h)
 
+    def lower_write(self, gff_format='simple gff3', order='insertion'):
+        """write_gff lowered to output rows (magot_gff_lower_write): a
+        GffWritePlan, or None when the walk takes a diagnostic path.  The
+        handle stays this object's: any number of formats and orders."""
+        if not self.handle:
+            raise MagotError('GffRead.lower_write: lowered or closed')
+        if order not in ('insertion', 'py2'):
+            raise ValueError("order must be 'insertion' or 'py2'")
+        L = _lib.lib()
+        nr, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = L.magot_gff_lower_write(self.handle, _lib.GFF_FORMATS[gff_format],
+                                     _lib.GFF_ORDER_PY2 if order == 'py2' else 0,
+                                     ctypes.byref(nr), ctypes.byref(nb))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None
+        check(rc, 'magot_gff_lower_write')
+        rows, blob = ctypes.c_void_p(), ctypes.c_void_p()
+        check(L.magot_gffplan_write_views(self.handle, ctypes.byref(rows), ctypes.byref(nr),
+                                          ctypes.byref(blob), ctypes.byref(nb)),
+              'magot_gffplan_write_views')
+        return GffWritePlan(self, _view(rows.value, nr.value, _lib.GFFROW_DTYPE),
+                            _view(blob.value, nb.value, np.uint8))
+
     def close(self):
         if self.handle:
             _lib.lib().magot_gffplan_destroy(self.handle)
             self.handle = None
         self._text = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GffWritePlan(object):
+    """The output lines of write_gff as the host planner lowered them: ``rows``
+    (GFFROW_DTYPE, one per line, in output order) and ``blob`` (the names the
+    planner made up; a reference at or above the GFF text's length points into
+    it).  Views of the GffRead's memory: valid until its next ``lower_write``
+    or ``close``."""
+
+    def __init__(self, read, rows, blob):
+        self._read = read
+        self.rows = rows
+        self.blob = blob
+
+
+class GffWriter(object):
+    """write_gff's text rendered on the device from a row table
+    (magot_gffwrite_*): one lane per row sizes its line, a scan lays the output
+    out, one wave per ``params()['rows_per_group']`` rows writes it.  ``parse``
+    returns (None, reason, row) where the device declines, ``row`` the first
+    offending row counted from 1 (0: none): 'too_large', 'score' (a score
+    column outside the two printable classes), 'columns' (a source line
+    without eight tabs)."""
+
+    PASSES = ('size', 'scan', 'render', 'copy')
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.n_rows = self.out_bytes = 0
+        self.upload_ms = 0.0
+        self.declined_row = 0
+
+    @classmethod
+    def parse(cls, data, blob, rows, max_bytes=0, ctx=None):
+        """``data``: the GFF text; ``blob``: bytes; ``rows``: GFFROW_DTYPE rows
+        of any caller.  A row that leaves the text and the blob is a MagotError
+        before any launch.  Returns the object, or (None, reason, row) where the
+        device declines."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(data)
+        blob = np.ascontiguousarray(np.frombuffer(bytes(blob), np.uint8)
+                                    if isinstance(blob, (bytes, bytearray)) else blob,
+                                    dtype=np.uint8).reshape(-1)
+        rows = np.ascontiguousarray(rows, dtype=_lib.GFFROW_DTYPE).reshape(-1)
+        h, reason, row = ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_uint64()
+        rc = _lib.lib().magot_gffwrite_open(
+            self.ctx.handle, _text_ptr(view), len(view), ptr(blob) if len(blob) else None,
+            len(blob), ptr(rows) if len(rows) else None, len(rows), int(max_bytes or 0),
+            ctypes.byref(h), ctypes.byref(reason), ctypes.byref(row))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None, _lib.GFFWRITE_REASONS[reason.value], row.value
+        check(rc, 'magot_gffwrite_open')
+        self.handle = h
+        n, m = ctypes.c_uint64(), ctypes.c_uint64()
+        check(_lib.lib().magot_gffwrite_sizes(h, ctypes.byref(n), ctypes.byref(m)),
+              'magot_gffwrite_sizes')
+        self.n_rows, self.out_bytes = n.value, m.value
+        self.upload_ms = float(_lib.lib().magot_gffwrite_upload_ms(h))
+        return self
+
+    @staticmethod
+    def params():
+        """{'rows_per_group': the rows one wave renders, 'threads': the threads
+        of a workgroup, 'max_head': the bytes within which a source line's
+        eighth tab must lie}"""
+        vals = [ctypes.c_uint32() for _ in range(3)]
+        _lib.lib().magot_gffwrite_params(*[ctypes.byref(v) for v in vals])
+        return dict(zip(('rows_per_group', 'threads', 'max_head'), [v.value for v in vals]))
+
+    def execute(self):
+        """The text rendered into the handle's device buffer; its bytes."""
+        need = ctypes.c_uint64()
+        check(_lib.lib().magot_gffwrite_render(self.ctx.handle, self.handle, ctypes.byref(need)),
+              'magot_gffwrite_render')
+        return need.value
+
+    def fetch(self, out=None):
+        """The rendered text to the host (``out``: a uint8 array to fill)."""
+        need = self.out_bytes
+        if out is None:
+            out = np.empty(max(need, 1), np.uint8)
+        check(_lib.lib().magot_gffwrite_render_fetch(self.ctx.handle, self.handle, ptr(out),
+                                                     len(out)), 'magot_gffwrite_render_fetch')
+        return out[:need]
+
+    def render(self):
+        """Every row's line, each ended by LF, as one uint8 array."""
+        self.execute()
+        return self.fetch()
+
+    def time(self, iters):
+        """Mean device ms per pass (PASSES; 'copy': a device copy of 'out_bytes'
+        bytes, the render's yardstick) (magot_gffwrite_time)."""
+        ms = np.zeros(len(self.PASSES), np.float64)
+        n, m = ctypes.c_uint64(), ctypes.c_uint64()
+        check(_lib.lib().magot_gffwrite_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                             ctypes.byref(n), ctypes.byref(m)),
+              'magot_gffwrite_time')
+        out = dict(zip(self.PASSES, ms.tolist()))
+        out['text_bytes'] = n.value
+        out['out_bytes'] = m.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_gffwrite_destroy(self.handle)
+            self.handle = None
 
     def __del__(self):
         try:

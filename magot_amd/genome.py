@@ -32,7 +32,7 @@ import sys
 import numpy as np
 
 from . import engine
-from .py2order import order_after_copies
+from .py2order import names_after_copies, order_after_copies, py2_float_str
 
 verbose = True
 
@@ -690,6 +690,83 @@ class AnnotationSet(object):
 
 _MISSING = object()
 
+# ---------------------------------------------------------------------------
+# Annotation text (genome.py:228-238, 616-645, 733-778)
+# ---------------------------------------------------------------------------
+
+_GFF3_FORMATS = ("simple gff3", "extended gff3", "exon added gff3")
+_NOT_EXTENDED = ('ID', 'Parent', 'score', 'strand', 'seqid', 'feature_type', 'phase', 'source')
+
+
+def _py2_str(value):
+    """``str(value)`` as Python 2 prints it: a float by the twelve-digit rule."""
+    return py2_float_str(value) if type(value) is float else str(value)
+
+
+def _check_order(order):
+    order = order or DEFAULT_ORDER
+    if order not in ('insertion', 'py2'):
+        raise ValueError("order must be 'insertion' or 'py2'")
+    return order
+
+
+def _attribute_names(obj, order):
+    """The names ``obj.__dict__`` iterates over: as set, or as an old-style
+    Python 2 instance holds them after read_gff's deepcopies."""
+    names = [n for n in obj.__dict__ if n != '_magot_copies']
+    if order == 'py2':
+        aset = obj if isinstance(obj, AnnotationSet) else obj.__dict__.get('annotation_set')
+        copies = aset.__dict__.get('_magot_copies', 0) if isinstance(aset, AnnotationSet) else 0
+        names = names_after_copies(names, copies)
+    return names
+
+
+def _gff_columns(obj):
+    """The first eight columns: ``str`` of each attribute, '.' on
+    AttributeError only (genome.py:618-624, 736-743)."""
+    reads = (lambda: obj.seqid, lambda: obj.source, lambda: obj.feature_type,
+             lambda: obj.get_coords()[0], lambda: obj.get_coords()[1],
+             lambda: obj.score, lambda: obj.strand, lambda: obj.phase)
+    cols = []
+    for read in reads:
+        try:
+            cols.append(_py2_str(read()))
+        except AttributeError:
+            cols.append('.')
+    return cols
+
+
+def _extended_tags(obj, defline, order):
+    for attribute in _attribute_names(obj, order):
+        value = obj.__dict__[attribute]
+        if type(value).__name__ == 'str' and attribute not in _NOT_EXTENDED:
+            defline = defline + ';' + attribute + '=' + value
+    return defline
+
+
+def write_gff(annotation_set, gff_format="simple gff3", order=None):
+    """genome.py:228-238: every table of the set whose first entry is an
+    annotation without a parent, all of its entries, one text.  ``order``:
+    'insertion' (default) or 'py2', the order Python 2 iterates the set's
+    attribute names and each table's keys in (``py2order``)."""
+    order = _check_order(order)
+    held = annotation_set.__dict__
+    copies = held.get('_magot_copies', 0)
+    gff_lines = []
+    for attribute in _attribute_names(annotation_set, order):
+        table = held[attribute]
+        if type(table) == dict and len(table) > 0:
+            keys = list(table)
+            if order == 'py2':
+                keys = order_after_copies(keys, copies)
+            first = table[keys[0]]
+            if first.__class__.__name__ in ("ParentAnnotation", "BaseAnnotation"):
+                if first.parent == None:  # noqa: E711 (reference compares with ==)
+                    for annotation_id in keys:
+                        gff_lines.append(table[annotation_id].get_gff(gff_format, order))
+    return '\n'.join(gff_lines)
+
+
 
 class BaseAnnotation(object):
     """genome.py:586-645 (extraction part)."""
@@ -740,6 +817,34 @@ class BaseAnnotation(object):
         job = batch.add([iv], 'nuc')
         return Sequence(batch.render(_Rec(job)))
 
+    def get_gff(self, gff_format="simple gff3", order=None):
+        """genome.py:616-645."""
+        order = _check_order(order)
+        if self.annotation_set != None:  # noqa: E711
+            fields_list = _gff_columns(self)
+            if gff_format in _GFF3_FORMATS:
+                defline = 'ID=' + self.ID
+                if self.parent != None:  # noqa: E711
+                    defline = defline + ';Parent=' + self.parent
+            if gff_format == "extended gff3":
+                defline = _extended_tags(self, defline, order)
+            elif gff_format[:13] == "augustus hint":
+                gff_format_fields = gff_format.split()
+                fields_list[2] = gff_format_fields[2]
+                defline = "src=" + gff_format_fields[3]
+                if len(gff_format_fields) > 4:
+                    defline = defline + ";pri=" + gff_format_fields[4]
+            elif gff_format == "gtf":
+                defline = ('transcript_id ' + self.parent + ';gene_id '
+                           + self.annotation_set[self.parent].parent)
+            fields_list.append(defline)  # another format: UnboundLocalError, as there
+            if gff_format == "exon added gff3" and fields_list[2] == "CDS":
+                line = '\t'.join(fields_list)
+                return (line.replace('\tCDS\t', '\texon\t').replace('ID=', 'ID=ExonOf')
+                        + "\n" + line)
+            return '\t'.join(fields_list)
+        return None
+
 
 class ParentAnnotation(object):
     """genome.py:649-731 (extraction part)."""
@@ -778,6 +883,49 @@ class ParentAnnotation(object):
         batch = _Batch()
         node = self._plan_fasta(batch, seq_type, longest, genomic, name_from)
         return batch.render(node)
+
+    def get_gff(self, gff_format="simple gff3", order=None):
+        """genome.py:733-778: this feature's line (none under gtf and augustus
+        hint), then its children by coords; two children of equal coords are
+        kept apart by the clash key of genome.py:767."""
+        order = _check_order(order)
+        if self.annotation_set != None:  # noqa: E711
+            fields_list = _gff_columns(self)
+            parent_line = True
+            if gff_format in _GFF3_FORMATS:
+                defline = 'ID=' + self.ID
+                if self.parent != None:  # noqa: E711
+                    defline = defline + ';Parent=' + self.parent
+            if gff_format == "extended gff3":
+                defline = _extended_tags(self, defline, order)
+            elif gff_format[:13] == "augustus hint":
+                parent_line = False
+            elif gff_format == 'gtf':
+                parent_line = False
+            if parent_line:
+                fields_list.append(defline)
+                lines_list = ['\t'.join(fields_list)]
+            else:
+                lines_list = []
+            child_dict = {}
+            for child in self.child_list:
+                child_object = self.annotation_set[child]
+                if child_object.get_coords() not in child_dict:
+                    child_dict[child_object.get_coords()] = child_object.get_gff(gff_format, order)
+                else:
+                    child_dict[(child_object.get_coords()[0],
+                                child_object.get_coords()[1] + len(child_dict))] = \
+                        child_object.get_gff(gff_format, order)
+            for child_index in sorted(child_dict):
+                lines_list.append(child_dict[child_index])
+            if gff_format == "exon added gff3":
+                lines_list = '\n'.join(lines_list).split('\n')
+                for line in lines_list[:]:
+                    if line.split('\t')[2] == "CDS":
+                        lines_list.remove(line)
+                        lines_list.append(line)
+            return '\n'.join(lines_list)
+        return None
 
     def _plan_fasta(self, batch, seq_type, longest, genomic, name_from):
         aset = self.annotation_set
@@ -1703,4 +1851,4 @@ def _gcd(a, b):
 
 __all__ = ['Genome', 'GenomeSequence', 'AnnotationSet', 'BaseAnnotation', 'ParentAnnotation',
            'Sequence', 'read_gff', 'read_exonerate', 'read_blast_csv', 'read_cegma_gff',
-           'vulgar2gff', 'ensure_file', 'DEFAULT_ORDER', 'position_dic']
+           'vulgar2gff', 'write_gff', 'ensure_file', 'DEFAULT_ORDER', 'position_dic']

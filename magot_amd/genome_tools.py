@@ -30,6 +30,8 @@
     python -m magot_amd.genome_tools fasta2tab <fasta> [native=False]
     python -m magot_amd.genome_tools replace_names <text> <names.tsv> [name_end=';']
            [order=py2|insertion] [native=False]
+    python -m magot_amd.genome_tools convert_gff <gff> gff3|gtf|augustus|RepeatMasker <gff3|gtf|exon_added_gff3>
+           [order=py2|insertion] [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -54,6 +56,7 @@ import numpy as np
 
 from . import engine
 from . import genome
+from .py2order import py2_float_str as _py2_float_str  # the rule genome.get_gff prints scores by
 
 
 class _Clock(object):
@@ -1481,11 +1484,6 @@ def besthits_from_psl(psl, order='py2', native='True'):
 
 besthits_from_psl.last_path = None
 
-def _py2_float_str(value):
-    """str(float) of Python 2: twelve significant digits, and '.0' on a result
-    that has neither '.' nor 'e'."""
-    text = '%.12g' % value
-    return text if ('.' in text or 'e' in text or 'n' in text) else text + '.0'
 
 
 def _composition_host(fasta_alignment, order):
@@ -1980,6 +1978,79 @@ def replace_names(text_file, replace_table, name_end=' ', order='py2', native='T
 replace_names.last_path = None
 
 
+def convert_gff(gff, input_format, output_format, order='py2', native='True'):
+    """genome_tools.py:527-545: an annotation read in one format and written in
+    another.  ``input_format``: ``gff3`` (also the name under which a GTF with
+    ``gene_id``/``transcript_id`` is read) or a preset of ``read_gff``;
+    ``output_format``: ``gff3``, ``gtf`` or ``exon_added_gff3``.
+
+    On the device (engine.GffWriter) when ``input_format`` names no preset and
+    the host planner can lower the annotation to output rows; otherwise, where
+    the planner or the device declines and with ``native=False``, ``write_gff``
+    on the host restates the reference, its exceptions included.  Nothing is
+    written before the path is known.  ``convert_gff.last_path`` names the path
+    the last call took."""
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'py2' or 'insertion'")
+    if input_format == 'gff3':
+        presets = None
+    else:
+        presets = input_format
+    if output_format == 'gff3':
+        gff_format = "simple gff3"
+    elif output_format == 'gtf':
+        gff_format = 'gtf'
+    elif output_format == "exon_added_gff3":
+        gff_format = "exon added gff3"
+    else:
+        _write("currently only writes 'gff3' and 'gtf' format\n")
+        return None
+    text = None
+    if native != 'True':
+        why = "native != 'True'"
+    elif presets in genome._PRESETS:
+        why = 'preset'
+    elif not (isinstance(gff, str) and os.path.isfile(gff)):
+        why = 'not a regular file'
+    else:
+        text, why = _convert_gff_native(gff, gff_format, order)
+    if text is not None:
+        convert_gff.last_path = ('convert_gff', 'native', None)
+        _write_bytes(text, b'\n')
+    else:
+        convert_gff.last_path = ('convert_gff', 'host', why)
+        annotations = genome.read_gff(gff, presets=presets)
+        _write(genome.write_gff(annotations, gff_format, order) + '\n')
+
+
+convert_gff.last_path = None
+
+
+def _convert_gff_native(gff, gff_format, order):
+    """(text, None) from the planner's rows rendered on the device, or
+    (None, why) where the planner or the device declines."""
+    data = genome.read_buffer(gff)
+    read = engine.GffRead.read(data, for_write=True)
+    if read is None:
+        return None, 'read_gff takes a diagnostic path'
+    try:
+        plan = read.lower_write(gff_format, order)
+        if plan is None:
+            return None, 'write_gff takes a diagnostic path'
+        if not len(plan.rows):
+            return b'', None  # '\n'.join of no line
+        writer = engine.GffWriter.parse(data, plan.blob, plan.rows)
+        if isinstance(writer, tuple):
+            return None, writer[1]
+        try:
+            out = writer.render()
+        finally:
+            writer.close()
+        return out[:-1], None  # write_gff joins the lines: the last has no LF
+    finally:
+        read.close()
+
+
 TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at_content_from_fasta,
          'fqstats': fqstats, 'purge_overlaps': purge_overlaps, 'besthits_from_psl': besthits_from_psl,
          'extract_upstream_downstream': extract_upstream_downstream,
@@ -1990,7 +2061,7 @@ TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at
          'composition_by_site': composition_by_site,
          'heterozygosity_from_vcf': heterozygosity_from_vcf,
          'exclude_from_fasta': exclude_from_fasta, 'fasta2tab': fasta2tab,
-         'replace_names': replace_names}
+         'replace_names': replace_names, 'convert_gff': convert_gff}
 
 
 def parse_argv(argv):

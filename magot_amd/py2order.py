@@ -87,3 +87,37 @@ def order_after_copies(keys, copies=1):
     for _ in range(copies):
         out = dict_order(out)
     return out
+
+
+def merge_order(keys):
+    """Iteration order of an empty Py2 dict after ``dict.update(other)``, with
+    ``keys`` the iteration order of ``other`` (CPython 2.7 PyDict_Merge): the
+    table is presized once to the smallest power of two > 2 * len(other) when
+    len(other) * 3 >= 8 * 2, then every entry is placed in the slot order of
+    ``other`` with no further resize."""
+    size = 8
+    if len(keys) * 3 >= size * 2:
+        while size <= 2 * len(keys):
+            size <<= 1
+    t = _SlotTable(size)
+    for k in keys:
+        t._place(k, str_hash(k))
+    return t.order()
+
+
+def names_after_copies(names, copies=1):
+    """Attribute names of an old-style instance set in the order ``names``,
+    after ``copies`` rounds of ``copy.deepcopy``: each round rebuilds the
+    ``__dict__`` by insertion (_deepcopy_dict) and then merges it into the new
+    instance's empty ``__dict__`` (``y.__dict__.update(state)``)."""
+    out = dict_order(names)
+    for _ in range(copies):
+        out = merge_order(dict_order(out))
+    return out
+
+
+def py2_float_str(value):
+    """str(float) of Python 2: twelve significant digits, and '.0' on a result
+    that has neither '.' nor 'e'."""
+    text = '%.12g' % value
+    return text if ('.' in text or 'e' in text or 'n' in text) else text + '.0'
