@@ -343,6 +343,20 @@ int magot_debug_tile_cut(const uint64_t* ex_out, uint64_t n_ex, const uint64_t* 
                          const uint64_t* tx_pep, uint64_t n_rec, uint32_t lane_chunks, void* tiles,
                          uint64_t tiles_cap, uint64_t* n_tiles);
 
+/* Debug (no device): the six-frame kernel's tile cut (orf6_plan_tiles), as
+ * magot_orf6_batch and magot_plan_orf6 upload it.  noff = n_rec + 1 offsets of
+ * the records in the walked concatenation.  row_start = the n_rows starts of
+ * the non-empty intervals in it, ascending, then noff[n_rec] as their sentinel
+ * (n_rows + 1 entries), or NULL for the raw-byte batch, which has no interval
+ * rows.  t0 receives *n_tiles + 1 tile starts (the last one the total), r0
+ * the record holding each start; e0 (the interval holding each staged
+ * window's first base) and m (the window's rows, capped) are written only
+ * with row_start and may be NULL without it.  At most tiles_cap tiles are
+ * written; t0 == NULL: the count only. */
+int magot_debug_orf6_tiles(const uint64_t* noff, uint64_t n_rec, const uint64_t* row_start,
+                           uint64_t n_rows, uint64_t* t0, uint32_t* r0, uint32_t* e0, uint32_t* m,
+                           uint64_t tiles_cap, uint64_t* n_tiles);
+
 /* Debug (no device): everything magot_plan_create plans before it touches
  * the device, for contigs given as to magot_genome_load (packed on the host)
  * and tables and output flags given as to magot_plan_create; the same status
@@ -497,6 +511,12 @@ int magot_orf6_sizes(const uint64_t* seq_off, uint64_t n, uint64_t* stream_off,
  * length); any other table is refused with MAGOT_ERR_ARG before a launch. */
 int magot_orf6_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n,
                      const uint8_t* lut64, const uint64_t* stream_off, uint8_t* out);
+/* Debug: magot_orf6_batch with its device output filled with the byte
+ * `poison` (0..255) before the launch, so that a chunk no lane wrote shows in
+ * out; poison < 0 fills nothing (magot_orf6_batch itself). */
+int magot_debug_orf6_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n,
+                           const uint8_t* lut64, const uint64_t* stream_off, uint8_t* out,
+                           int32_t poison);
 /* The same over an extraction plan's records, in HBM (BASELINE configs[4],
  * C5): one kernel gathers each record from the packed genome through the
  * plan's intervals and writes its six translations (the plan's nucleotide
@@ -511,6 +531,10 @@ typedef struct magot_orf6 magot_orf6;
 int magot_plan_orf6(magot_ctx* ctx, magot_plan* p, const uint8_t* lut64, magot_orf6** out,
                     uint64_t* total_res);
 int magot_orf6_execute(magot_ctx* ctx, magot_orf6* o);
+/* Debug: fill the plan's output (total_res bytes) with `byte` on the context
+ * stream.  magot_orf6_execute does not clear its output, so without this a
+ * chunk that no lane wrote keeps what an earlier execute left there. */
+int magot_orf6_poison(magot_ctx* ctx, magot_orf6* o, uint8_t byte);
 int magot_orf6_fetch(magot_ctx* ctx, magot_orf6* o, uint8_t* out, uint64_t* stream_off,
                      uint64_t* stream_len);
 /* D2D copy of the padded residue bytes (total_res) into caller device memory

@@ -50,7 +50,8 @@ EXPORTS = (
     'magot_genome_wire_export', 'magot_genome_wire_import',
     'magot_debug_tile_blocks', 'magot_debug_tile_cut', 'magot_debug_plan',
     'magot_debug_text_index', 'magot_debug_text_lines', 'magot_debug_piece_copy',
-    'magot_debug_text_assembly',
+    'magot_debug_text_assembly', 'magot_debug_orf6_tiles', 'magot_debug_orf6_batch',
+    'magot_orf6_poison',
     'magot_orfcall_tile', 'magot_orfcall_create', 'magot_orfcall_fetch', 'magot_orfcall_text',
     'magot_orfcall_text_fetch', 'magot_orfcall_time', 'magot_orfcall_destroy',
     'magot_mask_piece', 'magot_mask_plan', 'magot_maskplan_table', 'magot_maskplan_destroy',
@@ -250,6 +251,11 @@ def _declare(lib):
         'magot_plan_copy_outputs': (ctypes.c_int, [_vp, _vp, _vp, _vp]),
         'magot_orf6_sizes': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp]),
         'magot_orf6_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+        'magot_debug_orf6_batch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                                  ctypes.c_int32]),
+        'magot_debug_orf6_tiles': (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp,
+                                                  _vp, _vp, _vp, ctypes.c_uint64, _u64p]),
+        'magot_orf6_poison': (ctypes.c_int, [_vp, _vp, ctypes.c_uint8]),
         'magot_plan_orf6': (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_vp), _u64p]),
         'magot_orf6_execute': (ctypes.c_int, [_vp, _vp]),
         'magot_orf6_fetch': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),

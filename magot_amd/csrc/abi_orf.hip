@@ -196,6 +196,16 @@ int magot_orf6_execute(magot_ctx* ctx, magot_orf6* o) {
   return MAGOT_OK;
 }
 
+int magot_orf6_poison(magot_ctx* ctx, magot_orf6* o, uint8_t byte) {
+  if (int rc = bind(ctx)) return rc;
+  if (!o) {
+    set_error("magot_orf6_poison: null handle");
+    return MAGOT_ERR_ARG;
+  }
+  if (o->total) MAGOT_HIP_TRY(hipMemsetAsync(o->out, byte, o->total, ctx->stream));
+  return MAGOT_OK;
+}
+
 int magot_orf6_fetch(magot_ctx* ctx, magot_orf6* o, uint8_t* out, uint64_t* stream_off,
                      uint64_t* stream_len) {
   if (int rc = bind(ctx)) return rc;

@@ -275,8 +275,38 @@ int magot_orf6_sizes(const uint64_t* seq_off, uint64_t n, uint64_t* stream_off,
   return MAGOT_OK;
 }
 
+int magot_debug_orf6_tiles(const uint64_t* noff, uint64_t n_rec, const uint64_t* row_start,
+                           uint64_t n_rows, uint64_t* t0, uint32_t* r0, uint32_t* e0, uint32_t* m,
+                           uint64_t tiles_cap, uint64_t* n_tiles) {
+  if (!noff || !n_tiles || (t0 && !r0) || (t0 && row_start && (!e0 || !m))) {
+    set_error("magot_debug_orf6_tiles: null argument");
+    return MAGOT_ERR_ARG;
+  }
+  Orf6Tiles tiles;
+  orf6_plan_tiles(noff, n_rec, row_start, n_rows, &tiles);
+  *n_tiles = tiles.r0.size();
+  if (!t0) return MAGOT_OK;
+  if (*n_tiles > tiles_cap) {
+    set_error("magot_debug_orf6_tiles: tile arrays too small");
+    return MAGOT_ERR_ARG;
+  }
+  std::memcpy(t0, tiles.t0.data(), tiles.t0.size() * 8);
+  std::memcpy(r0, tiles.r0.data(), tiles.r0.size() * 4);
+  if (row_start) {
+    std::memcpy(e0, tiles.e0.data(), tiles.e0.size() * 4);
+    std::memcpy(m, tiles.m.data(), tiles.m.size() * 4);
+  }
+  return MAGOT_OK;
+}
+
 int magot_orf6_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n,
                      const uint8_t* lut64, const uint64_t* stream_off, uint8_t* out) {
+  return magot_debug_orf6_batch(ctx, seqs, seq_off, n, lut64, stream_off, out, -1);
+}
+
+int magot_debug_orf6_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n,
+                           const uint8_t* lut64, const uint64_t* stream_off, uint8_t* out,
+                           int32_t poison) {
   if (int rc = bind(ctx)) return rc;
   if (!seq_off || !stream_off) {
     set_error("magot_orf6_batch: null argument");
@@ -325,6 +355,8 @@ int magot_orf6_batch(magot_ctx* ctx, const uint8_t* seqs, const uint64_t* seq_of
   cv.place(d);
   char* base = static_cast<char*>(d);
   hipError_t e = hipMemcpyAsync(base + o_in, seqs, total, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && poison >= 0)
+    e = hipMemsetAsync(a.out, poison & 0xFF, total_res, ctx->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(base + o_lut, tables, 256, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess)

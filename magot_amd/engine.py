@@ -926,10 +926,14 @@ def revcomp_batch(seqs, ctx=None):
     return [raw[int(off[i]):int(off[i + 1])].decode('latin-1') for i in range(len(seqs))]
 
 
-def orf6_batch(seqs, lut64=None, ctx=None):
+def orf6_batch(seqs, lut64=None, ctx=None, poison=None, raw=False):
     """The six translations Sequence.get_orfs splits (genome.py:824-851), per
     input: a list of 6 values in the reference's loop order (frame 0,1,2 x
-    strand '-','+'), each the trimmed ``translate()`` result or None."""
+    strand '-','+'), each the trimmed ``translate()`` result or None.
+
+    Test hooks: ``poison`` (a byte value) fills the device output before the
+    launch (magot_debug_orf6_batch); ``raw`` returns the untrimmed buffer as
+    (padded residue bytes, stream offsets 6n+1, real stream lengths 6n)."""
     ctx = ctx or _lib.default_context()
     n = len(seqs)
     buf, off = _concat(seqs)
@@ -941,8 +945,13 @@ def orf6_batch(seqs, lut64=None, ctx=None):
     total = int(soff[6 * n])
     out = np.empty(max(total, 1), dtype=np.uint8)
     lut = np.frombuffer(bytes(lut64), dtype=np.uint8).copy() if lut64 is not None else None
-    check(L.magot_orf6_batch(ctx.handle, ptr(buf) if len(buf) else None, ptr(off), n, ptr(lut),
-                             ptr(soff), ptr(out)), 'magot_orf6_batch')
+    args = (ctx.handle, ptr(buf) if len(buf) else None, ptr(off), n, ptr(lut), ptr(soff), ptr(out))
+    if poison is None:
+        check(L.magot_orf6_batch(*args), 'magot_orf6_batch')
+    else:
+        check(L.magot_debug_orf6_batch(*args, int(poison) & 0xFF), 'magot_debug_orf6_batch')
+    if raw:
+        return out[:total], soff, slen[:6 * n]
     raw = out[:total].tobytes().decode('latin-1')
     res = []
     for r in range(n):
@@ -978,6 +987,11 @@ class Orf6Plan(object):
 
     def execute(self):
         check(_lib.lib().magot_orf6_execute(self.ctx.handle, self.handle), 'magot_orf6_execute')
+
+    def poison(self, byte):
+        """Test hook: fill the output with ``byte`` (execute() does not clear it)."""
+        check(_lib.lib().magot_orf6_poison(self.ctx.handle, self.handle, int(byte) & 0xFF),
+              'magot_orf6_poison')
 
     def fetch(self):
         """(padded residue bytes, stream offsets 6n+1 (16-aligned), real stream lengths 6n)."""
