@@ -1374,6 +1374,86 @@ void magot_rename_params(uint32_t* max_name, uint32_t* text_block, uint32_t* pie
 void magot_rename_destroy(magot_rename* p);
 
 /*
+ * Column cuts of a tab-separated text on the device: tab2fasta
+ * (magot_smallfuncs.py:12-18) and repeatmasker2augustushints
+ * (genome_tools.py:449-454).  The text is resident, as a PSL's.
+ *
+ * A cut is a program of at most max_items items run on every line (lines end
+ * at LF).  A line with fewer than `need` TABs is skipped
+ * (MAGOT_TABCUT_SHORT_SKIP) or reported (MAGOT_TABCUT_SHORT_ERROR) and prints
+ * nothing; every other line prints its items one after the other.  An item is
+ * a literal, the b bytes at offset a of `literals`, or a field range, the
+ * source bytes from the first byte of field a to the last byte of field b,
+ * the TABs between them included (a <= b <= need; fields count from 0).  A
+ * field ends at one of the line's first `need` TABs; field `need` ends at the
+ * next TAB when the line has one, else at the line's end less the LF and less
+ * one CR before it.  tab2fasta is need 1, MAGOT_TABCUT_SHORT_ERROR, cr_check 1
+ * and ">" F[0..0] LF F[1..1] LF; the hints are need 6, MAGOT_TABCUT_SHORT_SKIP,
+ * cr_check 0 and F[0..1] "\tnonexonpart\t" F[3..5] "\t.\t.\tpri=2;src=RM\n".
+ * No pass reads a field's bytes: a line costs a search in the TAB offsets and
+ * its items, whatever its length.
+ *   magot_tabcut_parse  uploads text and literals, indexes the LFs and the
+ *       TABs, gives every line its verdict and lays the output out.  Declined
+ *       with MAGOT_ERR_UNSUPPORTED, *out = NULL and *reason a MAGOT_TABCUT_*
+ *       code: a text longer than max_bytes (0: a quarter of the free device
+ *       memory), before anything of that size is allocated or read, or one
+ *       whose tables exceed half the free device memory; 2^31 - 1 lines or
+ *       more; with cr_check, a CR that is neither directly before an LF nor the
+ *       text's last byte.  MAGOT_ERR_ARG before any launch: a null argument,
+ *       more than max_items items, an item of no known kind, a field range
+ *       that decreases or names a field above `need`, a literal that leaves
+ *       the blob, a short_mode that is neither of the two.  A short line under
+ *       MAGOT_TABCUT_SHORT_ERROR is no decline: the parse succeeds and
+ *       magot_tabcut_sizes reports the line.
+ *   magot_tabcut_sizes  the text's lines, its TABs, the kept lines, the
+ *       output's pieces and bytes, and the lowest short line of error mode
+ *       (0-based), all ones when there is none.
+ *   magot_tabcut_upload_ms  as magot_psl_upload_ms.
+ *   magot_tabcut_rows  per line: its verdict (MAGOT_TABCUT_LINE_*) and where
+ *       its output begins.  Either pointer may be NULL.
+ *   magot_tabcut_render  the kept lines' output into a device buffer of the
+ *       handle; *bytes: its length.
+ *   magot_tabcut_render_fetch  that text to the host (cap >= its length).
+ *   magot_tabcut_time  mean device ms over `iters` runs of: the two indexes,
+ *       the rows, the layout, the piece list, the copy into the output
+ *       (*out_bytes), and a device copy of the text (*text_bytes), in
+ *       ms6[0..5].  The handle's answers stand afterwards; a rendered text does
+ *       not.
+ *   magot_tabcut_params  the bytes of an item one lane slot of the copy takes,
+ *       the bytes of a text block of the indexes, and the most items of a
+ *       program.
+ */
+enum {
+  MAGOT_TABCUT_STRAY_CR = 1,       /* a CR in mid-line (cr_check) */
+  MAGOT_TABCUT_TOO_LARGE = 2,      /* the text or its line and TAB tables */
+  MAGOT_TABCUT_TOO_MANY_LINES = 3  /* 2^31 - 1 lines or more */
+};
+enum { MAGOT_TABCUT_ITEM_LITERAL = 0, MAGOT_TABCUT_ITEM_FIELDS = 1 };
+enum { MAGOT_TABCUT_SHORT_SKIP = 0, MAGOT_TABCUT_SHORT_ERROR = 1 };
+enum { MAGOT_TABCUT_LINE_SKIPPED = 0, MAGOT_TABCUT_LINE_KEPT = 1, MAGOT_TABCUT_LINE_SHORT = 2 };
+typedef struct magot_tabcut_item {
+  uint32_t kind; /* MAGOT_TABCUT_ITEM_* */
+  uint32_t a, b; /* a literal: offset and length in the blob; fields: first and last */
+} magot_tabcut_item;
+typedef struct magot_tabcut magot_tabcut;
+int magot_tabcut_parse(magot_ctx* ctx, const char* text, uint64_t len,
+                       const magot_tabcut_item* items, uint32_t n_items, const uint8_t* literals,
+                       uint64_t literals_len, uint32_t need, uint32_t short_mode,
+                       uint32_t cr_check, uint64_t max_bytes, magot_tabcut** out,
+                       uint32_t* reason);
+int magot_tabcut_sizes(const magot_tabcut* p, uint64_t* n_lines, uint64_t* n_tabs,
+                       uint64_t* n_kept, uint64_t* n_pieces, uint64_t* out_bytes,
+                       uint64_t* short_line);
+double magot_tabcut_upload_ms(const magot_tabcut* p);
+int magot_tabcut_rows(magot_ctx* ctx, magot_tabcut* p, uint8_t* verdict, uint64_t* offset);
+int magot_tabcut_render(magot_ctx* ctx, magot_tabcut* p, uint64_t* bytes);
+int magot_tabcut_render_fetch(magot_ctx* ctx, magot_tabcut* p, uint8_t* out, uint64_t cap);
+int magot_tabcut_time(magot_ctx* ctx, magot_tabcut* p, int iters, double* ms6,
+                      uint64_t* text_bytes, uint64_t* out_bytes);
+void magot_tabcut_params(uint32_t* piece, uint32_t* text_block, uint32_t* max_items);
+void magot_tabcut_destroy(magot_tabcut* p);
+
+/*
  * write_gff (genome.py:228-238, 616-645, 733-778) as a table of output lines:
  * the annotation lowered on the host, its text rendered on the device.
  *

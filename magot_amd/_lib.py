@@ -85,6 +85,9 @@ EXPORTS = (
     'magot_rename_parse', 'magot_rename_sizes', 'magot_rename_upload_ms', 'magot_rename_hits',
     'magot_rename_render', 'magot_rename_render_fetch', 'magot_rename_time',
     'magot_rename_params', 'magot_rename_destroy',
+    'magot_tabcut_parse', 'magot_tabcut_sizes', 'magot_tabcut_upload_ms', 'magot_tabcut_rows',
+    'magot_tabcut_render', 'magot_tabcut_render_fetch', 'magot_tabcut_time',
+    'magot_tabcut_params', 'magot_tabcut_destroy',
     'magot_gff_lower_write', 'magot_gffplan_write_views',
     'magot_gffwrite_open', 'magot_gffwrite_sizes', 'magot_gffwrite_upload_ms',
     'magot_gffwrite_render', 'magot_gffwrite_render_fetch', 'magot_gffwrite_time',
@@ -138,6 +141,13 @@ FASTAREC_REASONS = (None, 'leading_text', 'stray_cr', 'long_name', 'hash_collisi
 FASTAREC_STYLES = {'fasta': 0, 'tab': 1}
 # magot_rename_parse's reasons (MAGOT_RENAME_*), by code
 RENAME_REASONS = (None, 'too_large', 'hash_collision', 'table_too_large')
+# magot_tabcut_parse's reasons (MAGOT_TABCUT_*), by code
+TABCUT_REASONS = (None, 'stray_cr', 'too_large', 'too_many_lines')
+TABCUT_LITERAL, TABCUT_FIELDS = 0, 1
+TABCUT_SHORT = {'skip': 0, 'error': 1}
+TABCUT_SKIPPED, TABCUT_KEPT, TABCUT_SHORT_LINE = 0, 1, 2
+# magot_tabcut_item (include/magot.h)
+TABCUT_ITEM_DTYPE = np.dtype([('kind', '<u4'), ('a', '<u4'), ('b', '<u4')])
 # magot_gffwrite_open's reasons (MAGOT_GFFWRITE_*), by code
 GFFWRITE_REASONS = (None, 'too_large', 'score', 'columns')
 # magot_gffrow (include/magot.h)
@@ -439,6 +449,19 @@ def _declare(lib):
         'magot_rename_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p, _u64p]),
         'magot_rename_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3),
         'magot_rename_destroy': (None, [_vp]),
+        'magot_tabcut_parse': (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp,
+                                              ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_uint32, ctypes.c_uint64,
+                                              ctypes.POINTER(_vp),
+                                              ctypes.POINTER(ctypes.c_uint32)]),
+        'magot_tabcut_sizes': (ctypes.c_int, [_vp] + [_u64p] * 6),
+        'magot_tabcut_upload_ms': (ctypes.c_double, [_vp]),
+        'magot_tabcut_rows': (ctypes.c_int, [_vp] * 4),
+        'magot_tabcut_render': (ctypes.c_int, [_vp, _vp, _u64p]),
+        'magot_tabcut_render_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_tabcut_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u64p, _u64p]),
+        'magot_tabcut_params': (None, [ctypes.POINTER(ctypes.c_uint32)] * 3),
+        'magot_tabcut_destroy': (None, [_vp]),
         'magot_gff_lower_write': (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p,
                                                  _u64p]),
         'magot_gffplan_write_views': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _u64p,

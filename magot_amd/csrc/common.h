@@ -1115,6 +1115,60 @@ hipError_t launch_rn_layout(const RnArgs& a, void* tmp, size_t tmp_bytes, hipStr
 hipError_t launch_rn_render(const RnArgs& a, const RnRenderArgs& r, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// tab2fasta, repeatmasker2augustushints: column cuts of a resident text
+// (tabcut.hip; magot_smallfuncs.py:12-18, genome_tools.py:449-454;
+// magot_tabcut_*)
+// ---------------------------------------------------------------------------
+// A cut is a small program run on every line: a line with fewer than `need`
+// TABs is skipped or reported, every other line prints the program's items, a
+// literal of the blob or the source bytes of the fields a..b (inner TABs
+// included).  A field ends at one of the line's first `need` TABs; field
+// `need` ends at the next TAB when the line has one, else at the line's end
+// less the LF and less one CR before it.  No pass reads a field's bytes: a
+// line's cost is a search in the TAB offsets and the items.
+constexpr uint32_t kTcPiece = 4096;  // bytes of an item one lane slot of the copy takes
+constexpr uint32_t kTcMaxItems = 8;
+constexpr uint64_t kTcMaxLines = (1ull << 31) - 1;
+constexpr int kTcGroup = 16;         // pieces per wave of the copy
+constexpr uint32_t kTcShortLine = 1;  // the status word's reason
+enum { kTcLiteral = 0, kTcFields = 1 };              // TcItem::kind (MAGOT_TABCUT_ITEM_*)
+enum { kTcShortSkip = 0, kTcShortError = 1 };        // TcArgs::short_mode (MAGOT_TABCUT_SHORT_*)
+enum { kTcSkipped = 0, kTcKept = 1, kTcShort = 2 };  // a line's verdict (MAGOT_TABCUT_LINE_*)
+struct TcItem {
+  uint32_t kind;
+  uint32_t a, b;  // a literal: offset and length in the blob; fields: a <= b <= need
+};
+struct TcArgs {
+  // the text (readable to the next multiple of 16 and 16 more) and its two
+  // indexes: ix.pos[k] is where line k starts, tx.pos[j] the offset of TAB j
+  // (tx counts nothing itself: its blk and pre are ix's blk2 and pre2)
+  TextIndexArgs ix, tx;
+  uint64_t n_tabs;
+  uint32_t need, short_mode, n_items;
+  TcItem items[kTcMaxItems];
+  uint64_t lit_base;  // the literal blob's first byte, counted from `text` (as readable as it)
+  unsigned long long* status;  // [0]: the stray-CR check's word; [1]: min of (line << 8 |
+                               // kTcShortLine) over the short lines of error mode; ~0 when clean
+  unsigned long long* n_kept;  // the lines with the verdict kTcKept
+  // per line, ix.n_lines + 1 of each (the last entry of olen and pcnt 0, of the scans the total)
+  uint8_t* verdict;
+  uint64_t* tab0;           // the line's first TAB in tx.pos (n_tabs where none follows)
+  uint64_t *olen, *obase;   // bytes the line prints; the scan
+  uint64_t *pcnt, *pbase;   // its pieces of at most kTcPiece bytes, none for an empty item; the scan
+};
+struct TcRenderArgs {
+  uint64_t n_pieces;
+  uint64_t *p_src, *p_dst;  // n_pieces: from `text`, in `out`
+  uint32_t* p_len;
+  uint8_t* out;        // out_bytes, 16-byte aligned
+  uint64_t out_bytes;  // obase[n_lines]
+};
+hipError_t launch_tc_rows(const TcArgs& a, hipStream_t s);
+hipError_t launch_tc_layout(const TcArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_tc_pieces(const TcArgs& a, const TcRenderArgs& r, hipStream_t s);
+hipError_t launch_tc_copy(const TcArgs& a, const TcRenderArgs& r, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // write_gff's text from a table of rows (gffwrite.hip; magot.h: magot_gffrow).
 // Pass 1, one lane per row: the eight tabs of the row's source line, its score
 // and phase classified, the output line's exact length.  A scan of the lengths.

@@ -2224,6 +2224,129 @@ class NameReplacer(object):
             pass
 
 
+class TabCut(object):
+    """A column cut of a resident tab-separated text (magot_tabcut_*;
+    magot_smallfuncs.py:12-18, genome_tools.py:449-454): for every line a few
+    leading fields taken by their TAB positions and printed with literals
+    between them.  A program is ``need`` (the TABs a line must have),
+    ``short`` ('skip' or 'error': what a line with fewer does), ``cr_check``
+    and its items: a byte string is a literal, a pair ``(a, b)`` the source
+    bytes of the fields a..b, inner TABs included.  The LFs and the TABs are
+    indexed in one pass; one lane per line finds its TABs by a search and lays
+    the line out, one lane per 4 KiB piece names a copy, and a grouped copy
+    writes the text: no lane walks a field.  ``parse`` returns (None, reason)
+    where the device declines: 'stray_cr', 'too_large', 'too_many_lines'."""
+
+    PASSES = ('index', 'rows', 'layout', 'pieces', 'render', 'copy')
+    TAB2FASTA = dict(need=1, short='error', cr_check=True,
+                     items=(b'>', (0, 0), b'\n', (1, 1), b'\n'))
+    HINTS = dict(need=6, short='skip', cr_check=False,
+                 items=((0, 1), b'\tnonexonpart\t', (3, 5), b'\t.\t.\tpri=2;src=RM\n'))
+
+    def __init__(self):
+        self.ctx = None
+        self.handle = None
+        self.n_lines = self.n_tabs = self.n_kept = self.n_pieces = self.out_bytes = 0
+        self.short_line = None  # the lowest short line of 'error' (0-based), None when none
+        self.upload_ms = 0.0
+
+    @staticmethod
+    def lower(items):
+        """(the magot_tabcut_item rows, the literal blob) of a program's items"""
+        rows = np.zeros(len(items), _lib.TABCUT_ITEM_DTYPE)
+        blob = bytearray()
+        for row, item in zip(rows, items):
+            if isinstance(item, (bytes, bytearray)):
+                row['kind'], row['a'], row['b'] = _lib.TABCUT_LITERAL, len(blob), len(item)
+                blob += item
+            else:
+                row['kind'], row['a'], row['b'] = _lib.TABCUT_FIELDS, item[0], item[1]
+        return rows, np.frombuffer(bytes(blob), np.uint8)
+
+    @classmethod
+    def parse(cls, data, need, short, items, cr_check=False, max_bytes=0, ctx=None):
+        """The text in ``data`` (bytes, a buffer, an mmap, numpy) made resident,
+        indexed and laid out under the program.  ``max_bytes``: a longer text is
+        declined (0: a quarter of the free device memory).  A short line under
+        'error' is no decline: ``short_line`` names the lowest."""
+        self = cls()
+        self.ctx = ctx or _lib.default_context()
+        view = _text_view(data)
+        rows, blob = cls.lower(items)
+        return self._open(view, rows, blob, need, _lib.TABCUT_SHORT[short], cr_check, max_bytes)
+
+    def _open(self, view, rows, blob, need, short_mode, cr_check, max_bytes):
+        h, reason = ctypes.c_void_p(), ctypes.c_uint32()
+        rc = _lib.lib().magot_tabcut_parse(
+            self.ctx.handle, _text_ptr(view), len(view), ptr(rows) if len(rows) else None,
+            len(rows), _text_ptr(blob), len(blob), int(need), int(short_mode),
+            1 if cr_check else 0, int(max_bytes or 0), ctypes.byref(h), ctypes.byref(reason))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return None, _lib.TABCUT_REASONS[reason.value]
+        check(rc, 'magot_tabcut_parse')
+        self.handle = h
+        sizes = [ctypes.c_uint64() for _ in range(6)]
+        check(_lib.lib().magot_tabcut_sizes(h, *[ctypes.byref(x) for x in sizes]),
+              'magot_tabcut_sizes')
+        (self.n_lines, self.n_tabs, self.n_kept, self.n_pieces, self.out_bytes,
+         short_line) = [x.value for x in sizes]
+        self.short_line = None if short_line == 2 ** 64 - 1 else short_line
+        self.upload_ms = float(_lib.lib().magot_tabcut_upload_ms(h))
+        return self
+
+    @staticmethod
+    def params():
+        """{'piece': the bytes of an item one lane slot of the copy takes,
+        'text_block': the bytes per workgroup of the indexes, 'max_items': the
+        most items of a program}"""
+        vals = [ctypes.c_uint32() for _ in range(3)]
+        _lib.lib().magot_tabcut_params(*[ctypes.byref(v) for v in vals])
+        return dict(zip(('piece', 'text_block', 'max_items'), [v.value for v in vals]))
+
+    def rows(self):
+        """Per line, as a dict of arrays: 'verdict' (0 skipped, 1 kept, 2
+        short under 'error') and 'offset' (where its output begins)."""
+        verdict = np.zeros(max(self.n_lines, 1), np.uint8)
+        offset = np.zeros(max(self.n_lines, 1), np.uint64)
+        check(_lib.lib().magot_tabcut_rows(self.ctx.handle, self.handle, ptr(verdict),
+                                           ptr(offset)), 'magot_tabcut_rows')
+        return {'verdict': verdict[:self.n_lines], 'offset': offset[:self.n_lines]}
+
+    def render(self):
+        """What the kept lines print, as one uint8 array."""
+        need = ctypes.c_uint64()
+        check(_lib.lib().magot_tabcut_render(self.ctx.handle, self.handle, ctypes.byref(need)),
+              'magot_tabcut_render')
+        out = np.empty(max(need.value, 1), np.uint8)
+        check(_lib.lib().magot_tabcut_render_fetch(self.ctx.handle, self.handle, ptr(out),
+                                                   need.value), 'magot_tabcut_render_fetch')
+        return out[:need.value]
+
+    def time(self, iters):
+        """Mean device ms per pass (PASSES; 'render': the copy into the output,
+        'out_bytes' bytes; 'copy': a device copy of the text, 'text_bytes' bytes)
+        (magot_tabcut_time)."""
+        ms = np.zeros(len(self.PASSES), np.float64)
+        n, m = ctypes.c_uint64(), ctypes.c_uint64()
+        check(_lib.lib().magot_tabcut_time(self.ctx.handle, self.handle, int(iters), ptr(ms),
+                                           ctypes.byref(n), ctypes.byref(m)), 'magot_tabcut_time')
+        out = dict(zip(self.PASSES, ms.tolist()))
+        out['text_bytes'] = n.value
+        out['out_bytes'] = m.value
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_tabcut_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SiteCounts(object):
     """composition_by_site's counting pass over a resident genome
     (magot_site_*, genome_tools.py:488-503): the alignment's rows are contigs of

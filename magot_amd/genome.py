@@ -144,6 +144,18 @@ def fasta2tab(fasta_file):
     return '\n'.join(''.join(row) for row in rows)
 
 
+def tab2fasta(tab_file):
+    """magot_smallfuncs.py:12-18: every line of a table as ``>`` its first
+    field, LF, its second field, joined by LF, in file order; the LF and every
+    CR of a line go before it is split at its TABs.  A line without a TAB, an
+    empty one included, is an IndexError."""
+    rows = []
+    for line in ensure_file(tab_file):
+        fields = line.replace('\n', '').replace('\r', '').split('\t')
+        rows.append('>' + fields[0] + '\n' + fields[1])
+    return '\n'.join(rows)
+
+
 # ---------------------------------------------------------------------------
 # Sequence (genome.py:781-851)
 # ---------------------------------------------------------------------------

@@ -32,6 +32,8 @@
            [order=py2|insertion] [native=False]
     python -m magot_amd.genome_tools convert_gff <gff> gff3|gtf|augustus|RepeatMasker <gff3|gtf|exon_added_gff3>
            [order=py2|insertion] [native=False]
+    python -m magot_amd.genome_tools tab2fasta <table.tab> [native=False]
+    python -m magot_amd.genome_tools repeatmasker2augustushints <repeatmasker.gff> [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -1798,6 +1800,111 @@ def fasta2tab(fasta_file, native='True'):
 fasta2tab.last_path = None
 
 
+def _tabcut_native(path, program, clock):
+    """(the cut text as a uint8 array, None) from the device: engine.TabCut
+    under ``program``.  (None, reason) where the device declines.  Raises the
+    reference's IndexError for a short line the program reports."""
+    data = genome.read_buffer(path)
+    clock.lap('open')
+    cut = engine.TabCut.parse(data, **program)
+    clock.lap('kernels')
+    if isinstance(cut, tuple):
+        return cut
+    try:
+        if cut.short_line is not None:
+            raise IndexError('list index out of range')  # fields[1] of a line without a TAB
+        text = cut.render()
+        clock.lap('render')
+        return text, None
+    finally:
+        cut.close()
+
+
+def tab2fasta(tab_file, native='True'):
+    """genome_tools.py:345-346 over magot_smallfuncs.py:12-18: every line of a
+    table as ``>`` its first field, LF, its second field, LF, in file order;
+    further fields are dropped, and the LF and every CR of a line go before it
+    is split.  A line without a TAB, an empty one included, is an IndexError,
+    and nothing is printed.  An empty table prints one LF.
+
+    On the device (engine.TabCut: the fields cut by their TAB offsets at a cost
+    that does not depend on a line's length, the text written by a grouped copy)
+    for a regular file the device does not decline -- a CR that is neither
+    before an LF nor the file's last byte, a text too large; otherwise, and with
+    ``native=False``, genome.tab2fasta on the host, a string that names no file
+    read as the text itself included.  ``tab2fasta.last_path`` names the path
+    the last call took."""
+    clock = _Clock()
+    if native != 'True':
+        why = "native != 'True'"
+    elif not (isinstance(tab_file, str) and os.path.isfile(tab_file)):
+        why = 'not a regular file'
+    else:
+        tab2fasta.last_path = ('tab2fasta', 'native', None)
+        text, why = _tabcut_native(tab_file, engine.TabCut.TAB2FASTA, clock)
+        if text is not None:
+            _write_bytes(text if len(text) else b'\n')  # `print ''`
+            clock.lap('write')
+            clock.emit()
+            return
+    tab2fasta.last_path = ('tab2fasta', 'host', why)
+    _write(genome.tab2fasta(tab_file) + '\n')
+    clock.lap('write')
+    clock.emit()
+
+
+tab2fasta.last_path = None
+
+
+def _hints_host(data):
+    """The reference's loop restated over bytes: every line with more than five
+    TABs as its fields 0, 1, 3, 4 and 5 among the hint's constants."""
+    out = []
+    for line in data.split(b'\n'):
+        if line.count(b'\t') > 5:  # the LF holds no TAB, and field 5 is never the last
+            f = line.split(b'\t')
+            out.append(b'\t'.join([f[0], f[1], b'nonexonpart', f[3], f[4], f[5], b'.', b'.',
+                                   b'pri=2;src=RM']) + b'\n')
+    return out
+
+
+def repeatmasker2augustushints(repeatmasker_gff, native='True'):
+    """genome_tools.py:449-454: a RepeatMasker GFF as AUGUSTUS hints.  Every
+    line with more than five TABs prints its columns 1, 2, 4, 5 and 6 as
+    ``c1 c2 nonexonpart c4 c5 c6 . . pri=2;src=RM``; every other line prints
+    nothing, and ``#`` lines are lines like any other.  Nothing is stripped: a
+    CR inside those columns is copied.  A path that does not open is an
+    OSError.
+
+    On the device (engine.TabCut) for a regular file the device does not
+    decline; otherwise, and with ``native=False``, the loop on the host
+    restates the reference.  ``repeatmasker2augustushints.last_path`` names the
+    path the last call took."""
+    clock = _Clock()
+    with open(repeatmasker_gff, 'rb'):  # the reference's plain open
+        pass
+    if native != 'True':
+        why = "native != 'True'"
+    elif not (isinstance(repeatmasker_gff, str) and os.path.isfile(repeatmasker_gff)):
+        why = 'not a regular file'
+    else:
+        text, why = _tabcut_native(repeatmasker_gff, engine.TabCut.HINTS, clock)
+        if text is not None:
+            repeatmasker2augustushints.last_path = ('repeatmasker2augustushints', 'native', None)
+            _write_bytes(text)
+            clock.lap('write')
+            clock.emit()
+            return
+    repeatmasker2augustushints.last_path = ('repeatmasker2augustushints', 'host', why)
+    with open(repeatmasker_gff, 'rb') as fh:
+        _write_bytes(*_hints_host(fh.read()))
+    clock.lap('write')
+    clock.emit()
+
+
+repeatmasker2augustushints.last_path = None
+
+
 def _replace_table(table):
     """genome_tools.py:436-440 as bytes: (name, f1) of every line of the table
     in file order.  Lines end at LF only; f1 of a two-field line keeps its LF.
@@ -2061,7 +2168,8 @@ TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at
          'composition_by_site': composition_by_site,
          'heterozygosity_from_vcf': heterozygosity_from_vcf,
          'exclude_from_fasta': exclude_from_fasta, 'fasta2tab': fasta2tab,
-         'replace_names': replace_names, 'convert_gff': convert_gff}
+         'replace_names': replace_names, 'convert_gff': convert_gff, 'tab2fasta': tab2fasta,
+         'repeatmasker2augustushints': repeatmasker2augustushints}
 
 
 def parse_argv(argv):
