@@ -601,6 +601,57 @@ int magot_orfcall_time(magot_ctx* ctx, magot_orfcall* c, int text, int iters, do
 void magot_orfcall_destroy(magot_orfcall* c);
 
 /*
+ * The longest ORF of every record of an executed extraction plan, fused:
+ * Sequence.get_orfs(longest=True) (genome.py:824-851) over the plan's
+ * nucleotide output where it lies in HBM, as get_CDS_peptides asks it of every
+ * CDS (genome_tools.py:283-321).  A record's bytes are what get_seq() returns.
+ * Stream j = 2*frame + (strand == '+') of a record of L bases holds the real
+ * codons only, (L - 2*frame) / 3 of them when L >= 2*frame + 3 (the definition
+ * above magot_orf6_sizes); a residue is lut64[codon] (NULL: the standard
+ * code), 'X' when a base is not one of ACGTacgt; a frame-0 stream loses one
+ * leading 'X' and its residue indices count from the trimmed start.  A None
+ * or empty stream is passed over, as get_orfs passes it over (no
+ * MAGOT_ORF_REC_NONE here).  The winner of a record is the first maximal run
+ * of residues other than '*', in order of j and then of its start, whose
+ * length is the greatest; a record without a non-empty run has none and is
+ * flagged MAGOT_ORF_REC_NO_LONGEST (the reference's IndexError,
+ * genome.py:849).  No stream, ORF table or losing ORF is written to memory.
+ *   magot_longorf_create   p must have MAGOT_OUT_NUC (else MAGOT_ERR_ARG) and
+ *       have been executed (else MAGOT_ERR_STATE), in either layout, and must
+ *       outlive the handle; a record of 2^32 bases or more: MAGOT_ERR_RANGE.
+ *   magot_longorf_execute  the calling pass, a scan of the winners' lengths
+ *       and the pass that writes them; reports the payload's bytes.
+ *   magot_longorf_fetch    one row per record, in record order: stream j,
+ *       start residue k, length (0 for a flagged record), offset in the
+ *       concatenated payload; the payload; one flag byte per record.  Any
+ *       pointer may be NULL.
+ *   magot_longorf_text     the tool's text in one device buffer, for records
+ *       [0, n_print): '>' name '\n' residues '\n' (genome_tools.py:318).
+ *       Record r's name is names[name_off[r], name_off[r+1]) (any bytes).  A
+ *       flagged record among them gets an empty residue line.  *out_len
+ *       receives the size; magot_longorf_text_fetch copies the text down.
+ *   magot_longorf_time     mean device time of the calling passes (text == 0)
+ *       or of the text passes of the last magot_longorf_text (text != 0), an
+ *       event pair around each of `iters` runs.
+ *   magot_longorf_params   the codons per step of the calling pass (a run may
+ *       span any number of steps) and the waves the handle launches, each of
+ *       which strides over the records; with h NULL the most any handle of
+ *       the context launches.
+ */
+typedef struct magot_longorf magot_longorf;
+int magot_longorf_create(magot_ctx* ctx, magot_plan* p, const uint8_t* lut64, magot_longorf** out);
+int magot_longorf_execute(magot_ctx* ctx, magot_longorf* h, uint64_t* payload_bytes);
+int magot_longorf_fetch(magot_ctx* ctx, magot_longorf* h, uint8_t* stream, uint32_t* start,
+                        uint32_t* length, uint64_t* payload_off, uint8_t* payload,
+                        uint8_t* record_flags);
+int magot_longorf_text(magot_ctx* ctx, magot_longorf* h, const uint64_t* name_off,
+                       const uint8_t* names, uint64_t n_print, uint64_t* out_len);
+int magot_longorf_text_fetch(magot_ctx* ctx, magot_longorf* h, uint8_t* out, uint64_t cap);
+int magot_longorf_time(magot_ctx* ctx, magot_longorf* h, int text, int iters, double* avg_ms);
+int magot_longorf_params(magot_ctx* ctx, const magot_longorf* h, uint32_t* step, uint64_t* waves);
+void magot_longorf_destroy(magot_longorf* h);
+
+/*
  * Native batch planner for gff2fasta (genome_tools.py:324-330).
  * Parses GFF3/GTF text with read_gff's rules and default arguments
  * (genome.py:242-415: '#'/8-tab acceptance, version sniffing, ID synthesis
@@ -654,6 +705,44 @@ int magot_gff_read(const char* gff, uint64_t gff_len, uint32_t flags, magot_gffp
 int magot_gff_lower(magot_gffplan* p, const char* const* seqids, const uint64_t* contig_lens,
                     uint32_t n_contigs, const char* feature, uint32_t flags, uint64_t* n_exons,
                     uint64_t* n_tx);
+/*
+ * get_CDS_peptides (genome_tools.py:283-321, its read_gff3 read as read_gff)
+ * lowered from a plan magot_gff_read made (once per plan, else
+ * MAGOT_ERR_STATE): one single-interval record per printed CDS in output
+ * order (magot_gffplan_tables; start_rc clamped as the Python slice clamps,
+ * bit 63 from the CDS's own strand, '.' counting as '+'), and the records'
+ * names.  Genes come in the order of annotations.gene (flags:
+ * MAGOT_GFF_ORDER_PY2, as magot_gff_lower).  A gene is dropped when one of the
+ * n_filters strings is a substring of its ID, or when length_filter is not
+ * NULL and the first record of its get_fasta() has fewer bases.  Per
+ * transcript of a kept gene the CDS children are keyed by coords (a later one
+ * replaces an earlier one), sorted, and reversed when the transcript's strand
+ * is '-'.  names_from: the CDS's ID, or the transcript's or the gene's ID +
+ * "-CDS" + n, n counted from 1 per transcript.  The records of one transcript
+ * form a group: the reference computes every ORF of a transcript before it
+ * writes the first, so an IndexError (MAGOT_ORF_REC_NO_LONGEST from
+ * magot_longorf) cuts the output at the start of its record's group.
+ * MAGOT_ERR_UNSUPPORTED whenever anything in the annotation, dropped genes
+ * included, would take the reference off its straight path (a gene child that
+ * is no transcript, a transcript child that is no CDS, a seqid the genome does
+ * not have, a strand outside + - ., a gene whose get_fasta() has no second
+ * line, a replaced CDS on another seqid than the one that replaces it): the
+ * object path reproduces those.  The gene, transcript and CDS dicts themselves
+ * are missing only where read_gff returns None and leaves no annotations at
+ * all (AttributeError in the reference): magot_gff_read declines such a text,
+ * so it never reaches this call; a model that was read always has the three.
+ *   magot_gffplan_cds_views  name_off (n_rec + 1) into names, and group_off
+ *       (n_groups + 1) into the records; valid while the plan lives.
+ */
+#define MAGOT_CDS_NAMES_CDS 0u
+#define MAGOT_CDS_NAMES_TRANSCRIPT 1u
+#define MAGOT_CDS_NAMES_GENE 2u
+int magot_gff_lower_cds(magot_gffplan* p, const char* const* seqids, const uint64_t* contig_lens,
+                        uint32_t n_contigs, const char* const* filters, uint32_t n_filters,
+                        const int64_t* length_filter, uint32_t names_from, uint32_t flags,
+                        uint64_t* n_rec, uint64_t* n_groups);
+int magot_gffplan_cds_views(const magot_gffplan* p, const uint64_t** name_off,
+                            const uint8_t** names, const uint64_t** group_off);
 /*
  * extract_upstream_downstream (genome_tools.py:457-480) as a plan of the same
  * shape: one single-interval record per printed window (the `sequence_length`

@@ -92,6 +92,9 @@ EXPORTS = (
     'magot_gffwrite_open', 'magot_gffwrite_sizes', 'magot_gffwrite_upload_ms',
     'magot_gffwrite_render', 'magot_gffwrite_render_fetch', 'magot_gffwrite_time',
     'magot_gffwrite_params', 'magot_gffwrite_destroy',
+    'magot_longorf_create', 'magot_longorf_execute', 'magot_longorf_fetch', 'magot_longorf_text',
+    'magot_longorf_text_fetch', 'magot_longorf_time', 'magot_longorf_params',
+    'magot_longorf_destroy', 'magot_gff_lower_cds', 'magot_gffplan_cds_views',
 )
 
 ERR_ARG = -1
@@ -106,6 +109,7 @@ GFF_GENOMIC = 8
 GFF_FROM_EXONS = 16
 GFF_FOR_WRITE = 32
 GFF_FORMATS = {'simple gff3': 0, 'gtf': 1, 'exon added gff3': 2}
+CDS_NAMES = {'CDS': 0, 'transcript': 1, 'gene': 2}  # magot_gff_lower_cds' names_from
 GFFROW_LINE, GFFROW_EXON_TWIN, GFFROW_GTF, GFFROW_MADE_PARENT = 0, 1, 2, 3
 GFFROW_HAS_PARENT = 0x100
 PACK_HOST = 1
@@ -310,6 +314,21 @@ def _declare(lib):
         'magot_orfcall_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_double)]),
         'magot_orfcall_destroy': (None, [_vp]),
+        'magot_longorf_create': (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_vp)]),
+        'magot_longorf_execute': (ctypes.c_int, [_vp, _vp, _u64p]),
+        'magot_longorf_fetch': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        'magot_longorf_text': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _u64p]),
+        'magot_longorf_text_fetch': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64]),
+        'magot_longorf_time': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_double)]),
+        'magot_longorf_params': (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint32), _u64p]),
+        'magot_longorf_destroy': (None, [_vp]),
+        'magot_gff_lower_cds': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_char_p), _u64p,
+                                               ctypes.c_uint32, ctypes.POINTER(ctypes.c_char_p),
+                                               ctypes.c_uint32, _i64p, ctypes.c_uint32,
+                                               ctypes.c_uint32, _u64p, _u64p]),
+        'magot_gffplan_cds_views': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                   ctypes.POINTER(_vp)]),
         'magot_mask_piece': (ctypes.c_uint32, []),
         'magot_mask_plan': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p),
                                            _u64p, ctypes.c_uint32, ctypes.c_char_p,

@@ -24,7 +24,8 @@ SOURCES = ['abi.hip', 'abi_genome.hip', 'abi_plan.hip', 'abi_seq.hip', 'abi_orf.
            'fastq.hip', 'overlap.hip', 'overlapplan.cpp', 'abi_psl.hip', 'psl.hip', 'pslhost.cpp',
            'abi_site.hip', 'sitecount.hip', 'sitehost.cpp', 'abi_vcf.hip', 'vcf.hip',
            'vcfhost.cpp', 'abi_fasta.hip', 'fastarec.hip', 'abi_rename.hip', 'rename.hip',
-           'textindex.hip', 'abi_gffwrite.hip', 'gffwrite.hip', 'abi_tabcut.hip', 'tabcut.hip']
+           'textindex.hip', 'abi_gffwrite.hip', 'gffwrite.hip', 'abi_tabcut.hip', 'tabcut.hip',
+           'abi_longorf.hip', 'longorf.hip']
 HEADERS = ['common.h', 'hostutil.h', 'wavecopy.h', 'abi_internal.h', 'textindex.h',
            os.path.join('..', '..', 'include', 'magot.h')]
 

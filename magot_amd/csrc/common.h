@@ -585,6 +585,44 @@ hipError_t launch_orftext_sizes(const OrfTextArgs& a, hipStream_t s);
 hipError_t launch_orftext_copy(const OrfTextArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// The longest ORF of every record of a plan's nucleotide output, fused
+// (longorf.hip; magot_longorf_*)
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLongOrfStep = 64;  // codons per step: one per lane of a wave
+struct LongOrfArgs {
+  const uint8_t* nuc;     // the plan's nucleotide output
+  const uint64_t* start;  // n: each record's first byte in nuc (the plan's layout)
+  const uint64_t* noff;   // n + 1 record offsets (for the record lengths, all < 2^32)
+  uint64_t n;
+  const uint8_t* lut;     // 64: the library, c0 + 4*c1 + 16*c2 with A=0 C=1 G=2 T=3
+  uint32_t waves;         // launched, a multiple of 4; each strides over the records
+  uint8_t* j;             // n: the winner's stream
+  uint32_t* k;            // n: its start residue (behind a trimmed leading 'X')
+  uint32_t* ku;           // n: its first codon in the stream (the trimmed one counted)
+  uint32_t* len;          // n + 1: its residues, 0 for a flagged record; the last entry 0
+  uint8_t* flags;         // n: 0 or kOrfFlagNoLongest
+  uint64_t* poff;         // n + 1: prefix of len
+  uint8_t* payload;       // poff[n] bytes
+  void* scan_tmp;
+  size_t scan_bytes;
+};
+struct LongOrfTextArgs {
+  uint64_t n_print;          // entries: records [0, n_print)
+  const uint64_t* name_off;  // n_print + 1
+  const uint8_t* names;
+  uint32_t* tlen;            // n_print + 1: bytes of each entry, the last entry 0
+  uint64_t* tstart;          // n_print + 1: their prefix
+  uint8_t* out;
+  void* scan_tmp;
+  size_t scan_bytes;
+};
+size_t longorf_scan_bytes(uint64_t n);
+hipError_t launch_longorf_call(const LongOrfArgs& a, hipStream_t s);   // winners, then poff
+hipError_t launch_longorf_write(const LongOrfArgs& a, hipStream_t s);  // the payload
+hipError_t launch_longorf_text_sizes(const LongOrfArgs& a, const LongOrfTextArgs& t, hipStream_t s);
+hipError_t launch_longorf_text_write(const LongOrfArgs& a, const LongOrfTextArgs& t, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // mask_from_gff (maskplan.cpp, maskgen.hip; magot_mask_*)
 // ---------------------------------------------------------------------------
 constexpr uint32_t kMaskPiece = 2048;  // most bases of one interval piece (maskplan.cpp)

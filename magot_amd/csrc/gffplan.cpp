@@ -1096,6 +1096,9 @@ struct magot_gffplan : magot::Lowered {
   int stage = 0;  // 1: read (magot_gff_read), 2: lowered (magot_gff_lower)
   // magot_gff_lower_write's last result (the blob is the reader's: model.w->blob)
   std::vector<magot_gffrow> w_rows;
+  // magot_gff_lower_cds: record r's name is text[cds_name_off[r], cds_name_off[r+1]);
+  // transcript g printed records [cds_group[g], cds_group[g+1])
+  std::vector<uint64_t> cds_name_off, cds_group;
 };
 
 namespace magot {
@@ -1579,6 +1582,177 @@ int magot_gff_plan(const char* gff, uint64_t gff_len, const char* const* seqids,
     return rc;
   }
   *out = P;
+  return MAGOT_OK;
+}
+
+// get_CDS_peptides (genome_tools.py:283-321, read_gff3 read as read_gff)
+// lowered to one single-interval record per printed CDS, in output order, with
+// the records' names.  Genes in the order of annotations.gene; a gene is
+// dropped when a filter is a substring of its ID, or when length_filter is
+// given and the first record of its get_fasta() is shorter.  Per transcript of
+// a kept gene: its CDS children keyed by coords (a later one replaces an
+// earlier one), sorted, reversed when the transcript's strand is '-'; each
+// record reverse-complemented by its own CDS's strand.  Every way the
+// reference leaves the straight path declines, wherever in the annotation it
+// lies (a dropped gene included): declining too often is safe.  A replaced CDS
+// on another seqid than the one that replaces it declines as well: the
+// reference calls get_orfs on it too, and only on the same seqid is its
+// IndexError the IndexError of the CDS that is kept.
+int magot_gff_lower_cds(magot_gffplan* P, const char* const* seqids, const uint64_t* contig_lens,
+                        uint32_t n_contigs, const char* const* filters, uint32_t n_filters,
+                        const int64_t* length_filter, uint32_t names_from, uint32_t flags,
+                        uint64_t* n_rec, uint64_t* n_groups) {
+  using magot::sv;
+  if (!P || (n_contigs && (!seqids || !contig_lens)) || (n_filters && !filters) ||
+      names_from > MAGOT_CDS_NAMES_GENE) {
+    magot::set_error("magot_gff_lower_cds: null argument or unknown names_from");
+    return MAGOT_ERR_ARG;
+  }
+  if (P->stage != 1) {
+    magot::set_error("magot_gff_lower_cds: plan not read (magot_gff_read) or already lowered");
+    return MAGOT_ERR_STATE;
+  }
+  P->stage = 2;
+  P->protein = false;
+  try {
+    const magot::Model& M = P->model;
+    std::unordered_map<std::string, uint32_t> contig_of;
+    for (uint32_t i = 0; i < n_contigs; ++i) contig_of[seqids[i]] = i;  // last duplicate wins
+    std::vector<int64_t> contig_idx(M.seqids.strs.size(), -1);
+    for (size_t q = 0; q < contig_idx.size(); ++q) {
+      auto ci = contig_of.find(std::string(M.seqids.strs[q]));
+      if (ci != contig_of.end()) contig_idx[q] = ci->second;
+    }
+    std::vector<uint32_t> id_of_feat(M.feats.size(), 0);
+    for (uint32_t t = 0; t < M.tables.size(); ++t)
+      for (uint32_t k : M.tables[t].keys) id_of_feat[(size_t)M.slot(t, k)] = k;
+    uint32_t tab[3];
+    const char* const tab_name[3] = {"gene", "transcript", "CDS"};
+    // AnnotationSet.__init__ (genome.py:529-534) makes the three dicts, as Model()
+    // does: they are missing only where read_gff returns None, and magot_gff_read
+    // has declined such a text already
+    for (int q = 0; q < 3; ++q) tab[q] = M.table_index.at(tab_name[q]);
+    std::vector<uint32_t> keys = M.tables[tab[0]].keys;
+    if (flags & MAGOT_GFF_ORDER_PY2) {  // as magot_gff_lower orders its table
+      std::vector<uint64_t> hash(keys.size());
+      std::vector<uint32_t> pos(keys.size());
+      for (size_t i = 0; i < keys.size(); ++i) {
+        hash[i] = magot::py2_hash(M.ids.strs[keys[i]]);
+        pos[i] = (uint32_t)i;
+      }
+      pos = magot::py2_dict_order(pos, hash);
+      pos = magot::py2_dict_order(pos, hash);
+      std::vector<uint32_t> ordered(pos.size());
+      for (size_t i = 0; i < pos.size(); ++i) ordered[i] = keys[pos[i]];
+      keys.swap(ordered);
+    }
+    struct Cds {
+      std::pair<int64_t, int64_t> coords;
+      magot_exon x;
+      uint32_t id;
+    };
+    std::vector<Cds> by;
+    std::string& names = P->text;
+    char num[24];
+    P->cds_name_off.assign(1, 0);
+    P->cds_group.assign(1, 0);
+    for (uint32_t key : keys) {
+      const uint32_t gi = (uint32_t)M.slot(tab[0], key);
+      const magot::Feature& G = M.feats[gi];
+      if (G.base) throw Unsupported();  // no child_list, no get_fasta
+      const sv gid = M.ids.strs[key];
+      bool keep = true;
+      for (uint32_t f = 0; f < n_filters; ++f)
+        if (gid.find(sv(filters[f])) != sv::npos) keep = false;
+      if (length_filter) {
+        // len(gene.get_fasta().split('\n')[1]): the first record's bases
+        magot::Lowered T;
+        magot::Lowering sub{T, M, false, contig_idx, contig_lens, id_of_feat};
+        if (sub.fasta(gi, true) == 0) throw Unsupported();  // '': IndexError
+        const magot_tx& t0 = T.txs[0];
+        int64_t seqlen = 0;
+        for (uint64_t e = t0.exon_begin; e < t0.exon_begin + t0.n_exons; ++e) seqlen += T.exons[e].len;
+        if (seqlen < *length_filter) keep = false;
+      }
+      for (uint32_t tid : M.children(G)) {
+        const int64_t ti = M.slot(tab[1], tid);
+        if (ti < 0) throw Unsupported();  // KeyError
+        const magot::Feature& T = M.feats[(size_t)ti];
+        if (T.base) throw Unsupported();  // no child_list
+        by.clear();
+        for (uint32_t cid : M.children(T)) {
+          const int64_t ci = M.slot(tab[2], cid);
+          if (ci < 0) throw Unsupported();  // KeyError
+          const magot::Feature& C = M.feats[(size_t)ci];
+          if (!C.base) throw Unsupported();  // no coords, no get_seq
+          const sv sd = M.strands.strs[C.strand];
+          if (sd != "+" && sd != "." && sd != "-") throw Unsupported();  // get_seq prints, None
+          const int64_t cix = contig_idx[C.seqid];
+          if (cix < 0) throw Unsupported();  // get_seq prints, None
+          uint64_t st, ln;
+          magot::Lowering::slice(C.lo - 1, C.hi, (int64_t)contig_lens[cix], &st, &ln);
+          if (ln >= 0xFFFFFFFFull) throw Unsupported();
+          Cds c;
+          c.coords = {C.lo, C.hi};
+          c.x.start_rc = st | (sd == "-" ? magot::kRcBit : 0);
+          c.x.contig = (uint32_t)cix;
+          c.x.len = (uint32_t)ln;
+          c.id = cid;
+          bool found = false;
+          for (Cds& e : by)
+            if (e.coords == c.coords) {
+              if (e.x.contig != c.x.contig) throw Unsupported();
+              e = c;
+              found = true;
+              break;
+            }
+          if (!found) by.push_back(c);
+        }
+        if (!keep) continue;
+        std::stable_sort(by.begin(), by.end(),
+                         [](const Cds& a, const Cds& b) { return a.coords < b.coords; });
+        if (M.strands.strs[T.strand] == "-") std::reverse(by.begin(), by.end());
+        uint64_t counter = 1;
+        for (const Cds& c : by) {
+          if (names_from == MAGOT_CDS_NAMES_CDS) {
+            names += M.ids.strs[c.id];
+          } else {
+            names += names_from == MAGOT_CDS_NAMES_TRANSCRIPT ? M.ids.strs[tid] : gid;
+            const int k = snprintf(num, sizeof num, "-CDS%llu", (unsigned long long)counter++);
+            names.append(num, (size_t)k);
+          }
+          P->cds_name_off.push_back(names.size());
+          magot_tx t;
+          t.exon_begin = P->exons.size();
+          t.n_exons = 1;
+          t.flags = 0;
+          P->exons.push_back(c.x);
+          P->txs.push_back(t);
+        }
+        P->cds_group.push_back(P->txs.size());
+      }
+    }
+  } catch (const Unsupported&) {
+    magot::set_error("magot_gff_lower_cds: input takes a diagnostic path; use the object path");
+    return MAGOT_ERR_UNSUPPORTED;
+  } catch (const std::exception& e) {
+    magot::set_error(std::string("magot_gff_lower_cds: ") + e.what());
+    return MAGOT_ERR_ARG;
+  }
+  if (n_rec) *n_rec = P->txs.size();
+  if (n_groups) *n_groups = P->cds_group.size() - 1;
+  return MAGOT_OK;
+}
+
+int magot_gffplan_cds_views(const magot_gffplan* p, const uint64_t** name_off, const uint8_t** names,
+                            const uint64_t** group_off) {
+  if (!p || p->cds_name_off.empty()) {
+    magot::set_error("magot_gffplan_cds_views: null plan, or not lowered by magot_gff_lower_cds");
+    return MAGOT_ERR_ARG;
+  }
+  if (name_off) *name_off = p->cds_name_off.data();
+  if (names) *names = reinterpret_cast<const uint8_t*>(p->text.data());
+  if (group_off) *group_off = p->cds_group.data();
   return MAGOT_OK;
 }
 

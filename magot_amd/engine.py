@@ -706,6 +706,47 @@ class GffRead(object):
             if h is not None:
                 L.magot_gffplan_destroy(h)
 
+    def lower_cds(self, names, lengths, gene_name_filters=(), gene_length_filter=None,
+                  names_from='CDS', order='insertion'):
+        """get_CDS_peptides lowered (magot_gff_lower_cds): a CdsPlan with one
+        single-interval record per printed CDS in output order, the records'
+        names and the transcript groups, or None when anything in the
+        annotation takes a diagnostic path.  This object gives its handle up.
+        ``gene_name_filters``: strings (a gene whose ID contains one is
+        dropped); ``gene_length_filter``: None or an int; ``names_from``: 'CDS',
+        'transcript' or 'gene'."""
+        if not self.handle:
+            raise MagotError('GffRead.lower_cds: already lowered or closed')
+        if order not in ('insertion', 'py2'):
+            raise ValueError("order must be 'insertion' or 'py2'")
+        L = _lib.lib()
+        n = len(names)
+        arr = (ctypes.c_char_p * max(n, 1))(*[_as_bytes(x) for x in names])
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+        filters = [_as_bytes(f) for f in gene_name_filters]
+        if any(b'\0' in f for f in filters):
+            raise ValueError('a filter with a NUL byte')
+        farr = (ctypes.c_char_p * max(len(filters), 1))(*filters)
+        glf = None if gene_length_filter is None else ctypes.c_int64(int(gene_length_filter))
+        nr, ng = ctypes.c_uint64(), ctypes.c_uint64()
+        h, self.handle = self.handle, None
+        try:
+            rc = L.magot_gff_lower_cds(h, arr, lens.ctypes.data_as(_lib._u64p), n, farr,
+                                       len(filters), ctypes.byref(glf) if glf is not None else None,
+                                       _lib.CDS_NAMES[names_from],
+                                       _lib.GFF_ORDER_PY2 if order == 'py2' else 0,
+                                       ctypes.byref(nr), ctypes.byref(ng))
+            if rc == _lib.ERR_UNSUPPORTED:
+                return None
+            check(rc, 'magot_gff_lower_cds')
+            plan = CdsPlan(h, nr.value, ng.value)
+            h = None
+            return plan
+        finally:
+            self._text = None
+            if h is not None:
+                L.magot_gffplan_destroy(h)
+
     def lower_write(self, gff_format='simple gff3', order='insertion'):
         """write_gff lowered to output rows (magot_gff_lower_write): a
         GffWritePlan, or None when the walk takes a diagnostic path.  The
@@ -740,6 +781,36 @@ class GffRead(object):
             self.close()
         except Exception:
             pass
+
+
+class CdsPlan(object):
+    """What GffRead.lower_cds made: ``exons`` / ``txs`` (one single-interval
+    record per printed CDS, in output order), ``name_off`` (n + 1) into
+    ``names`` (uint8) and ``group_off``: transcript g printed the records
+    [group_off[g], group_off[g + 1]).  Copies: the native plan is freed."""
+
+    def __init__(self, handle, n_rec, n_groups):
+        L = _lib.lib()
+        try:
+            ep, tp = ctypes.c_void_p(), ctypes.c_void_p()
+            check(L.magot_gffplan_table_views(handle, ctypes.byref(ep), ctypes.byref(tp)),
+                  'magot_gffplan_table_views')
+            self.exons = _view(ep.value, n_rec, EXON_DTYPE).copy()
+            self.txs = _view(tp.value, n_rec, TX_DTYPE).copy()
+            no, nm, go = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            check(L.magot_gffplan_cds_views(handle, ctypes.byref(no), ctypes.byref(nm),
+                                            ctypes.byref(go)), 'magot_gffplan_cds_views')
+            self.name_off = _view(no.value, n_rec + 1, np.uint64).copy()
+            self.names = _view(nm.value, int(self.name_off[-1]), np.uint8).copy()
+            self.group_off = _view(go.value, n_groups + 1, np.uint64).copy()
+        finally:
+            L.magot_gffplan_destroy(handle)
+        self.n_records = n_rec
+
+    def name_list(self):
+        raw = self.names.tobytes()
+        o = self.name_off
+        return [raw[int(o[i]):int(o[i + 1])] for i in range(self.n_records)]
 
 
 class GffWritePlan(object):
@@ -1132,6 +1203,125 @@ class OrfCalls(object):
     def close(self):
         if getattr(self, 'handle', None):
             _lib.lib().magot_orfcall_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+LONGORF_TABLE_DTYPE = np.dtype([('stream', 'u1'), ('start', '<u4'), ('length', '<u4'),
+                                ('payload_off', '<u8')])
+
+
+class LongestOrfs(object):
+    """The longest six-frame ORF of every record of an executed ExtractionPlan
+    with OUT_NUC (magot_longorf_*): Sequence.get_orfs(longest=True)
+    (genome.py:824-851) over the plan's nucleotide output where it lies in
+    HBM, in one fused pass that writes no stream and no losing ORF.
+    ``table()`` gives one row per record in record order (stream j = 2*frame +
+    (strand == '+'), start residue, length, payload offset), the concatenated
+    winners and a flag byte per record (_lib.ORF_REC_NO_LONGEST: no candidate,
+    the reference's IndexError; its row has length 0).  ``text(names,
+    n_print)`` gives '>name\\nORF\\n' for the first ``n_print`` records,
+    assembled on the device."""
+
+    def __init__(self, plan, lut64=None):
+        self.ctx = plan.ctx
+        self._keep = plan
+        self.n_records = plan.n_tx
+        lut = np.frombuffer(bytes(lut64), dtype=np.uint8).copy() if lut64 is not None else None
+        if lut is not None and len(lut) != 64:
+            raise ValueError('lut64 holds 64 residues')
+        L = _lib.lib()
+        h = ctypes.c_void_p()
+        check(L.magot_longorf_create(self.ctx.handle, plan.handle, ptr(lut), ctypes.byref(h)),
+              'magot_longorf_create')
+        self.handle = h
+        pb = ctypes.c_uint64()
+        check(L.magot_longorf_execute(self.ctx.handle, h, ctypes.byref(pb)),
+              'magot_longorf_execute')
+        self.payload_bytes = pb.value
+
+    def table(self):
+        """(rows LONGORF_TABLE_DTYPE[n_records], payload uint8[payload_bytes],
+        record flags uint8[n_records])."""
+        n = self.n_records
+        st = np.empty(max(n, 1), np.uint8)
+        k = np.empty(max(n, 1), np.uint32)
+        ln = np.empty(max(n, 1), np.uint32)
+        po = np.empty(max(n, 1), np.uint64)
+        pay = np.empty(max(self.payload_bytes, 1), np.uint8)
+        fl = np.zeros(max(n, 1), np.uint8)
+        check(_lib.lib().magot_longorf_fetch(self.ctx.handle, self.handle, ptr(st), ptr(k),
+                                             ptr(ln), ptr(po), ptr(pay), ptr(fl)),
+              'magot_longorf_fetch')
+        rows = np.empty(n, LONGORF_TABLE_DTYPE)
+        rows['stream'], rows['start'] = st[:n], k[:n]
+        rows['length'], rows['payload_off'] = ln[:n], po[:n]
+        return rows, pay[:self.payload_bytes], fl[:n]
+
+    def flags(self):
+        """The flag byte of every record."""
+        fl = np.zeros(max(self.n_records, 1), np.uint8)
+        check(_lib.lib().magot_longorf_fetch(self.ctx.handle, self.handle, None, None, None,
+                                             None, None, ptr(fl)), 'magot_longorf_fetch')
+        return fl[:self.n_records]
+
+    def text(self, names, n_print=None):
+        """The text (a uint8 array) '>name\\nORF\\n' of records [0, n_print)
+        (all of them by default) for one name per record (str or bytes)."""
+        if len(names) != self.n_records:
+            raise ValueError('one name per record')
+        n_print = self.n_records if n_print is None else int(n_print)
+        if not 0 <= n_print <= self.n_records:
+            raise ValueError('n_print outside [0, records]')
+        buf, off = _concat(names[:n_print])
+        return self.text_blob(buf, off, n_print)
+
+    def text_blob(self, buf, off, n_print):
+        """``text`` with the names as a uint8 blob and uint64 offsets
+        (``n_print`` + 1 of them at least)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if not 0 <= n_print <= self.n_records or len(off) < n_print + 1 or \
+                (n_print and int(off[n_print]) > len(buf)):
+            raise ValueError('n_print or the name table does not fit')
+        size = ctypes.c_uint64()
+        L = _lib.lib()
+        check(L.magot_longorf_text(self.ctx.handle, self.handle, ptr(off),
+                                   ptr(buf) if len(buf) else None, n_print, ctypes.byref(size)),
+              'magot_longorf_text')
+        out = np.empty(max(size.value, 1), np.uint8)
+        check(L.magot_longorf_text_fetch(self.ctx.handle, self.handle, ptr(out), size.value),
+              'magot_longorf_text_fetch')
+        return out[:size.value]
+
+    def time(self, iters, text=False):
+        """Mean device time (ms) of the calling passes, or with ``text`` of the
+        text passes of the last ``text()`` call."""
+        ms = ctypes.c_double()
+        check(_lib.lib().magot_longorf_time(self.ctx.handle, self.handle, int(bool(text)),
+                                            int(iters), ctypes.byref(ms)), 'magot_longorf_time')
+        return ms.value
+
+    def params(self):
+        """{'step': codons per step of the calling pass, 'waves': waves this
+        handle launches, 'max_waves': the most any handle of the context does}."""
+        L = _lib.lib()
+        step, w, mw = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(L.magot_longorf_params(self.ctx.handle, self.handle, ctypes.byref(step),
+                                     ctypes.byref(w)), 'magot_longorf_params')
+        check(L.magot_longorf_params(self.ctx.handle, None, None, ctypes.byref(mw)),
+              'magot_longorf_params')
+        return {'step': step.value, 'waves': w.value, 'max_waves': mw.value}
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.lib().magot_longorf_destroy(self.handle)
             self.handle = None
         self._keep = None
 
@@ -2721,4 +2911,5 @@ __all__ = ['DeviceGenome', 'ExtractionPlan', 'revcomp_batch', 'translate_batch',
            'OUT_PEP', 'MagotError', 'GffPlan', 'orf6_batch', 'Orf6Plan', 'fasta_read',
            'FastaGenome', 'PartitionedGenome', 'device_genome', 'extract_records', 'plan_parts',
            'copy_segments', 'orf6_sizes', 'OrfCalls', 'ORFCALL_TILE', 'ORF_TABLE_DTYPE',
+           'LongestOrfs', 'LONGORF_TABLE_DTYPE', 'CdsPlan',
            'GenomeTrack', 'TrackWindows', 'interval_pieces', 'ReadLengths']

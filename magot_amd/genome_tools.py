@@ -34,6 +34,9 @@
            [order=py2|insertion] [native=False]
     python -m magot_amd.genome_tools tab2fasta <table.tab> [native=False]
     python -m magot_amd.genome_tools repeatmasker2augustushints <repeatmasker.gff> [native=False]
+    python -m magot_amd.genome_tools get_CDS_peptides <fasta> <gff> <out.fasta>
+           [gene_name_filters=<characters>] [gene_length_filter=<bases>]
+           [names_from=CDS|transcript|gene] [order=py2|insertion] [native=False]
 
 Arguments follow the reference's CLI convention (genome_tools.py:25-45):
 positional values, then ``key=value`` pairs, all strings.  The reference
@@ -51,6 +54,7 @@ import ast
 import ctypes
 import json
 import os
+import re
 import sys
 import time
 
@@ -680,6 +684,189 @@ def _dna2orfs_contig(out, name, length, six, from_atg, longest):
                            '\n').encode('latin-1'))
     if longest:
         out.write(candidates[-1].encode('latin-1'))
+
+
+_CDSPEP_INT = re.compile(r'\s*[+-]?[0-9]+\s*\Z')
+
+
+def get_CDS_peptides(genome_sequence, gff, output_location, gene_name_filters=[],
+                     gene_length_filter=None, names_from='CDS', order='py2', native='True'):
+    """genome_tools.py:283-321: for every CDS feature of every kept gene, the
+    longest six-frame ORF of that CDS ('>name\\nORF\\n'), the exon peptides that
+    prep4apollo maps with tblastn.
+
+    One deliberate deviation: the reference calls ``Genome.read_gff3``, which
+    does not exist, and dies there; here it is ``read_gff``,
+    with which the rest of the function runs.
+
+    A gene is dropped when an element of ``gene_name_filters`` is a substring
+    of its ID (from the command line the argument is a string, and every
+    character is a filter, as in the reference), or when ``gene_length_filter``
+    is given and the first record of its ``get_fasta()`` is shorter.
+    ``names_from``: 'CDS' (the CDS's ID), 'transcript' or 'gene' (that ID +
+    '-CDS' + n).  Genes come in the reference's Python 2 dict order unless
+    ``order='insertion'``.
+
+    On the device (engine.LongestOrfs over one extraction plan, one record per
+    printed CDS) when the host planner can lower the annotation; a CDS without
+    any ORF (IndexError in the reference) is found from the kernel's flags, and
+    the file holds what the reference had written before it.  Every other way
+    the reference leaves the straight path, and ``native=False``, take the
+    object path, which restates the reference.  Nothing is written before the
+    path is known.  ``get_CDS_peptides.last_path`` names the path the last call
+    took."""
+    if order not in ('py2', 'insertion'):
+        raise ValueError("order must be 'py2' or 'insertion'")
+    filters = list(gene_name_filters)
+    result = None
+    if native != 'True':
+        why = "native != 'True'"
+    elif names_from not in ('CDS', 'transcript', 'gene'):
+        why = 'invalid names_from'
+    elif not all(isinstance(f, str) for f in filters):
+        why = 'a filter that is not a string'
+    elif not (gene_length_filter is None or type(gene_length_filter) is int or
+              (isinstance(gene_length_filter, str) and _CDSPEP_INT.match(gene_length_filter))):
+        why = 'bad integer'
+    elif not all(isinstance(p, str) and os.path.isfile(p) for p in (genome_sequence, gff)):
+        why = 'not a regular file'
+    else:
+        glf = None if gene_length_filter is None else int(gene_length_filter)
+        if glf is not None and abs(glf) >= 1 << 62:
+            why = 'bad integer'
+        else:
+            result, why = _cds_peptides_native(genome_sequence, gff, filters, glf, names_from, order)
+    if result is not None:
+        get_CDS_peptides.last_path = ('get_CDS_peptides', 'native', None)
+        text, failed = result
+        with open(output_location, 'wb') as out:
+            out.write(text)
+        if failed:
+            raise IndexError('list index out of range')
+        return
+    get_CDS_peptides.last_path = ('get_CDS_peptides', 'host', why)
+    _cds_peptides_host(genome_sequence, gff, output_location, filters, gene_length_filter,
+                       names_from, order)
+
+
+get_CDS_peptides.last_path = None
+
+
+def _cds_peptides_native(genome_sequence, gff, filters, glf, names_from, order):
+    """((text bytes, whether the reference raises IndexError behind it), None),
+    or (None, why) where the planner or the device path declines."""
+    dev = engine.FastaGenome.load(genome.read_buffer(genome_sequence))
+    if dev is None:
+        return None, 'the FASTA needs the Python reader'
+    read = ex = calls = None
+    try:
+        if dev.total_bases > engine.PART_BASES:
+            return None, 'a genome above one device plane'
+        read = engine.GffRead.read(genome.read_buffer(gff))
+        if read is None:
+            return None, 'read_gff takes a diagnostic path'
+        plan = read.lower_cds(dev.names, dev.lengths, filters, glf, names_from, order)
+        if plan is None:
+            return None, 'the annotation takes a diagnostic path'
+        if not plan.n_records:
+            return (b'', False), None
+        ex = engine.ExtractionPlan(dev, plan.exons, plan.txs,
+                                   engine.OUT_NUC | engine.OUT_GENOME_ORDER)
+        ex.execute()
+        calls = engine.LongestOrfs(ex)
+        flagged = np.flatnonzero(calls.flags())
+        n_print = plan.n_records
+        if len(flagged):
+            # the reference computes every ORF of a transcript before it writes
+            # the first: the output ends where the failing record's group begins
+            g = int(np.searchsorted(plan.group_off, flagged[0], side='right')) - 1
+            n_print = int(plan.group_off[g])
+        text = calls.text_blob(plan.names, plan.name_off, n_print).tobytes()
+        return (text, bool(len(flagged))), None
+    finally:
+        for obj in (calls, ex, read, dev):
+            if obj is not None:
+                obj.close()
+
+
+def _cds_peptides_host(genome_sequence, gff, output_location, filters, gene_length_filter,
+                       names_from, order):
+    """The reference's loop over the annotation objects.  The walk collects
+    every CDS sequence up to the first exception, one six-frame launch
+    translates them all, and the replay writes what the reference writes and
+    raises what it raises, in its order.
+
+    One difference, on stdout only: the walk does not know yet which CDS has no
+    ORF, so it goes on past one that will raise IndexError, and a diagnostic
+    that ``get_seq()`` or ``get_fasta()`` prints for a later gene (a seqid the
+    genome does not have, say) is printed although the reference had raised
+    before it.  The exception and the file are the reference's."""
+    g = genome.Genome(genome_sequence)
+    g.read_gff(gff)
+    ann = g.annotations
+    genes = list(ann.gene)
+    if order == 'py2':
+        genes = genome.order_after_copies(genes, ann.__dict__.get('_magot_copies', 0))
+    work = []       # per transcript: [gene ID, ID, strand, {coords: (CDS ID, seq index)}, seqs, whole]
+    pending = None  # the exception the walk met: raised behind what precedes it
+    try:
+        for gene in genes:
+            gene_obj = ann.gene[gene]
+            keepgene = True
+            for name_filter in filters:
+                if name_filter in gene_obj.ID:
+                    keepgene = False
+            if gene_length_filter != None:  # noqa: E711
+                seqlen = len(gene_obj.get_fasta().split('\n')[1])
+                if isinstance(gene_length_filter, str) and '_' in gene_length_filter:
+                    raise ValueError("invalid literal for int() with base 10: %r"
+                                     % gene_length_filter)
+                if seqlen < int(gene_length_filter):
+                    keepgene = False
+            if keepgene:
+                for transcript in gene_obj.child_list:
+                    transcript_obj = ann.transcript[transcript]
+                    entry = [gene_obj.ID, transcript_obj.ID, transcript_obj.strand, {}, [], False]
+                    work.append(entry)
+                    for CDS in transcript_obj.child_list:
+                        CDS_obj = ann.CDS[CDS]
+                        seq = CDS_obj.get_seq()
+                        if seq is None:
+                            raise AttributeError("'NoneType' object has no attribute 'get_orfs'")
+                        entry[3][CDS_obj.coords] = (CDS_obj.ID, len(entry[4]))
+                        entry[4].append(str(seq))
+                    entry[5] = True
+    except Exception as e:  # noqa: BLE001
+        pending = e
+    seqs = [s for entry in work for s in entry[4]]
+    sixes = engine.orf6_batch(seqs) if seqs else []
+    at = 0
+    with open(output_location, 'wb') as out:
+        for gene_id, transcript_id, strand, CDSdict, tseqs, whole in work:
+            orfs = [genome._orfs_from_translations(sixes[at + i], True, False)
+                    for i in range(len(tseqs))]  # IndexError: no candidate
+            at += len(tseqs)
+            if not whole:
+                break
+            CDSlist = sorted(CDSdict)
+            if strand == "-":
+                CDSlist.reverse()
+            counter = 1
+            for CDS in CDSlist:
+                if names_from == 'CDS':
+                    pep_name = CDSdict[CDS][0]
+                elif names_from == 'transcript':
+                    pep_name = transcript_id + '-CDS' + str(counter)
+                    counter = counter + 1
+                elif names_from == 'gene':
+                    pep_name = gene_id + '-CDS' + str(counter)
+                    counter = counter + 1
+                else:
+                    _write("invalid option for 'names_from' argument\n")
+                    break
+                out.write(('>' + pep_name + '\n' + orfs[CDSdict[CDS][1]] + '\n').encode('latin-1'))
+    if pending is not None:
+        raise pending
 
 
 _MASK_OVERWRITE = ('True', 'T', 'true', 't', 'TRUE')
@@ -2169,7 +2356,8 @@ TOOLS = {'gff2fasta': gff2fasta, 'cds2pep': cds2pep, 'at_content_from_fasta': at
          'heterozygosity_from_vcf': heterozygosity_from_vcf,
          'exclude_from_fasta': exclude_from_fasta, 'fasta2tab': fasta2tab,
          'replace_names': replace_names, 'convert_gff': convert_gff, 'tab2fasta': tab2fasta,
-         'repeatmasker2augustushints': repeatmasker2augustushints}
+         'repeatmasker2augustushints': repeatmasker2augustushints,
+         'get_CDS_peptides': get_CDS_peptides}
 
 
 def parse_argv(argv):
